@@ -215,6 +215,32 @@ def check_losses(ref, it, lf, lg):
                 bounds=list(LOSS_TOL), ok=bool(ef <= LOSS_TOL[0] and eg <= LOSS_TOL[1]))
 
 
+DUMP_SAMPLE = 1 << 20          # --dump-outputs: elements drawn from each flat fp32 buffer (~4 MB per file, ~28 MB in all)
+DUMP_SEED = 0
+
+
+def dump_outputs(path, S, lf, lg):
+    """--dump-outputs DIR: what the last timed step computed, as a caller of SiDStep.iteration receives it -- the two losses it
+    returns and the state it updates in place (the weights of G, the fake-score network and G's EMA; the Adam second moments of
+    both optimizers, which carry the step's gradients: one step moves a weight by only ~lr) -- as DIR/<name>.npy.  The flat
+    buffers (~860 M elements at full size) are read at one fixed, seeded set of indices, DIR/sample_index.npy.  The bf16 path is not
+    bit-reproducible (atomically reduced gradients): two runs of one build at the default workload differed by ~1e-4 relative in the
+    losses, a few lr in the weights and ~4e-3 relative (L2) in the second moments -- compare with a tolerance of that order."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    n = S.G.flat_params.numel()
+    idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_SAMPLE))
+    sel = torch.from_numpy(idx).to(S.G.flat_params.device)
+    out = {'loss_fake': lf.detach().float().reshape(1), 'loss_G': lg.detach().float().reshape(1)}
+    for name, buf in (('G_params', S.G.flat_params), ('fake_score_params', S.psi.flat_params), ('G_ema_params', S.G_ema.flat_params),
+                      ('G_adam_exp_avg_sq', S.step.opt_G.exp_avg_sq), ('fake_score_adam_exp_avg_sq', S.step.opt_fake.exp_avg_sq)):
+        assert buf.numel() == n and buf.dtype == torch.float32, name
+        out[name] = buf.index_select(0, sel)
+    for name, t in out.items():
+        np.save(os.path.join(path, name + '.npy'), t.cpu().numpy())
+    np.save(os.path.join(path, 'sample_index.npy'), idx.astype(np.float64))      # (exact: n < 2^53)
+
+
 class _Setup:
     pass
 
@@ -313,6 +339,9 @@ def main():
                          '`comm` then reports how long the compute stream stood still for it (no xGMI traffic: a lower bound)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-kernel-timing', action='store_true')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the last timed step computed (losses; a fixed, seeded sample of the updated '
+                         'weights and Adam second moments) to DIR/<name>.npy, for comparing two builds on identical inputs (rank 0)')
     args = ap.parse_args()
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -405,6 +434,8 @@ def main():
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         dt = float(tt)
+    if args.dump_outputs and rank == 0:          # before the iterations below move the weights on
+        dump_outputs(args.dump_outputs, S, lf, lg)
     t_host = None
     if S.use_graph:                  # per-kernel events cannot see inside a graph launch: sample eager iterations now
         hs = time.time()

@@ -154,6 +154,36 @@ def test_bench_under_torchrun_two_ranks(dev):
     assert out['loss_check'] in ('ok', 'no reference stored for this configuration')
 
 
+def test_bench_dump_outputs_are_reproducible(dev, tmp_path):
+    """`bench.py --dump-outputs DIR`: two runs with the same arguments draw the same inputs, so what their last timed steps computed
+    (losses, sampled weights and Adam second moments) agrees up to the bf16 path's run-to-run spread; the
+    files are float32 / float64, under 64 MB, and the dumped losses are the ones the JSON line reports."""
+    flags = ('--steps', '3', '--warmup', '1', '--batch-gpu', '2', '--arch', 'tiny40', '--resolution', '128', '--no-cpu-baseline',
+             '--no-kernel-timing')
+    runs = []
+    for i in range(2):
+        d = tmp_path / f'dump{i}'
+        out = _run_bench(1, *flags, '--dump-outputs', str(d), env_extra=dict(SIDLSG_BENCH_DETAIL=str(tmp_path / f'detail{i}.json')))
+        assert out['steps'] == 3 and out['ms_per_step'] > 0
+        files = sorted(os.listdir(d))
+        arrays = {f[:-len('.npy')]: np.load(d / f) for f in files}
+        assert all(f.endswith('.npy') for f in files) and sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        assert all(a.dtype in (np.float32, np.float64) and a.size > 0 and np.isfinite(a).all() for a in arrays.values())
+        for k in ('loss_fake', 'loss_G'):
+            assert abs(float(arrays[k][0]) - out[k]) <= 1e-4 * max(1.0, abs(out[k])), k      # (the line carries 4 decimals)
+        runs.append(arrays)
+    a, b = runs
+    assert set(a) == set(b) == {'loss_fake', 'loss_G', 'G_params', 'fake_score_params', 'G_ema_params', 'G_adam_exp_avg_sq',
+                                'fake_score_adam_exp_avg_sq', 'sample_index'}
+    np.testing.assert_array_equal(a['sample_index'], b['sample_index'])
+    for k in ('loss_fake', 'loss_G'):
+        np.testing.assert_allclose(b[k], a[k], rtol=1e-3, err_msg=k)
+    # (bf16 run-to-run spread, bench.dump_outputs; two full-size runs on two boxes met this bound, tiny40 runs were bit-equal)
+    for k in ('G_params', 'fake_score_params', 'G_ema_params', 'G_adam_exp_avg_sq', 'fake_score_adam_exp_avg_sq'):
+        print(f'{k}: max |difference| {np.abs(b[k] - a[k]).max():.3g} of max |value| {np.abs(a[k]).max():.3g}')
+        np.testing.assert_allclose(b[k], a[k], rtol=1e-2, atol=1e-3 * float(np.abs(a[k]).max()), err_msg=k)
+
+
 def test_rccl_world1_timing_of_the_full_size_messages(dev, tmp_path):
     """The exchange of one full-size network (859.5 M fp32 gradients = 4 messages of 0.86 GB) through RCCL at world size 1
     (collectives forced): message count / bytes / rate and the exposed wait as FlatGradReducer reports them -- the figures

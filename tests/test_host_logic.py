@@ -11,6 +11,10 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# The two-rank gloo runs below test the CPU path, so their workers see no GPU on a GPU host either: sid_lsg_amd.distributed.init
+# binds rank r to cuda:r whenever a GPU is visible, and a one-GPU host has no cuda:1 (HIP drops a device list from its first invalid
+# ordinal on, so -1 leaves none)
+CPU_WORKER_ENV = dict(HIP_VISIBLE_DEVICES='-1', MASTER_ADDR='127.0.0.1')
 
 
 def test_library_exports_every_header_symbol():
@@ -234,7 +238,7 @@ assert not torch.equal(g3, want)          # it IS a lossy exchange: off by defau
 assert dist.FlatGradReducer().exchange_dtype == torch.float32
 dist.print0("REDUCER_OK", world)
 ''')
-    env = dict(os.environ, MASTER_ADDR='127.0.0.1')
+    env = dict(os.environ, **CPU_WORKER_ENV)
     out = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr',
                           '127.0.0.1', '--master-port', '29631', str(script)], capture_output=True, text=True, env=env, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -423,7 +427,7 @@ dist.print0("METRICS_OK", dist.get_world_size(), float(metrics.frechet_distance(
 ''')
     out = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr',
                           '127.0.0.1', '--master-port', '29633', str(script)], capture_output=True, text=True,
-                         env=dict(os.environ, MASTER_ADDR='127.0.0.1'), timeout=300)
+                         env=dict(os.environ, **CPU_WORKER_ENV), timeout=300)
     assert out.returncode == 0 and 'METRICS_OK 2' in out.stdout, out.stdout[-1000:] + out.stderr[-2000:]
 
 
