@@ -7,7 +7,9 @@
 Same options and file layout as the reference (`generate_onestep.py:113-125, 218-311`): image i uses prompt line i and the
 latent drawn from torch.Generator(seed_i) (`StackedRandomGenerator`), x_hat = G(z; t_init) in one UNet evaluation,
 `vae.decode(x_hat / scaling_factor)`, uint8 `(img*127.5+128).clip(0,255)` PNG named `<seed:06d>.png`.  Batches are strided
-over ranks.  `--repo_id` must be a local diffusers-layout directory (text encoder, tokenizer, VAE) or `random:<arch>`.
+over ranks.  `--repo_id` must be a local diffusers-layout directory (text encoder, tokenizer, VAE, scheduler) or `random:<arch>`
+(`random:<arch>:v` for a v-prediction model); its parameterisation must be the snapshot's.  `--resolution` is the image size
+(latent = resolution / 8; 768 for an SD 2.x 768-v generator).
 """
 import os
 import pickle
@@ -18,7 +20,7 @@ import numpy as np
 import torch
 
 from sid_lsg_amd import distributed as dist
-from sid_lsg_amd.sd_util import load_sd15, sid_sd_sampler
+from sid_lsg_amd.sd_util import check_prediction_type, load_sd15, sid_sd_sampler
 
 
 class StackedRandomGenerator:
@@ -74,13 +76,16 @@ def save_png(path, hwc_uint8):
 @click.option('--num', 'num_fid_samples', type=click.IntRange(min=1), default=30000, show_default=True, help='Maximum number of images')
 @click.option('--init_timestep', type=click.IntRange(min=0), default=625, show_default=True, help='t_init, in [0,999]')
 @click.option('--text_prompts', type=str, default='prompts/captions.txt', show_default=True, help='Prompt file, one per line')
-@click.option('--repo_id', type=str, default='runwayml/stable-diffusion-v1-5', show_default=True, help='Local diffusers directory or random:<arch>')
+@click.option('--repo_id', type=str, default='runwayml/stable-diffusion-v1-5', show_default=True, help='Local diffusers directory, random:<arch> or random:<arch>:v')
+@click.option('--resolution', type=click.IntRange(min=8), default=512, show_default=True, help='Image resolution (latent = resolution / 8)')
 @click.option('--use_fp16', type=bool, default=True, show_default=True, help='Accepted for compatibility (compute is bf16)')
 @click.option('--enable_compress_npz', type=bool, default=False, show_default=True, help='Also write the batch as images.npz')
 @click.option('--num_steps_eval', type=click.IntRange(min=0), default=1, show_default=True, help='Generation steps (1 = one-step)')
 @click.option('--custom_seed', type=bool, default=False, show_default=True, help='Prompt i <-> i-th seed of the list instead of seed value')
-def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, init_timestep, text_prompts, repo_id, use_fp16,
+def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, init_timestep, text_prompts, repo_id, resolution, use_fp16,
          enable_compress_npz, num_steps_eval, custom_seed):
+    if resolution % 8:
+        raise click.BadParameter(f'{resolution}: must be a multiple of 8', param_hint='--resolution')
     dist.init()
     device = torch.device('cuda')
     rank, world = dist.get_rank(), dist.get_world_size()
@@ -98,12 +103,13 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
     G_ema.eval().requires_grad_(False)
     _, vae, sched, text_encoder, tokenizer = load_sd15(repo_id, repo_id, device, torch.bfloat16)
     del _
+    check_prediction_type(G_ema, sched)       # a v snapshot with an epsilon --repo_id (or the reverse) would sample garbage
     if world > 1 and rank == 0:
         torch.distributed.barrier()
     if num_steps_eval > 1:
         outdir = f'{outdir}_numstep{num_steps_eval}'
 
-    lat = 64
+    lat = resolution // 8
     dist.print0(f'Generating {len(seeds)} images to "{outdir}"...')
     for batch in rank_batches:
         if world > 1:
@@ -117,7 +123,7 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
         with torch.no_grad():
             images = sid_sd_sampler(unet=G_ema, latents=z, contexts=prompts,
                                     init_timesteps=init_timestep * torch.ones(len(batch), device=device, dtype=torch.long),
-                                    noise_scheduler=sched, text_encoder=text_encoder, tokenizer=tokenizer, resolution=512,
+                                    noise_scheduler=sched, text_encoder=text_encoder, tokenizer=tokenizer, resolution=resolution,
                                     dtype=torch.bfloat16, return_images=True, vae=vae, num_steps=1, train_sampler=False,
                                     num_steps_eval=num_steps_eval)
         arr = (images.float() * 127.5 + 128).clip(0, 255).to(torch.uint8).permute(0, 2, 3, 1).cpu().numpy()

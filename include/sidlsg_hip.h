@@ -203,16 +203,19 @@ int sidlsg_attn_bwd_ps(const void* Q, const void* K, const void* V, const void* 
  * noisy_input: x_t = s0[b]*x0 + s1[b]*noise (x0 NULL -> zeros: the one-step generator input),
  *   NCHW fp32 in, NHWC bf16 [dup*B][HW][Cp] out (dup=2: [uncond ; cond] halves of the CFG batch),
  *   optional fp32 NCHW copy of x_t.
- * cfg_x0: eps [dup*B][HW][Ce>=C] fp32 -> out NCHW fp32 = predict_x0 ? (x_t - s1*e)/s0 : e with
- *   e = u + kappa*(c-u) when dup=2. */
+ * cfg_x0: eps [dup*B][HW][Ce>=C] fp32 -> out NCHW fp32, e = u + kappa*(c-u) when dup=2, by `mode`
+ *   (the network's parameterisation):  0 raw: e;  1 x0 from epsilon: (x_t - s1*e)/s0;  2 x0 from v: s0*x_t - s1*e.
+ *   Modes 0 and 1 are the former predict_x0 = 0 / 1.  Any other mode -> SIDLSG_EINVAL.
+ * cfg_x0_bwd: d_eps NHWC [dup*B][HW][Cp] (zero padded) and, when dxt != NULL, d_xt fp32 NCHW:
+ *   mode 0: d_e = g, d_xt = 0;  1: d_e = -s1/s0*g, d_xt = g/s0;  2: d_e = -s1*g, d_xt = s0*g. */
 int sidlsg_noisy_input(const float* x0, const float* noise, const float* s0, const float* s1, void* out, float* xt, int B,
                        int C, int HW, int Cp, int dup, void* stream);
 int sidlsg_noisy_input_bwd(const void* g, const float* s0, float* dx0, int B, int C, int HW, int Cp, int dup, int accumulate,
                            void* stream);
 int sidlsg_cfg_x0(const float* eps, const float* xt, const float* s0, const float* s1, float* out, int B, int C, int HW,
-                  int Ce, int dup, float kappa, int predict_x0, void* stream);
+                  int Ce, int dup, float kappa, int mode, void* stream);
 int sidlsg_cfg_x0_bwd(const float* g, const float* s0, const float* s1, void* deps, float* dxt, int B, int C, int HW, int Cp,
-                      int dup, float kappa, int predict_x0, void* stream);
+                      int dup, float kappa, int mode, void* stream);
 
 /* ---- losses with closed-form gradients (sid_training_loop.py:423-445, 508-530) -------------
  * Per-sample NaN filtering is done in-kernel (a sample containing NaN contributes 0 and gets zero
@@ -221,6 +224,13 @@ int sidlsg_g_loss(const float* x, const float* yr, const float* yf, float* dx, f
                   int S, int n, float alpha, float scale, void* stream);
 int sidlsg_fake_loss(const float* e, const float* noise, float* de, float* loss, float* ws, int S, int n, float scale,
                      void* stream);
+/* v-prediction fake-score loss (sid_training_loop.py:423-445, v branch) of a network output o against the velocity target
+ * v* = s0[s]*noise - s1[s]*x0, formed in-kernel (never written).  o, x0 (the generator's images), noise: [S][n] fp32;
+ * s0, s1, w: [S] fp32 in device memory (w = snr/(snr+1), snr = abar/(1-abar): DDPMScheduler.snr_weights).
+ * loss[0] = scale * sum_s w[s] * sum_i (o - v*)^2 over the samples whose o and v* hold no NaN; de = 2*scale*w[s]*(o - v*),
+ * zero for a dropped sample.  Same two-stage reduction and workspace as sidlsg_fake_loss: ws >= 2*S + 8*S floats. */
+int sidlsg_fake_loss_v(const float* o, const float* x0, const float* noise, const float* s0, const float* s1, const float* w,
+                       float* de, float* loss, float* ws, int S, int n, float scale, void* stream);
 
 /* ---- optimizer: nan_to_num + clip + Adam/AdamW + EMA + bf16 weight copy + zero_grad --------
  * (sid_training_loop.py:458-462, 541-565; sid_train.py:219-226).  hyper: 11 floats in DEVICE memory:
@@ -339,7 +349,7 @@ int sidlsg_noisy_input_f32(const float* x0, const float* noise, const float* s0,
 int sidlsg_noisy_input_bwd_f32(const void* g, const float* s0, float* dx0, int B, int C, int HW, int Cp, int dup,
                                int accumulate, void* stream);
 int sidlsg_cfg_x0_bwd_f32(const float* g, const float* s0, const float* s1, void* deps, float* dxt, int B, int C, int HW,
-                          int Cp, int dup, float kappa, int predict_x0, void* stream);
+                          int Cp, int dup, float kappa, int mode, void* stream);
 int sidlsg_timestep_embed_f32(const long long* t, void* out, int B, int dim, void* stream);
 int sidlsg_silu_fwd_f32(const void* x, void* y, long long n, void* stream);
 int sidlsg_silu_bwd_f32(const void* x, const void* dy, void* dx, long long n, void* stream);

@@ -52,11 +52,16 @@ __global__ void noisy_input_bwd_kernel(const T* __restrict__ g, const float* __r
     }
 }
 
-// CFG combine + optional x0 prediction.  eps: [dup*B][HW][C] fp32 (NHWC, uncond first).
-// out (NCHW fp32) = predict_x0 ? (x_t - s1*e)/s0 : e,   e = dup==2 ? u + kappa*(c-u) : eps
+// CFG combine + optional x0 prediction.  eps: [dup*B][HW][C] fp32 (NHWC, uncond first).  e = dup==2 ? u + kappa*(c-u) : eps
+// MODE (compile time: the epsilon kernels are the same code as before the v mode existed):
+//   0 raw           out = e
+//   1 x0 from eps   out = (x_t - s1*e)/s0
+//   2 x0 from v     out = s0*x_t - s1*e
+// out is NCHW fp32.
+template <int MODE>
 __global__ void cfg_x0_kernel(const float* __restrict__ eps, const float* __restrict__ xt, const float* __restrict__ s0,
                               const float* __restrict__ s1, float* __restrict__ out, int B, int C, int HW, int Ce, int dup,
-                              float kappa, int predict_x0) {
+                              float kappa) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;  // over B*HW
     if (idx >= B * HW) return;
     const int b = idx / HW, p = idx - b * HW;
@@ -64,15 +69,18 @@ __global__ void cfg_x0_kernel(const float* __restrict__ eps, const float* __rest
         float e = eps[((size_t)b * HW + p) * Ce + c];
         if (dup == 2) { const float cnd = eps[((size_t)(B + b) * HW + p) * Ce + c]; e = e + kappa * (cnd - e); }
         const size_t i = ((size_t)b * C + c) * HW + p;
-        out[i] = predict_x0 ? (xt[i] - s1[b] * e) / s0[b] : e;
+        if (MODE == 1) out[i] = (xt[i] - s1[b] * e) / s0[b];
+        else if (MODE == 2) out[i] = s0[b] * xt[i] - s1[b] * e;
+        else out[i] = e;
     }
 }
 
-// backward of cfg_x0: d_eps (NHWC [dup*B][HW][Cp], zero padded) and, when predict_x0, d_xt = g/s0 (fp32 NCHW)
-template <typename T>
+// backward of cfg_x0: d_eps (NHWC [dup*B][HW][Cp], zero padded) and d_xt (fp32 NCHW, may be null):
+//   MODE 0: d_e = g, d_xt = 0;  MODE 1: d_e = -g*s1/s0, d_xt = g/s0;  MODE 2: d_e = -g*s1, d_xt = g*s0
+template <typename T, int MODE>
 __global__ void cfg_x0_bwd_kernel(const float* __restrict__ g, const float* __restrict__ s0, const float* __restrict__ s1,
                                   T* __restrict__ deps, float* __restrict__ dxt, int B, int C, int HW, int Cp, int dup,
-                                  float kappa, int predict_x0) {
+                                  float kappa) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= B * HW) return;
     const int b = idx / HW, p = idx - b * HW;
@@ -80,8 +88,8 @@ __global__ void cfg_x0_bwd_kernel(const float* __restrict__ g, const float* __re
     for (int c = 0; c < C; c++) {
         const size_t i = ((size_t)b * C + c) * HW + p;
         const float go = g[i];
-        const float ge = predict_x0 ? -go * s1[b] / s0[b] : go;
-        if (dxt) dxt[i] = predict_x0 ? go / s0[b] : 0.f;
+        const float ge = MODE == 1 ? -go * s1[b] / s0[b] : MODE == 2 ? -go * s1[b] : go;
+        if (dxt) dxt[i] = MODE == 1 ? go / s0[b] : MODE == 2 ? go * s0[b] : 0.f;
         if (dup == 2) { du[c] = (1.f - kappa) * ge; dc[c] = kappa * ge; }
         else du[c] = ge;
     }
@@ -432,6 +440,53 @@ __global__ void sid_fake_loss_kernel(const float* __restrict__ e, const float* _
     if (threadIdx.x == 0) loss_part[blockIdx.y * gridDim.x + blockIdx.x] = (sh[0] + sh[1] + sh[2] + sh[3]) * scale;
 }
 
+// v-prediction fake-score loss (sid_training_loop.py:423-445, v branch).  Per sample s the target is v* = s0[s]*noise - s1[s]*x0,
+// formed in registers (never stored).  Prepass: st[s][0] = 1 if o or v* holds a NaN in sample s (st[s][1] = 0: same workspace
+// layout as sid_sample_stats_kernel).
+__global__ void sid_fake_v_stats_kernel(const float* __restrict__ o, const float* __restrict__ x0, const float* __restrict__ noise,
+                                        const float* __restrict__ s0, const float* __restrict__ s1, float* __restrict__ st, int n) {
+    __shared__ float sh[4];
+    const int s = blockIdx.x;
+    const float a = s0[s], c = s1[s];
+    float flag = 0.f;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const size_t k = (size_t)s * n + i;
+        const float x = o[k];
+        const float v = a * noise[k] - c * x0[k];
+        if (x != x || v != v) flag = 1.f;
+    }
+    flag = wave_max(flag);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = flag;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        st[s * 2] = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
+        st[s * 2 + 1] = 0.f;
+    }
+}
+
+// sum_s w[s] * sum_i (o - v*)^2 * scale over non-NaN samples; d o = 2*scale*w[s]*(o - v*), zero for a dropped sample
+__global__ void sid_fake_loss_v_kernel(const float* __restrict__ o, const float* __restrict__ x0, const float* __restrict__ noise,
+                                       const float* __restrict__ s0, const float* __restrict__ s1, const float* __restrict__ w,
+                                       const float* __restrict__ st, float* __restrict__ de, float* __restrict__ loss_part, int n,
+                                       float scale) {
+    __shared__ float sh[4];
+    const int s = blockIdx.y;
+    const bool drop = st[s * 2] != 0.f;
+    const float a = s0[s], c = s1[s], ws = w[s], gs = 2.f * scale * ws;
+    float acc = 0.f;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const size_t k = (size_t)s * n + i;
+        if (drop) { de[k] = 0.f; continue; }
+        const float d = o[k] - (a * noise[k] - c * x0[k]);
+        acc += d * d;
+        de[k] = gs * d;
+    }
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) loss_part[blockIdx.y * gridDim.x + blockIdx.x] = drop ? 0.f : (sh[0] + sh[1] + sh[2] + sh[3]) * ws * scale;
+}
+
 __global__ void sum_small_kernel(const float* __restrict__ part, float* __restrict__ out, int n) {
     float t = 0.f;
     for (int i = threadIdx.x; i < n; i += 64) t += part[i];
@@ -460,10 +515,13 @@ static int noisy_input_bwd_t(const void* g, const float* s0, float* dx0, int B, 
 }
 template <typename T>
 static int cfg_x0_bwd_t(const float* g, const float* s0, const float* s1, void* deps, float* dxt, int B, int C, int HW, int Cp,
-                        int dup, float kappa, int predict_x0, void* stream) {
-    if (C > 8 || Cp % 8) return SIDLSG_EINVAL;
-    hipLaunchKernelGGL(cfg_x0_bwd_kernel<T>, GRID1D((size_t)B * HW, 256), dim3(256), 0, (hipStream_t)stream, g, s0, s1,
-                       (T*)deps, dxt, B, C, HW, Cp, dup, kappa, predict_x0);
+                        int dup, float kappa, int mode, void* stream) {
+    if (C > 8 || Cp % 8 || mode < 0 || mode > 2) return SIDLSG_EINVAL;
+    const dim3 grid = GRID1D((size_t)B * HW, 256);
+    hipStream_t s = (hipStream_t)stream;
+    if (mode == 0) hipLaunchKernelGGL((cfg_x0_bwd_kernel<T, 0>), grid, dim3(256), 0, s, g, s0, s1, (T*)deps, dxt, B, C, HW, Cp, dup, kappa);
+    else if (mode == 1) hipLaunchKernelGGL((cfg_x0_bwd_kernel<T, 1>), grid, dim3(256), 0, s, g, s0, s1, (T*)deps, dxt, B, C, HW, Cp, dup, kappa);
+    else hipLaunchKernelGGL((cfg_x0_bwd_kernel<T, 2>), grid, dim3(256), 0, s, g, s0, s1, (T*)deps, dxt, B, C, HW, Cp, dup, kappa);
     return sidlsg_last_error();
 }
 template <typename T>
@@ -602,15 +660,18 @@ SIDLSG_BOTH(sidlsg_noisy_input_bwd, noisy_input_bwd_t,
             (const void* g, const float* s0, float* dx0, int B, int C, int HW, int Cp, int dup, int accumulate, void* stream),
             (g, s0, dx0, B, C, HW, Cp, dup, accumulate, stream))
 int sidlsg_cfg_x0(const float* eps, const float* xt, const float* s0, const float* s1, float* out, int B, int C, int HW,
-                  int Ce, int dup, float kappa, int predict_x0, void* stream) {
-    if (Ce < C) return SIDLSG_EINVAL;
-    hipLaunchKernelGGL(cfg_x0_kernel, GRID1D((size_t)B * HW, 256), dim3(256), 0, (hipStream_t)stream, eps, xt, s0, s1, out, B,
-                       C, HW, Ce, dup, kappa, predict_x0);
+                  int Ce, int dup, float kappa, int mode, void* stream) {
+    if (Ce < C || mode < 0 || mode > 2) return SIDLSG_EINVAL;
+    const dim3 grid = GRID1D((size_t)B * HW, 256);
+    hipStream_t s = (hipStream_t)stream;
+    if (mode == 0) hipLaunchKernelGGL(cfg_x0_kernel<0>, grid, dim3(256), 0, s, eps, xt, s0, s1, out, B, C, HW, Ce, dup, kappa);
+    else if (mode == 1) hipLaunchKernelGGL(cfg_x0_kernel<1>, grid, dim3(256), 0, s, eps, xt, s0, s1, out, B, C, HW, Ce, dup, kappa);
+    else hipLaunchKernelGGL(cfg_x0_kernel<2>, grid, dim3(256), 0, s, eps, xt, s0, s1, out, B, C, HW, Ce, dup, kappa);
     return sidlsg_last_error();
 }
 SIDLSG_BOTH(sidlsg_cfg_x0_bwd, cfg_x0_bwd_t,
-            (const float* g, const float* s0, const float* s1, void* deps, float* dxt, int B, int C, int HW, int Cp, int dup, float kappa, int predict_x0, void* stream),
-            (g, s0, s1, deps, dxt, B, C, HW, Cp, dup, kappa, predict_x0, stream))
+            (const float* g, const float* s0, const float* s1, void* deps, float* dxt, int B, int C, int HW, int Cp, int dup, float kappa, int mode, void* stream),
+            (g, s0, s1, deps, dxt, B, C, HW, Cp, dup, kappa, mode, stream))
 SIDLSG_BOTH(sidlsg_timestep_embed, timestep_embed_t, (const long long* t, void* out, int B, int dim, void* stream), (t, out, B, dim, stream))
 SIDLSG_BOTH(sidlsg_silu_fwd, silu_fwd_t, (const void* x, void* y, long long n, void* stream), (x, y, n, stream))
 SIDLSG_BOTH(sidlsg_silu_bwd, silu_bwd_t, (const void* x, const void* dy, void* dx, long long n, void* stream), (x, dy, dx, n, stream))
@@ -667,6 +728,16 @@ int sidlsg_fake_loss(const float* e, const float* noise, float* de, float* loss,
     float* st = ws; float* part = ws + 2 * S;
     hipLaunchKernelGGL(sid_sample_stats_kernel, dim3(S), dim3(256), 0, s, e, (const float*)nullptr, (const float*)nullptr, st, n);
     hipLaunchKernelGGL(sid_fake_loss_kernel, dim3(SID_GB, S), dim3(256), 0, s, e, noise, st, de, part, n, scale);
+    hipLaunchKernelGGL(sum_small_kernel, dim3(1), dim3(64), 0, s, part, loss, S * SID_GB);
+    return sidlsg_last_error();
+}
+int sidlsg_fake_loss_v(const float* o, const float* x0, const float* noise, const float* s0, const float* s1, const float* w,
+                       float* de, float* loss, float* ws, int S, int n, float scale, void* stream) {
+    if (S <= 0 || n <= 0) return SIDLSG_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    float* st = ws; float* part = ws + 2 * S;
+    hipLaunchKernelGGL(sid_fake_v_stats_kernel, dim3(S), dim3(256), 0, s, o, x0, noise, s0, s1, st, n);
+    hipLaunchKernelGGL(sid_fake_loss_v_kernel, dim3(SID_GB, S), dim3(256), 0, s, o, x0, noise, s0, s1, w, st, de, part, n, scale);
     hipLaunchKernelGGL(sum_small_kernel, dim3(1), dim3(64), 0, s, part, loss, S * SID_GB);
     return sidlsg_last_error();
 }

@@ -19,6 +19,7 @@ import os
 import torch
 
 from ._lib import lib
+from .scheduler import prediction_mode
 
 BF16 = torch.bfloat16
 F32 = torch.float32
@@ -1510,31 +1511,34 @@ def noisy_input(x0, noise, s0, s1, dup, dtype=BF16):
 
 
 class _CfgX0(torch.autograd.Function):
-    """eps [dup*B,HW,C] fp32 (+ x_t) -> NCHW fp32 guided eps or x0 prediction."""
+    """eps [dup*B,HW,C] fp32 (+ x_t) -> NCHW fp32 guided output (mode 0) or x0 prediction (mode 1: epsilon, 2: v)."""
 
     @staticmethod
-    def forward(ctx, eps, xt, s0, s1, kappa, predict_x0, act_dtype):
+    def forward(ctx, eps, xt, s0, s1, kappa, mode, act_dtype):
         B, C, H, W = xt.shape
         dup = eps.shape[0] // B
         out = torch.empty_like(xt)
         lib.sidlsg_cfg_x0(_p(_chk(eps, F32)), _p(_chk(xt, F32)), _p(s0), _p(s1), _p(out), B, C, H * W, eps.shape[-1], dup,
-                          float(kappa), int(predict_x0), _s())
+                          float(kappa), mode, _s())
         ctx.save_for_backward(s0, s1)
-        ctx.cfg = (B, C, H, W, dup, float(kappa), int(predict_x0), act_dtype)
+        ctx.cfg = (B, C, H, W, dup, float(kappa), mode, act_dtype)
         return out
 
     @staticmethod
     def backward(ctx, g):
         s0, s1 = ctx.saved_tensors
-        B, C, H, W, dup, kappa, px0, act_dtype = ctx.cfg
+        B, C, H, W, dup, kappa, mode, act_dtype = ctx.cfg
         deps = torch.empty((dup * B, H * W, 8), device=g.device, dtype=act_dtype)    # the network's activation dtype
         dxt = torch.empty((B, C, H, W), device=g.device, dtype=F32) if ctx.needs_input_grad[1] else None
-        _fn('cfg_x0_bwd', act_dtype)(_p(g.contiguous()), _p(s0), _p(s1), _p(deps), _p(dxt), B, C, H * W, 8, dup, kappa, px0, _s())
+        _fn('cfg_x0_bwd', act_dtype)(_p(g.contiguous()), _p(s0), _p(s1), _p(deps), _p(dxt), B, C, H * W, 8, dup, kappa, mode, _s())
         return deps, dxt, None, None, None, None, None
 
 
-def cfg_x0(eps, xt, s0, s1, kappa, predict_x0, act_dtype=BF16):
-    return _CfgX0.apply(eps, xt, s0, s1, kappa, predict_x0, act_dtype)
+def cfg_x0(eps, xt, s0, s1, kappa, predict_x0, act_dtype=BF16, prediction_type='epsilon'):
+    """u + kappa (c - u), then (predict_x0) x0 under the network's parameterisation `prediction_type` ('epsilon' | 'v_prediction');
+    predict_x0 False returns the guided network output itself."""
+    mode = prediction_mode(prediction_type) if predict_x0 else 0
+    return _CfgX0.apply(eps, xt, s0, s1, kappa, mode, act_dtype)
 
 
 class _GLoss(torch.autograd.Function):
@@ -1580,6 +1584,31 @@ class _FakeLoss(torch.autograd.Function):
 
 def sid_fake_score_loss(e, noise, scale):
     return _FakeLoss.apply(e, noise, scale)
+
+
+class _FakeLossV(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, o, images, noise, s0, s1, w, scale):
+        S = o.shape[0]
+        n = o.numel() // S
+        de = torch.empty_like(o)
+        loss = torch.empty(1, device=o.device, dtype=F32)
+        ws = torch.empty(10 * S, device=o.device, dtype=F32)
+        lib.sidlsg_fake_loss_v(_p(_chk(o, F32)), _p(_chk(images, F32)), _p(_chk(noise, F32)), _p(_chk(s0, F32)), _p(_chk(s1, F32)),
+                               _p(_chk(w, F32)), _p(de), _p(loss), _p(ws), S, n, float(scale), _s())
+        ctx.save_for_backward(de)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (de,) = ctx.saved_tensors
+        return de * g, None, None, None, None, None, None
+
+
+def sid_fake_score_loss_v(o, images, noise, s0, s1, w, scale):
+    """v-prediction fake-score loss: scale * sum_b w_b |o_b - v*_b|^2, v* = s0 noise - s1 images (never materialised), samples whose
+    o or v* holds a NaN dropped.  Gradient to o only (`images` come from the generator's no-grad pass)."""
+    return _FakeLossV.apply(o, images, noise, s0, s1, w, scale)
 
 
 # ------------------------------------------------------------------------------------------------

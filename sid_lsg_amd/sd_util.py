@@ -77,6 +77,16 @@ def _arch_from_dir(path):
     raise ValueError(f'{cj}: not one of the supported UNet configurations {sorted(CONFIGS)}')
 
 
+def _random_spec(name):
+    """'random:<arch>[:v]' -> (arch, prediction_type or None)."""
+    parts = name.lower().split(':')
+    if len(parts) == 3 and parts[2] == 'v':
+        return parts[1], 'v_prediction'
+    if len(parts) != 2:
+        raise ValueError(f"{name}: expected 'random:<arch>' or 'random:<arch>:v'")
+    return parts[1], None
+
+
 def _arch_of(name):
     if os.path.isdir(name):
         arch = _arch_from_dir(name)
@@ -84,10 +94,47 @@ def _arch_of(name):
             return arch
     n = os.path.basename(os.path.normpath(name)).lower() if os.path.isdir(name) else name.lower()
     if n.startswith('random:'):
-        return n.split(':', 1)[1]
+        return _random_spec(n)[0]
     if '2-1-base' in n or 'sd21' in n or 'stable-diffusion-2' in n:
         return 'sd21-base'
     return 'sd15'
+
+
+def resolve_scheduler(name):
+    """The noise scheduler of a model spec (what load_sd15 returns, on the CPU):
+      * a local diffusers-layout directory with scheduler/scheduler_config.json -> DDPMScheduler.from_config of that file
+        (prediction_type epsilon or v_prediction; anything it would not reproduce exactly raises);
+      * 'random:<arch>:v' -> v-prediction; 'random:<arch>' -> epsilon;
+      * with SIDLSG_ALLOW_RANDOM_INIT=1, the SD 2.x hub ids WITHOUT '-base' (stable-diffusion-2-1, stable-diffusion-2: the 768-v
+        checkpoints) -> v-prediction;
+      * otherwise today's default (scaled_linear 0.00085..0.012, 1000 steps, epsilon)."""
+    import json
+    name = str(name)
+    if os.path.isdir(name):
+        sj = os.path.join(name, 'scheduler', 'scheduler_config.json')
+        if os.path.isfile(sj):
+            with open(sj) as f:
+                return DDPMScheduler.from_config(json.load(f))
+        return DDPMScheduler()
+    n = name.lower()
+    if n.startswith('random:'):
+        pt = _random_spec(n)[1]
+        return DDPMScheduler(prediction_type=pt or 'epsilon')
+    if os.environ.get('SIDLSG_ALLOW_RANDOM_INIT', '0') == '1':
+        base = n.rstrip('/').rsplit('/', 1)[-1]
+        if base in ('stable-diffusion-2-1', 'stable-diffusion-2'):
+            return DDPMScheduler(prediction_type='v_prediction')
+    return DDPMScheduler()
+
+
+def check_prediction_type(unet, noise_scheduler):
+    """A network trained for one parameterisation evaluated under a scheduler of the other would be read wrongly without a
+    trace (e.g. a v snapshot sampled with an epsilon --repo_id): refuse."""
+    net_pt = getattr(_unwrap(unet), 'prediction_type', 'epsilon')
+    sch_pt = noise_scheduler.config.prediction_type
+    if net_pt != sch_pt:
+        raise ValueError(f'the network predicts {net_pt!r} but the noise scheduler is configured for {sch_pt!r}: '
+                         'use the scheduler of the model the network was distilled from')
 
 
 def resolve_compute_dtype(compute_dtype=None):
@@ -108,6 +155,8 @@ def load_sd15(pretrained_model_name_or_path, pretrained_vae_model_name_or_path, 
         tokenizer/{vocab.json,merges.txt}) -> real weights through `load_state_dict` (key names are diffusers');
       * 'random:<arch>' (arch in sd15 | sd21-base | tiny | tiny40), or any hub id when SIDLSG_ALLOW_RANDOM_INIT=1 ->
         seeded random weights of that architecture (no network here: benchmarks and parity tests use this).
+    The noise scheduler (and the `prediction_type` attribute of the returned UNet) come from resolve_scheduler:
+    <dir>/scheduler/scheduler_config.json when it exists, 'random:<arch>:v' for a v-prediction spec.
     `weight_dtype` is accepted for signature compatibility (the reference passes its fp16/fp32 switch here): masters are
     always fp32.  The COMPUTE dtype is `compute_dtype` (torch.bfloat16 = production MFMA path, torch.float32 = the
     fp32-accurate mode of csrc/fp32.hip), default from $SIDLSG_COMPUTE_DTYPE ('bf16' | 'fp32'), else bf16.
@@ -125,7 +174,9 @@ def load_sd15(pretrained_model_name_or_path, pretrained_vae_model_name_or_path, 
     if local:
         from safetensors.torch import load_file
         src = load_file(os.path.join(name, 'unet', 'diffusion_pytorch_model.safetensors'))
+    noise_scheduler = resolve_scheduler(name)
     unet = HipUNet2DCondition(cfg, compute_dtype=resolve_compute_dtype(compute_dtype))
+    unet.prediction_type = noise_scheduler.config.prediction_type
     unet.materialize(device, seed=seed, source=src)
     tcfg = TEXT_CONFIGS.get(arch, dict(hidden=cfg.cross_attention_dim, layers=2, heads=2, dff=2 * cfg.cross_attention_dim,
                                        act='quick_gelu'))
@@ -159,7 +210,7 @@ def load_sd15(pretrained_model_name_or_path, pretrained_vae_model_name_or_path, 
     else:
         vae.init_parameters(seed + 2)
     vae = vae.to(device)
-    return unet, vae, DDPMScheduler().to(device), text_encoder, tokenizer
+    return unet, vae, noise_scheduler.to(device), text_encoder, tokenizer
 
 
 def encode_contexts(contexts, text_encoder, tokenizer, device):
@@ -174,12 +225,12 @@ def encode_contexts(contexts, text_encoder, tokenizer, device):
 
 # ------------------------------------------------------------------------------------------------
 def hip_generate(unet, z, ctx16, init_t, sched, x0=None):
-    """x_t = s0*x0 + s1*z at t_init ; eps = G(x_t) ; x_hat = (x_t - s1*eps)/s0   (sid_sd_util.py:182-185)"""
+    """x_t = s0*x0 + s1*z at t_init ; o = G(x_t) ; x_hat = (x_t - s1*o)/s0 (epsilon) or s0*x_t - s1*o (v)   (sid_sd_util.py:182-185)"""
     s0, s1 = sched.coefficients(init_t)
     net = _unwrap(unet)
     xin, xt = ops.noisy_input(x0, z, s0, s1, 1, net.compute_dtype)
     eps = _ddp_exchange(unet, net.forward_nhwc(xin, init_t, ctx16))
-    return ops.cfg_x0(eps, xt, s0, s1, 1.0, True, net.compute_dtype)
+    return ops.cfg_x0(eps, xt, s0, s1, 1.0, True, net.compute_dtype, prediction_type=sched.config.prediction_type)
 
 
 def hip_prepare_denoise(images, noise, t, cond16, uncond16, sched, guided, act_dtype=torch.bfloat16):
@@ -190,13 +241,14 @@ def hip_prepare_denoise(images, noise, t, cond16, uncond16, sched, guided, act_d
     xin, xt = ops.noisy_input(images, noise, s0, s1, dup, act_dtype)
     ctx = torch.cat([uncond16, cond16]) if guided else cond16          # (sid_sd_util.py:259-261)
     tt = torch.cat([t, t]) if guided else t
-    return SimpleNamespace(xin=xin, xt=xt, s0=s0, s1=s1, ctx=ctx, tt=tt)
+    return SimpleNamespace(xin=xin, xt=xt, s0=s0, s1=s1, ctx=ctx, tt=tt, prediction_type=sched.config.prediction_type)
 
 
 def hip_denoise(unet, prep, guidance_scale, predict_x0):
     net = _unwrap(unet)
     eps = _ddp_exchange(unet, net.forward_nhwc(prep.xin, prep.tt, prep.ctx))
-    return ops.cfg_x0(eps, prep.xt, prep.s0, prep.s1, guidance_scale, predict_x0, net.compute_dtype)  # u + k(c-u), then x0 (:264-272)
+    return ops.cfg_x0(eps, prep.xt, prep.s0, prep.s1, guidance_scale, predict_x0, net.compute_dtype,     # u + k(c-u), then x0 (:264-272)
+                      prediction_type=prep.prediction_type)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -205,6 +257,7 @@ def sid_sd_sampler(unet, latents, contexts, init_timesteps, noise_scheduler, tex
                    num_steps_eval=1):
     steps = num_steps if train_sampler else num_steps_eval
     _require_hip(unet)
+    check_prediction_type(unet, noise_scheduler)
     emb = encode_contexts(contexts, text_encoder, tokenizer, latents.device).to(_unwrap(unet).compute_dtype).contiguous()
     D_x = None
     ctxmgr = torch.enable_grad() if train_sampler else torch.no_grad()
@@ -227,6 +280,7 @@ def sid_sd_sampler(unet, latents, contexts, init_timesteps, noise_scheduler, tex
 def sid_sd_denoise(unet, images, noise, contexts, timesteps, noise_scheduler, text_encoder, tokenizer, resolution,
                    dtype=torch.float16, predict_x0=True, guidance_scale=1):
     _require_hip(unet)
+    check_prediction_type(unet, noise_scheduler)
     b = images.shape[0]
     cond = encode_contexts(contexts, text_encoder, tokenizer, images.device)
     guided = guidance_scale != 1

@@ -19,7 +19,7 @@ import os
 import torch
 
 from . import ops
-from .sd_util import hip_denoise, hip_generate, hip_prepare_denoise
+from .sd_util import check_prediction_type, hip_denoise, hip_generate, hip_prepare_denoise
 
 
 class _SegmentedUpdate:
@@ -117,6 +117,10 @@ class SiDStep:
         opt_G.attach(ema=(G_ema.flat_params if (G_ema is not None and G_ema is not G) else None), w16=G.flat_w16, owner=G)
         if not (G.compute_dtype == fake_score.compute_dtype == true_score.compute_dtype):
             raise ValueError('G, fake_score and true_score must share one compute dtype (they share the noisy CFG batch)')
+        for net in (G, fake_score, true_score):
+            check_prediction_type(net, scheduler)
+        # v-prediction teacher (SD 2.x 768-v): the fake-score loss is the SNR-weighted velocity loss; x0 conversions follow the scheduler
+        self.vpred = scheduler.config.prediction_type == 'v_prediction'
         self.phi.requires_grad_(False)
 
     def _use_grouped(self, batch):
@@ -147,7 +151,10 @@ class SiDStep:
         prep = hip_prepare_denoise(images, r['noise'], r['t'], r['cond'], r.get('uncond'), self.sched, self.k1 != 1,
                                    act_dtype=self.psi.compute_dtype)
         eps = hip_denoise(self.psi, prep, self.k1, predict_x0=False)                # :418-421
-        loss = ops.sid_fake_score_loss(eps, r['noise'], self.ls / self.bgt)         # :423-445
+        if self.vpred:      # target v* = s0 noise - s1 images, weight snr/(snr+1) per sample (:424-441)
+            loss = ops.sid_fake_score_loss_v(eps, images, r['noise'], prep.s0, prep.s1, self.sched.snr_weights(r['t']), self.ls / self.bgt)
+        else:
+            loss = ops.sid_fake_score_loss(eps, r['noise'], self.ls / self.bgt)     # :423-445
         loss.backward()                                                             # :449-450
         return loss.detach()
 
@@ -227,8 +234,9 @@ class SiDStep:
                 before_fake_eval()
             eps_f, eps_r = self.psi.forward_pair(self.phi, prep.xin, prep.tt, prep.ctx)
             cd = self.psi.compute_dtype
-            y_fake = ops.cfg_x0(eps_f, prep.xt, prep.s0, prep.s1, k2, True, cd)     # u + k (c - u), then x0 (sid_sd_util.py:264-272)
-            y_real = ops.cfg_x0(eps_r, prep.xt, prep.s0, prep.s1, k4, True, cd)
+            pt = prep.prediction_type
+            y_fake = ops.cfg_x0(eps_f, prep.xt, prep.s0, prep.s1, k2, True, cd, prediction_type=pt)     # u + k (c - u), then x0 (sid_sd_util.py:264-272)
+            y_real = ops.cfg_x0(eps_r, prep.xt, prep.s0, prep.s1, k4, True, cd, prediction_type=pt)
             loss = ops.sid_generator_loss(images, y_real, y_fake, self.alpha, self.lsg / self.bgt)   # :508-530
             loss.backward()                                                             # :532-533
             return loss.detach()

@@ -30,7 +30,7 @@ from . import distributed as dist
 from .data import InfiniteSampler, prompt_batches
 from .dnnlib_util import EasyDict, construct_class_by_name, format_time
 from .distributed import FlatGradReducer
-from .sd_util import load_sd15, resolve_compute_dtype
+from .sd_util import check_prediction_type, load_sd15, resolve_compute_dtype
 from .sid_step import SiDStep
 from .text import TextConditioner
 
@@ -132,6 +132,7 @@ def training_loop(
     if world > 1 and rank == 0:
         torch.distributed.barrier()
     dist.print0('Loading network completed')
+    dist.print0(f'Noise scheduler: {noise_scheduler}; teacher parameterisation: {noise_scheduler.config.prediction_type}')
 
     start_time = time.time()
     batch_gpu_total = batch_size // world
@@ -168,6 +169,7 @@ def training_loop(
         dist.print0(f'Loading network weights from "{resume_pkl}"...')
         with open(resume_pkl, 'rb') as f:
             src = pickle.load(f)['ema']
+        check_prediction_type(src, noise_scheduler)
         for net in (G, G_ema):
             net.load_state_dict(_snapshot_state(src))
             net.refresh_compute_weights()

@@ -27,6 +27,7 @@ import torch  # noqa: E402
 
 from sid_lsg_amd import distributed as dist  # noqa: E402
 from sid_lsg_amd.dnnlib_util import EasyDict, construct_class_by_name  # noqa: E402
+from sid_lsg_amd.sd_util import resolve_scheduler  # noqa: E402
 from sid_lsg_amd.training_loop import training_loop  # noqa: E402
 
 
@@ -60,7 +61,7 @@ OPTIONS = [
     (('--resume',), dict(type=str, default=None, metavar='PT', help='Resume from training-state-*.pt')),
     (('-n', '--dry-run'), dict(is_flag=True, help='Print training options and exit')),
     (('--metrics',), dict(callback=_csv, default=None, help='Comma-separated list or "none"')),
-    (('--sd_model',), dict(type=str, default='runwayml/stable-diffusion-v1-5', show_default=True, help='Local diffusers directory or random:<arch>')),
+    (('--sd_model',), dict(type=str, default='runwayml/stable-diffusion-v1-5', show_default=True, help='Local diffusers directory, random:<arch> or random:<arch>:v')),
     (('--resolution',), dict(type=int, default=512, show_default=True, metavar='INT', help='Image resolution')),
     (('--init_timestep',), dict(type=int, default=625, show_default=True, metavar='INT', help='t_init, in [0,999]')),
     (('--fp16',), dict(type=bool, default=False, show_default=True, metavar='BOOL', help='Reference fp16 recipe (optimizer eps 1e-6)')),
@@ -209,6 +210,7 @@ def main(**kwargs):
     dist.print0(f'Number of GPUs:          {dist.get_world_size()}')
     dist.print0(f'Batch size:              {c.batch_size}')
     dist.print0(f'Compute:                 bf16 MFMA, fp32 masters (reference recipe: {dtype_str})')
+    dist.print0(f'Prediction type:         {resolve_scheduler(o.sd_model).config.prediction_type}')
     dist.print0()
     if o.dry_run:
         dist.print0('Dry run; exiting.')
