@@ -9,7 +9,13 @@ Nothing is skipped inside the timed region: noise/timestep sampling, CLIP text e
 the gradient all-reduces.  Weights are seeded random (no SD checkpoints offline) and prompts are synthetic
 Aesthetic-style captions tokenised by the offline stand-in tokenizer: `"data": "synthetic"`.
 
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line: images/s, ms per step, and the
+per-family kernel figures sampled inside the timed region.  Everything that takes work of its own after the timed region -- the
+loss check against the stored fp32 references, the stand-alone (`isolated`) kernel figures, the teacher and grouped-pass
+timings, --graph's host-enqueue and eager per-kernel iterations, the CPU baseline -- runs only with --full.
+
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29511 \
         bench.py --gpus 8 --steps 5 --warmup 2
 """
@@ -94,7 +100,7 @@ def compact_line(full):
     """The ONE JSON line of stdout (< LINE_LIMIT bytes; tests/test_host_logic.py::test_bench_line_is_compact) from the full result
     dict, which goes to bench_detail.json.  Keys: the driver's contract + `roofline` of the dominant kernel family (live,
     per-dispatch timestamps over the timed region; `traffic` is null: HBM-side PMC bytes need their own serialising rocprofv3
-    passes and live under profiles/) + one fraction per other family + `cpu_baseline`."""
+    passes and live under profiles/) + one fraction per other family + (--full) `cpu_baseline`, `loss_check`, `teacher_pass`."""
     keep = ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline', 'dtype', 'data')
     out = {k: _r(full[k]) for k in keep}
     c = full['config']
@@ -337,7 +343,11 @@ def main():
                     help='single rank only: run the data-parallel gradient exchange anyway (RCCL all-reduces over a world of 1, '
                          'FlatGradReducer(min_world=1)) -- the schedule, stream waits and launch path of a multi-GPU run on one GPU; '
                          '`comm` then reports how long the compute stream stood still for it (no xGMI traffic: a lower bound)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure and check what the headline figure does not need: the loss check against '
+                         'the stored fp32 references, stand-alone kernel figures, teacher / grouped-pass timings, --graph\'s host-enqueue '
+                         'and per-kernel iterations, and the CPU baseline')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
     ap.add_argument('--no-kernel-timing', action='store_true')
     ap.add_argument('--dump-outputs', metavar='DIR',
                     help='after the timed steps, write what the last timed step computed (losses; a fixed, seeded sample of the updated '
@@ -390,7 +400,7 @@ def main():
                    reducer=reducer)
     step, phi, cond, sched, gen, batch_size = S.step, S.phi, S.cond, S.sched, S.gen, S.batch_size
     one_iteration = S.one_iteration
-    loss_ref = load_loss_reference(args, world)
+    loss_ref = load_loss_reference(args, world) if args.full else None
 
     S.use_graph = args.graph
 
@@ -420,7 +430,8 @@ def main():
         lf, lg = one_iteration(it)
         if first is None:
             first = (lf.clone(), lg.clone())      # device scalars of the first timed step, read after the timed region (copies: the graphed
-                                                  # iteration returns STATIC scalars that the next replay overwrites)
+                                                  # iteration returns STATIC scalars that the next replay overwrites); taken in
+                                                  # every run, so the timed loop is the same with and without --full
     sync()
     dt = time.time() - t0
     if rank == 0 and loss_ref is not None and first is not None and (world == 1 or args.warmup == 0):
@@ -437,7 +448,7 @@ def main():
     if args.dump_outputs and rank == 0:          # before the iterations below move the weights on
         dump_outputs(args.dump_outputs, S, lf, lg)
     t_host = None
-    if S.use_graph:                  # per-kernel events cannot see inside a graph launch: sample eager iterations now
+    if S.use_graph and args.full:          # per-kernel events cannot see inside a graph launch: sample eager iterations now
         hs = time.time()
         for it in range(args.warmup + args.steps, args.warmup + args.steps + 3):
             one_iteration(it)
@@ -457,7 +468,7 @@ def main():
     # rocprofv3 --kernel-trace reports for the same command) is longer than the kernel's own.  A few extra iterations AFTER the
     # timed region, with that overlap switched off, give each family's stand-alone figure (`isolated` in the roofline objects).
     iso = {}
-    if not args.no_kernel_timing and step.side is not None:          # rank-independent condition: the iterations exchange gradients
+    if args.full and not args.no_kernel_timing and step.side is not None:          # rank-independent condition: the iterations exchange gradients
         from sid_lsg_amd import ops as _ops
         side, step.side = step.side, None
         wgrad_side, _ops._WGRAD_SIDE = _ops._WGRAD_SIDE, False      # weight gradients back on the main stream as well
@@ -473,7 +484,7 @@ def main():
     # north_star's second figure: MFMA utilisation of the CFG teacher pass alone (phi forward on the [uncond; cond] batch of
     # 2b samples + guidance + x0), timed with events on a few extra passes after the timed region (rank 0)
     teacher = pair = None
-    if timers:
+    if args.full and timers:
         from sid_lsg_amd.sd_util import hip_denoise, hip_prepare_denoise
         with torch.no_grad():
             prompts = synth_prompts(b, seed=12345)
@@ -530,14 +541,15 @@ def main():
     }
     # parity at the BENCH workload: the losses of iteration 0 against the fp32 CPU ORACLE run on this workload's own inputs and weights
     # (tests/golden/bench_loss_reference.json `oracle_fp32`, oracle/make_bench_oracle_reference.py) and of the first timed step against
-    # the stored HIP fp32-mode values (tools/make_bench_loss_reference.py; equal to the oracle at iteration 0 to 4e-8); bf16 bounds
-    if loss_ref is None:
-        out['loss_check'] = 'no reference stored for this configuration'
-    elif not checks:
-        out['loss_check'] = 'not run'
-    else:
-        out['loss_check'] = 'ok' if all(c['ok'] for c in checks) else 'FAILED'
-        out['loss_check_detail'] = checks
+    # the stored HIP fp32-mode values (tools/make_bench_loss_reference.py; equal to the oracle at iteration 0 to 4e-8); bf16 bounds (--full)
+    if args.full:
+        if loss_ref is None:
+            out['loss_check'] = 'no reference stored for this configuration'
+        elif not checks:
+            out['loss_check'] = 'not run'
+        else:
+            out['loss_check'] = 'ok' if all(c['ok'] for c in checks) else 'FAILED'
+            out['loss_check_detail'] = checks
     # multi-GPU: how long the compute stream stood still in FlatGradReducer.wait per step and network (the part of the gradient
     # exchange NOT hidden under compute), and the all-reduce rate the messages saw
     if comm is not None:
@@ -612,7 +624,7 @@ def main():
         out['roofline'] = dict(objs[dominant], family=dominant, why='largest est_ms_per_step of the MFMA kernel families in the timed region')
         for k in timers:
             out['roofline_' + k] = objs[k]
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         # torch's CPU backend degrades badly when oversubscribed on many-core hosts (256 threads: 160 s per forward);
         # 32 threads is the measured sweet spot class for one fp32 conv-heavy forward -> cores = threads actually used
         out['cpu_baseline'] = cpu_baseline(args.arch, min(os.cpu_count() or 1, 32), kappa=args.kappa)

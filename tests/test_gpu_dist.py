@@ -130,13 +130,13 @@ def _run_bench(nproc, *flags, env_extra=None, timeout=1500):
 
 def test_bench_under_torchrun_two_ranks(dev):
     """The driver's scaling run: `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`.  Two ranks share
-    the one GPU of this box (SIDLSG_BENCH_SHARE_GPU=1: gloo carries the exchange), DEFAULT flags otherwise -- per-family
+    one GPU (SIDLSG_BENCH_SHARE_GPU=1: gloo carries the exchange), --full and default flags otherwise -- per-family
     kernel timing on, i.e. including the extra `isolated` iterations after the timed region, which exchange gradients and
     therefore must be executed by every rank (a rank-0-only version of them paired rank 0's gradient all-reduce with the
     other ranks' timing all-reduce).  One JSON line, whole-job images/s, all ranks exit cleanly."""
     import json
     # (a small network: gloo moves the 2 x 3.4 GB of SD1.5 gradients through the host at ~40 s per iteration)
-    out = _run_bench(2, '--steps', '2', '--warmup', '1', '--batch-gpu', '2', '--arch', 'tiny40', '--resolution', '128',
+    out = _run_bench(2, '--steps', '2', '--warmup', '1', '--batch-gpu', '2', '--arch', 'tiny40', '--resolution', '128', '--full',
                      env_extra=dict(SIDLSG_BENCH_SHARE_GPU='1'))
     print({k: out[k] for k in ('value', 'n_gpus', 'ms_per_step', 'config')})
     assert out['n_gpus'] == 2 and out['steps'] == 2 and out['config']['global_batch'] == 4 and out['config']['parallelism'] == 'dp2'
@@ -182,6 +182,24 @@ def test_bench_dump_outputs_are_reproducible(dev, tmp_path):
     for k in ('G_params', 'fake_score_params', 'G_ema_params', 'G_adam_exp_avg_sq', 'fake_score_adam_exp_avg_sq'):
         print(f'{k}: max |difference| {np.abs(b[k] - a[k]).max():.3g} of max |value| {np.abs(a[k]).max():.3g}')
         np.testing.assert_allclose(b[k], a[k], rtol=1e-2, atol=1e-3 * float(np.abs(a[k]).max()), err_msg=k)
+
+
+def test_bench_plain_run_leaves_the_extras_to_full(dev, tmp_path):
+    """A plain `bench.py` run does only what its headline figure needs: set-up, warm-up, the timed steps and the line, with the
+    per-family kernel figures sampled inside the timed region.  The loss check, the stand-alone (`isolated`) kernel figures, the
+    teacher-pass timing and the CPU baseline come with --full, which prints the same kind of line."""
+    flags = ('--steps', '2', '--warmup', '1', '--batch-gpu', '2', '--arch', 'tiny40', '--resolution', '128')
+    plain = _run_bench(1, *flags, env_extra=dict(SIDLSG_BENCH_DETAIL=str(tmp_path / 'plain.json')))
+    full = _run_bench(1, *flags, '--full', env_extra=dict(SIDLSG_BENCH_DETAIL=str(tmp_path / 'full.json')))
+    for out in (plain, full):
+        assert out['steps'] == 2 and out['warmup'] == 1 and out['n_gpus'] == 1 and out['unit'] == 'images/s' and out['higher_is_better']
+        assert abs(out['value'] - 2 * 2 / (2 * out['ms_per_step'] / 1e3)) < 1e-4 * out['value']
+        assert out['roofline']['launches_timed'] > 0 and np.isfinite(out['loss_fake']) and np.isfinite(out['loss_G'])
+    assert plain['metric'] == full['metric'] and plain['dtype'] == full['dtype']
+    for k in ('loss_check', 'teacher_pass', 'cpu_baseline'):
+        assert k not in plain and k in full, k
+    assert plain['roofline']['isolated_frac'] is None and full['roofline']['isolated_frac'] > 0
+    assert full['teacher_pass']['ms'] > 0 and full['cpu_baseline']['value'] > 0
 
 
 def test_rccl_world1_timing_of_the_full_size_messages(dev, tmp_path):

@@ -4,7 +4,7 @@
 out=${1:-gpurun_out/decomp}
 mkdir -p $out
 for b in 1 2 4 8 12 16; do
-  python bench.py --graph --batch-gpu $b --steps 10 --warmup 3 --no-cpu-baseline > $out/graph_b$b.json 2> $out/graph_b$b.err
+  python bench.py --graph --full --batch-gpu $b --steps 10 --warmup 3 --no-cpu-baseline > $out/graph_b$b.json 2> $out/graph_b$b.err
 done
 for b in 1 2 4; do
   python bench.py --batch-gpu $b --steps 10 --warmup 3 --no-cpu-baseline > $out/eager_b$b.json 2> $out/eager_b$b.err

@@ -6,9 +6,9 @@ tag=${1:-r03}
 root=$(pwd)
 out=$root/gpurun_out/$tag
 mkdir -p $out
-python bench.py > $out/bench_default.json 2> $out/bench_default.err
+python bench.py --full > $out/bench_default.json 2> $out/bench_default.err
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $out/bench_prof -o b --output-format csv -- python $root/bench.py --no-cpu-baseline > $out/bench_under_rocprof.json 2> $out/bench_prof.log
+rocprofv3 --kernel-trace --stats -d $out/bench_prof -o b --output-format csv -- python $root/bench.py --full --no-cpu-baseline > $out/bench_under_rocprof.json 2> $out/bench_prof.log
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $out/gemmF -o f --output-format csv -- python $root/tools/bench_kernels.py gemm > $out/gemmF.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $out/gemmW -o w --output-format csv -- python $root/tools/bench_kernels.py gemm > $out/gemmW.log 2>&1
 cd $root

@@ -2,7 +2,7 @@
 # tools/other_configs.sh OUT.jsonl : bench lines of the configurations BASELINE.json lists beside the headline one (parity-tested in tests/; not bench lines of the driver)
 out=${1:-gpurun_out/other_configs.jsonl}
 : > $out
-run() { python bench.py --steps 8 --warmup 3 --no-cpu-baseline "$@" 2>/dev/null | tail -1 >> $out; }
+run() { python bench.py --steps 8 --warmup 3 --full --no-cpu-baseline "$@" 2>/dev/null | tail -1 >> $out; }
 run --kappa 4.5
 run --arch sd21-base --kappa 1.5
 run --arch sd21-base --kappa 1.5 --teacher-weights fp8
