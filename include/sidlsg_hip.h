@@ -109,6 +109,27 @@ int sidlsg_debug_set_p8(int mode); /* A/B switch: which GEMM / conv calls take t
 int sidlsg_conv3x3_wgrad_bf16(const void* dY, int ldy, const void* X, int ldx, float* dW, float* dBias, int B, int H, int Wd,
                               int Cin, int Cout, int stride, int ups, void* stream);
 
+/* ---- deterministic mode --------------------------------------------------------------------
+ * Process-wide switch (like sidlsg_debug_set_p8); initial value from the environment variable SIDLSG_DETERMINISTIC (unset or 0: off).
+ * On, every reduction of this library gives bits that depend only on its inputs and its launch configuration -- never on block
+ * scheduling or stream timing.  What changes while it is on (off: nothing does):
+ *   - column sums (sidlsg_colsum*, incl. _strided and _f32): per-chunk totals go to a slab [B][chunks][N] in the stream's workspace
+ *     (sidlsg_set_stream_workspace, else sidlsg_set_workspace) and a second kernel adds them in ascending chunk, then batch order;
+ *     without a workspace: one chunk per batch for per_batch and one chunk over all rows for total (slow, order-fixed);
+ *   - LayerNorm / GroupNorm dgamma, dbeta: the partial-sum reduction runs with one thread per channel over all partials in order,
+ *     immediate and deferred (sidlsg_flush_reductions) alike, so the two give equal bits; a GroupNorm backward WITH parameter
+ *     gradients skips the one-pass (small-stage) and per-group (SIDLSG_GN_GROUP) kernels, which add per block with atomics, and
+ *     takes the two-kernel path;
+ *   - bf16 weight gradients (single, grouped, dense, conv): pixel splits only with a slab per split (else one split); with several
+ *     splits the bias gradient is a column sum of dY (above) instead of per-split atomics;
+ *   - fp32 weight gradients: slabs in the stream's workspace + a split-ordered reduction, else one split.
+ * Audit of the rest: forward contractions (split-K slabs + gemm_finish), attention forward and backward, the norm forwards, the
+ * losses (fixed block partials) and sidlsg_adam_ema are order-fixed already; they use no atomics.
+ * Guaranteed: equal bits for the same library build, GPU model, shapes, launch configuration and stream assignment.  Not: across
+ * builds, batch sizes or split decisions (a different workspace size can change them).  A captured graph keeps the kernels of the
+ * mode it was captured in.  on: 1 on, 0 off, -1 query only; returns the previous setting. */
+int sidlsg_set_deterministic(int on);
+
 /* ---- normalisation (HBM bound) ------------------------------------------------------------
  * torch.nn.GroupNorm(32, C, eps)+SiLU of ResnetBlock2D.norm1/norm2, Transformer2DModel.norm,
  * conv_norm_out; torch.nn.LayerNorm of BasicTransformerBlock.norm1-3. */

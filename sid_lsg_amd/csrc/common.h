@@ -225,3 +225,9 @@ struct SidlsgTraceScope {
 
 // Launch-error helper for the extern "C" entry points: returns the HIP error code (0 = ok).
 static inline int sidlsg_last_error() { return (int)hipGetLastError(); }
+
+// Deterministic mode (sidlsg_set_deterministic, defined in gemm.hip): every parameter-gradient reduction takes an order-fixed form,
+// so its bits depend only on the inputs and the launch configuration.  Off: the atomic forms of the fast path.
+bool sidlsg_det();
+// The split-K / pixel-split scratch of stream `s` (sidlsg_set_stream_workspace, else sidlsg_set_workspace); null / 0 when none.
+float* sidlsg_ws_for_stream(hipStream_t s, long long* bytes);

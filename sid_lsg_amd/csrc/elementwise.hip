@@ -228,7 +228,9 @@ __global__ void add_kernel(const T* __restrict__ a, const T* __restrict__ b, T* 
 
 // ---- column sums of g [B][rows][N]: per_batch[b][n] += , total[n] += (fp32 atomics; callers zero per_batch) -----
 // grid (row chunks, B) fills the chip; 256 threads walk columns in passes of cpp 8-wide chunks, rows split over 256/cpp lanes.
-template <typename T>
+// SLAB (deterministic mode): no atomics; each block stores its chunk totals to per_batch = slab [B][row chunks][N] (ld_pb = N),
+// and colsum_slab_reduce_kernel adds them up in ascending chunk / batch order.
+template <typename T, bool SLAB = false>
 __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ g, float* __restrict__ per_batch,
                                                      float* __restrict__ total, int rows_per_batch, int N, int ldg,
                                                      int rows_per_chunk, int ld_pb) {
@@ -259,10 +261,44 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ g, fl
             if (col >= N) continue;
             float t = 0.f;
             for (int r = 0; r < rows; r++) t += sm[r * cpp * 8 + i];
-            if (per_batch) unsafeAtomicAdd(per_batch + (size_t)b * ld_pb + col, t);
-            if (total) unsafeAtomicAdd(total + col, t);
+            if constexpr (SLAB) {
+                per_batch[((size_t)b * gridDim.x + chunk) * N + col] = t;
+            } else {
+                if (per_batch) unsafeAtomicAdd(per_batch + (size_t)b * ld_pb + col, t);
+                if (total) unsafeAtomicAdd(total + col, t);
+            }
         }
     }
+}
+
+// Deterministic second pass over slab [B][nch][N]: block (64 columns, batch b); the 4 waves sum chunks c = w, w + 4, ... in
+// ascending order, wave 0 adds the four sums in wave order: per_batch[b][col] += s_b.  For `total`: B == 1 adds s_0 directly,
+// else s_b goes to sb [B][N] and colsum_total_kernel adds the batches in ascending order.
+__global__ __launch_bounds__(256) void colsum_slab_reduce_kernel(const float* __restrict__ slab, float* __restrict__ per_batch,
+                                                                 int ld_pb, float* __restrict__ total, float* __restrict__ sb,
+                                                                 int nch, int N) {
+    __shared__ float part[4][64];
+    const int tx = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int col = blockIdx.x * 64 + tx, b = blockIdx.y;
+    float s = 0.f;
+    if (col < N)
+        for (int c = w; c < nch; c += 4) s += slab[((size_t)b * nch + c) * N + col];
+    part[w][tx] = s;
+    __syncthreads();
+    if (w || col >= N) return;
+    s = part[0][tx] + part[1][tx] + part[2][tx] + part[3][tx];
+    if (per_batch) per_batch[(size_t)b * ld_pb + col] += s;
+    if (total) {
+        if (gridDim.y == 1) total[col] += s;
+        else sb[(size_t)b * N + col] = s;
+    }
+}
+__global__ void colsum_total_kernel(const float* __restrict__ sb, float* __restrict__ total, int B, int N) {
+    const int col = blockIdx.x * blockDim.x + threadIdx.x;
+    if (col >= N) return;
+    float t = 0.f;
+    for (int b = 0; b < B; b++) t += sb[(size_t)b * N + col];
+    total[col] += t;
 }
 
 // ---- weights: fp32 master -> bf16 compute copies ---------------------------------------------
@@ -594,7 +630,33 @@ static int colsum_t(const void* g, int ldg, float* per_batch, float* total, int 
     if (N % 8 || N <= 0 || (ld_pb && ld_pb < N)) return SIDLSG_EINVAL;
     const int nch = colsum_nchunks(B, rows_per_batch);
     const int rpc = (rows_per_batch + nch - 1) / nch;
-    hipLaunchKernelGGL(colsum_kernel<T>, dim3(nch, B), dim3(256), 0, (hipStream_t)stream, (const T*)g, per_batch, total,
+    hipStream_t s = (hipStream_t)stream;
+    if (sidlsg_det()) {
+        if (!per_batch && !total) return SIDLSG_OK;
+        // slab [B][nch][N] (+ [B][N] batch sums for `total`) in the stream's workspace
+        long long bytes = 0;
+        float* ws = sidlsg_ws_for_stream(s, &bytes);
+        const long long need = ((long long)B * nch * N + (total && B > 1 ? (long long)B * N : 0)) * 4;
+        if (ws && need <= bytes) {
+            float* sb = ws + (size_t)B * nch * N;
+            hipLaunchKernelGGL((colsum_kernel<T, true>), dim3(nch, B), dim3(256), 0, s, (const T*)g, ws, nullptr, rows_per_batch, N,
+                               ldg, rpc, N);
+            hipLaunchKernelGGL(colsum_slab_reduce_kernel, dim3((N + 63) / 64, B), dim3(256), 0, s, ws, per_batch, ld_pb ? ld_pb : N,
+                               total, sb, nch, N);
+            if (total && B > 1) hipLaunchKernelGGL(colsum_total_kernel, dim3((N + 255) / 256), dim3(256), 0, s, sb, total, B, N);
+            return sidlsg_last_error();
+        }
+        // no scratch: one chunk per batch (a single add per per_batch element), then `total` as ONE chunk over all B * rows rows
+        // (row b * rows_per_batch + r of g is batch b's row r) -- slow, order-fixed
+        if (per_batch)
+            hipLaunchKernelGGL(colsum_kernel<T>, dim3(1, B), dim3(256), 0, s, (const T*)g, per_batch, nullptr, rows_per_batch, N, ldg,
+                               rows_per_batch, ld_pb ? ld_pb : N);
+        if (total)
+            hipLaunchKernelGGL(colsum_kernel<T>, dim3(1, 1), dim3(256), 0, s, (const T*)g, nullptr, total, B * rows_per_batch, N, ldg,
+                               B * rows_per_batch, N);
+        return sidlsg_last_error();
+    }
+    hipLaunchKernelGGL(colsum_kernel<T>, dim3(nch, B), dim3(256), 0, s, (const T*)g, per_batch, total,
                        rows_per_batch, N, ldg, rpc, ld_pb ? ld_pb : N);
     return sidlsg_last_error();
 }

@@ -136,7 +136,7 @@ static int launch_gemm_f32(const GemmF32Params& p, hipStream_t s) {
 
 // ---------------------------------------------------------------------------------------------
 // weight gradient dW[N][K] += dY[M][N]^T A[M][K]: 64 (n) x 64 (k) tile, pixel contraction in LDS stages of 16 rows,
-// pixel range split over grid.y (fp32 atomics when split).
+// pixel range split over grid.y (fp32 atomics when split; in deterministic mode slabs in `ws` + wgrad_f32_reduce_kernel, or one split).
 struct WgradF32Params {
     const float* dY;  // [M][ldy]
     const float* A;   // dense [M][lda] or NHWC image
@@ -144,6 +144,7 @@ struct WgradF32Params {
     int M, N, K, ldy, lda;
     int H, Wd, Cin, Ho, Wo, stride, ups;
     int m_per_split, nsplits;
+    float* ws;        // deterministic mode: [nsplits][N][K] slabs (else null: atomics)
 };
 constexpr int WG_LD = 64 + 16;     // row stride: the two k-groups of a half-wave land on disjoint banks
 
@@ -219,9 +220,20 @@ __global__ __launch_bounds__(256) void wgrad_f32_kernel(WgradF32Params p) {
                 const int n = n0 + wn0 + 16 * i + lg * 4 + r;
                 if (n >= p.N) continue;
                 float* d = p.dW + (size_t)n * p.K + k;
-                if (p.nsplits == 1) *d += acc[i][j][r]; else unsafeAtomicAdd(d, acc[i][j][r]);
+                if (p.nsplits == 1) *d += acc[i][j][r];
+                else if (p.ws) p.ws[(size_t)blockIdx.y * p.N * p.K + (size_t)n * p.K + k] = acc[i][j][r];
+                else unsafeAtomicAdd(d, acc[i][j][r]);
             }
         }
+}
+
+// dW[e] += sum of the slabs in split order
+__global__ void wgrad_f32_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dW, size_t nk, int splits) {
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= nk) return;
+    float t = ws[e];
+    for (int sp = 1; sp < splits; sp++) t += ws[(size_t)sp * nk + e];
+    dW[e] += t;
 }
 
 template <int MODE>
@@ -234,8 +246,17 @@ static int launch_wgrad_f32(WgradF32Params p, hipStream_t s) {
     int mps = (p.M + splits - 1) / splits;
     mps = (mps + 15) / 16 * 16;
     splits = (p.M + mps - 1) / mps;
+    const size_t nk = (size_t)p.N * p.K;
+    p.ws = nullptr;
+    if (sidlsg_det() && splits > 1) {
+        long long bytes = 0;
+        float* ws = sidlsg_ws_for_stream(s, &bytes);
+        if (ws && (long long)(splits * nk * 4) <= bytes) p.ws = ws;
+        else { mps = (p.M + 15) / 16 * 16; splits = 1; }
+    }
     p.m_per_split = mps; p.nsplits = splits;
     hipLaunchKernelGGL((wgrad_f32_kernel<MODE>), dim3(tiles, splits), dim3(256), 0, s, p);
+    if (p.ws) hipLaunchKernelGGL(wgrad_f32_reduce_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, s, p.ws, p.dW, nk, splits);
     return sidlsg_last_error();
 }
 

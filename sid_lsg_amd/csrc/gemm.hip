@@ -742,6 +742,18 @@ static Ws ws_for(hipStream_t s) {
         if (g_ws_slots[i].stream == s) return {g_ws_slots[i].ptr, g_ws_slots[i].bytes};
     return {g_ws_default, g_ws_default_bytes};
 }
+float* sidlsg_ws_for_stream(hipStream_t s, long long* bytes) {
+    const Ws w = ws_for(s);
+    *bytes = w.ptr ? w.bytes : 0;
+    return w.ptr;
+}
+
+// Deterministic mode: -2 = not read yet (SIDLSG_DETERMINISTIC), else 0 / 1.  Process-wide, like g_p8_mode.
+static int g_det_mode = -2;
+bool sidlsg_det() {
+    if (g_det_mode == -2) g_det_mode = (getenv("SIDLSG_DETERMINISTIC") && atoi(getenv("SIDLSG_DETERMINISTIC"))) ? 1 : 0;
+    return g_det_mode == 1;
+}
 
 // ---------------------------------------------------------------------------------------------
 // Direct-to-LDS (buffer_load ... lds) kernels.  (A 256 x 160 / 8-wave / 3-stage-ring variant "v2" and a
@@ -2558,6 +2570,12 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ ws, float* __restr
 }
 
 
+extern "C" int sidlsg_colsum(const void* g, int ldg, float* per_batch, float* total, float* ws, int B, int rows_per_batch, int N,
+                             void* stream);
+
+// Deterministic mode, weight gradients: the pixel splits never meet in fp32 atomics.  dW: slabs + wgrad_reduce_kernel (split order) or
+// one split when no two slabs fit; the bias: the k-tile-0 blocks of every split added into dB, so with several splits the kernel
+// gets no dB and the bias gradient is an order-fixed column sum of dY (sidlsg_colsum, B = 1) after it.
 template <int MODE>
 static int launch_wgrad(WgradParams p, hipStream_t s) {
     static const bool v2_on = !(getenv("SIDLSG_WGRAD_V2") && atoi(getenv("SIDLSG_WGRAD_V2")) == 0);
@@ -2618,6 +2636,14 @@ static int launch_wgrad(WgradParams p, hipStream_t s) {
             p.ws = g_ws;
         }
     }
+    float* det_dB = nullptr;
+    if (sidlsg_det() && splits > 1) {
+        if (!p.ws || (p.dB && (p.N & 7))) {
+            splits = 1; mps = (p.M + WG_MB - 1) / WG_MB * WG_MB; p.ws = nullptr;
+        } else {
+            det_dB = p.dB; p.dB = nullptr;
+        }
+    }
     p.m_per_split = mps;
     p.nsplits = splits;
     if (p.assign && splits > 1 && !p.ws) {          // fp32-atomic fallback (no slab space): the atomics need a zeroed target
@@ -2650,6 +2676,7 @@ static int launch_wgrad(WgradParams p, hipStream_t s) {
     SIDLSG_LAUNCH((wgrad_bf16_kernel<MODE>), dim3(tiles, splits), dim3(NTHREADS), 0, s, p);
     if (splits > 1 && p.ws)
         SIDLSG_LAUNCH(wgrad_reduce_kernel, dim3((unsigned)((nk / 4 + 256) / 256)), dim3(256), 0, s, p.ws, p.dW, (size_t)nk, splits, p.assign);
+    if (det_dB) return sidlsg_colsum(p.dY, p.ldy, nullptr, det_dB, nullptr, 1, p.M, p.N, s);      // after the reduction: it reuses the workspace
     return sidlsg_last_error();
 }
 
@@ -2678,6 +2705,7 @@ static int launch_wgrad_group(WgradParams* jobs, int njobs, hipStream_t s, bool 
     int blocks = 0, rjobs = 0;
     unsigned rblocks = 0;
     long long ws_used = 0;
+    float* det_dB[WG_GROUP] = {};
     for (int i = 0; i < njobs; i++) {
         WgradParams p = jobs[i];
         const int max_splits = (p.M + 4 * WG_MB - 1) / (4 * WG_MB);
@@ -2697,6 +2725,7 @@ static int launch_wgrad_group(WgradParams* jobs, int njobs, hipStream_t s, bool 
             }
             if (splits > 1) { p.ws = reinterpret_cast<float*>(reinterpret_cast<char*>(wsl.ptr) + ws_used); ws_used += ((long long)splits * nk * 4 + 255) / 256 * 256; }
         }
+        if (sidlsg_det() && splits > 1 && p.dB) { det_dB[i] = p.dB; p.dB = nullptr; }      // (see launch_wgrad)
         p.m_per_split = mps;
         p.nsplits = splits;
         g.blk0[i] = blocks;
@@ -2722,6 +2751,9 @@ static int launch_wgrad_group(WgradParams* jobs, int njobs, hipStream_t s, bool 
     if (t160) SIDLSG_LAUNCH(wgrad_v2sg_kernel, dim3(blocks), dim3(NTHREADS), lds, s, g);
     else SIDLSG_LAUNCH(wgrad_v2g_kernel, dim3(blocks), dim3(NTHREADS), lds, s, g);
     if (rjobs) SIDLSG_LAUNCH(wgrad_reduce_g_kernel, dim3(rblocks), dim3(256), 0, s, rg);
+    for (int i = 0; i < njobs; i++)
+        if (det_dB[i])
+            if (int e = sidlsg_colsum(jobs[i].dY, jobs[i].ldy, nullptr, det_dB[i], nullptr, 1, jobs[i].M, jobs[i].N, s)) return e;
     return sidlsg_last_error();
 }
 
@@ -2736,6 +2768,13 @@ int sidlsg_debug_wgrad_blocks_per_cu(int which) {
     (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, f, NTHREADS, lds) != hipSuccess) return -1;
     return n;
+}
+
+// Deterministic mode: 1 on, 0 off, -1 query only.  Returns the previous setting.  See include/sidlsg_hip.h.
+int sidlsg_set_deterministic(int on) {
+    const int old = sidlsg_det() ? 1 : 0;
+    if (on >= 0) g_det_mode = on ? 1 : 0;
+    return old;
 }
 
 // (A/B switch) which GEMM / conv calls take the 256-row-tile kernels of gemm_p8.h: -1 by rule (default), 0 never, 1 / 2 every

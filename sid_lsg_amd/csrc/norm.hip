@@ -319,8 +319,10 @@ __global__ void colsum_reduce2_kernel(const float* __restrict__ part, float* __r
     }
     if (p1 > p0) { unsafeAtomicAdd(out0 + i, t0); unsafeAtomicAdd(out1 + i, t1); }
 }
+// Deterministic mode: grid.y = 1 -- one thread per channel sums p = 0 .. P-1 in order and adds once (the immediate launch and the
+// deferred batch then give equal bits)
 static dim3 reduce_grid(int n, int P) {
-    int split = (P + 15) / 16; if (split > 64) split = 64; if (split < 1) split = 1;
+    int split = (P + 15) / 16; if (split > 64) split = 64; if (split < 1 || sidlsg_det()) split = 1;
     return dim3((n + 255) / 256, split);
 }
 
@@ -1151,7 +1153,10 @@ static int groupnorm_bwd_t(const void* x, const void* dy, const float* stats, co
     const double tb_ = (double)B * HW * C * sizeof(T) * (dres ? 4 : 3);
     SidlsgTraceScope ts(SIDLSG_FAM_GN_BWD, tb_, tb_);                // read x, dy (, dres), write dx
     hipStream_t s = (hipStream_t)stream;
-    if constexpr (std::is_same<T, bf16>::value) {
+    // deterministic mode: the one-pass kernels add dgamma / dbeta per block with atomics -- a trainable layer takes the two-kernel
+    // path (fixed-order partials + colsum_reduce2); frozen layers (no parameter gradients) keep them
+    const bool onepass_ok = !(sidlsg_det() && dgamma && dbeta);
+    if constexpr (std::is_same<T, bf16>::value) if (onepass_ok) {
         GnSmall gs; int th, P;
         // one-pass kernel: x and dy read once, one launch (+ atomics for dgamma / dbeta); <= 8 chunks of x AND dy per thread (256 VGPRs
         // without spills): 8x8 stage 22.7 -> 9.0 us, 16x16 at 1280 channels 32.0 -> 15.6 us; beyond that the two-kernel path is faster
@@ -1163,7 +1168,7 @@ static int groupnorm_bwd_t(const void* x, const void* dy, const float* stats, co
             return sidlsg_last_error();
         }
     }
-    if constexpr (std::is_same<T, bf16>::value) {
+    if constexpr (std::is_same<T, bf16>::value) if (onepass_ok) {
         GnGrp gg; int th, P;
         if (gn_grp_geom(gg, th, P, B, HW, C, G, 64, 32, 1)) {      // x in registers (<= 64 dwords per thread in <= 640 threads, 32 in <= 1024), dy streamed twice
             const size_t lds = (dgamma && dbeta) ? (size_t)gg.R * gg.D * 4 * sizeof(float) : 0;

@@ -12,7 +12,9 @@ contiguous; parameters are fp32
 weight/bias gradients are ACCUMULATED IN PLACE by the kernels (atomics / +=) and the autograd
 functions return None for them, so no per-parameter gradient tensors are ever materialised.
 """
+import contextlib
 import ctypes
+import functools
 import weakref
 import os
 
@@ -122,6 +124,63 @@ def side_stream(device):
     return _side_streams[key]
 
 
+# ---- deterministic mode ---------------------------------------------------------------------------------------------------------
+# include/sidlsg_hip.h sidlsg_set_deterministic: every parameter-gradient reduction of the library in an order-fixed form.  On the host
+# side the mode also keeps the weight gradients on ONE side stream (wgrad_stream) and the optimizer steps after the whole backward
+# (sid_step.py: no segment-wise updates).  Policy: an explicit set_deterministic(True / False) wins; None (the default) = on when
+# SIDLSG_DETERMINISTIC is a non-zero integer, else what torch.use_deterministic_algorithms() says.  sync_deterministic() writes the
+# effective value to the library; every backward of this module calls it first, so a caller who only sets the torch flag and then
+# runs loss.backward() gets the deterministic kernels.
+def _env_int(name):
+    try:
+        return int(os.environ.get(name, '0').strip() or '0')
+    except ValueError:
+        return 0
+
+
+_det_explicit = None
+_det_env = _env_int('SIDLSG_DETERMINISTIC') != 0
+_det_lib = None            # the value last written to the library
+
+
+def is_deterministic():
+    """The effective mode (see set_deterministic)."""
+    if _det_explicit is not None:
+        return _det_explicit
+    return _det_env or torch.are_deterministic_algorithms_enabled()
+
+
+def sync_deterministic():
+    """Write the effective mode to the library's process-wide flag (when it changed); returns it."""
+    global _det_lib
+    on = is_deterministic()
+    if on != _det_lib:
+        lib.sidlsg_set_deterministic.raw(1 if on else 0)
+        _det_lib = on
+    return on
+
+
+def set_deterministic(mode):
+    """mode: True / False = on / off whatever the environment says; None = follow SIDLSG_DETERMINISTIC, then the torch flag.
+    Returns the effective mode.  A captured graph keeps the kernels of the mode it was captured in."""
+    global _det_explicit
+    if mode is not True and mode is not False and mode is not None:
+        raise ValueError(f'set_deterministic: expected True, False or None, got {mode!r}')
+    _det_explicit = mode
+    return sync_deterministic()
+
+
+@contextlib.contextmanager
+def deterministic(mode=True):
+    """with ops.deterministic(): ... -- set_deterministic(mode) for the block, the previous setting restored after it."""
+    old = _det_explicit
+    set_deterministic(mode)
+    try:
+        yield
+    finally:
+        set_deterministic(old)
+
+
 # ---- weight gradients on their own stream ---------------------------------------------------------------------------------
 # A weight-gradient launch is one round of equal-work blocks: they start together, wait for their tile DMAs together and end in
 # a chip-wide burst of slab writes followed by a small reduction kernel (tools/ab/wgrad_trace.py) -- MFMA and HBM idle in
@@ -175,6 +234,8 @@ def _wgrad_stream_list(device):
 def wgrad_stream(device):
     """The stream of the next weight-gradient launch (round robin when several are configured)."""
     lst = _wgrad_stream_list(device)
+    if len(lst) > 1 and is_deterministic():
+        return lst[0]             # one stream: launches that share a dW stay ordered
     key = _dev_key(device)
     i = _wgrad_rr.get(key, 0)
     _wgrad_rr[key] = (i + 1) % len(lst)
@@ -537,6 +598,7 @@ def colsum(g2d, rows_per_batch, per_batch=False, total=None, slot=None):
     part's columns of the holder's shared [B, sum C] gradient buffer (zeroed once per backward pass) and a view of it is returned."""
     R, N = g2d.shape
     B = R // rows_per_batch
+    sync_deterministic()
     if per_batch and slot is not None and slot[2] == N:
         holder, off, _ = slot
         buf = holder.buffer(B, g2d.device)
@@ -1735,3 +1797,18 @@ def cast_bf16(src_f32, out=None):
         out = torch.empty(src_f32.shape, device=src_f32.device, dtype=BF16)
     lib.sidlsg_cast_f32_bf16(_p(src_f32), _p(out), src_f32.numel(), _s())
     return out
+
+
+def _det_synced(backward):
+    @functools.wraps(backward)
+    def wrapper(*args):
+        sync_deterministic()
+        return backward(*args)
+    return staticmethod(wrapper)
+
+
+# every backward of this module sees the current deterministic mode (see sync_deterministic)
+for _cls in list(globals().values()):
+    if isinstance(_cls, type) and issubclass(_cls, torch.autograd.Function) and _cls.__module__ == __name__ and 'backward' in _cls.__dict__:
+        _cls.backward = _det_synced(_cls.__dict__['backward'].__func__)
+del _cls

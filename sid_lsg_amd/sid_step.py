@@ -138,6 +138,11 @@ class SiDStep:
         self.seg_opt = bool(on)
         self.opt_stream = torch.cuda.Stream(self.G.flat_params.device) if on else None
 
+    def _seg_opt_on(self):
+        # deterministic mode: the optimizer reads a gradient only after the whole backward (a segment's update may not start while
+        # weight-gradient or deferred reductions into it are still in flight)
+        return self.seg_opt and not ops.is_deterministic()
+
     def _init_t(self, n, device):
         return torch.full((n,), self.init_timestep, device=device, dtype=torch.long)
 
@@ -204,7 +209,7 @@ class SiDStep:
         return loss
 
     def fake_update(self, rounds):
-        if self.seg_opt:
+        if self._seg_opt_on():
             seg = _SegmentedUpdate(self, self.psi, self.opt_fake)
             loss = self.fake_backward(rounds, seg)
             seg.start_last()
@@ -266,7 +271,7 @@ class SiDStep:
         self.G.requires_grad_(True)                                                 # :468
         self.psi.requires_grad_(False)
         loss = None
-        if self.seg_opt:
+        if self._seg_opt_on():
             seg = _SegmentedUpdate(self, self.G, self.opt_G)
             for i, r in enumerate(rounds):
                 if i == len(rounds) - 1:
@@ -306,7 +311,7 @@ class SiDStep:
         Same result as fake_update(); generator_update(), but the psi gradient all-reduce + optimizer step are issued
         after phase A's backward and only WAITED for right before psi is evaluated in phase B, i.e. they overlap with
         the generator forward and the teacher forward of the first phase-B round."""
-        if self.seg_opt:
+        if self._seg_opt_on():
             # psi: segments 0 / 1 are exchanged + updated during its backward, the last one right after it on the optimizer
             # stream -- beside the generator forward and the teacher forward; joined right before psi is evaluated
             seg = _SegmentedUpdate(self, self.psi, self.opt_fake)

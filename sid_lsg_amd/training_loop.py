@@ -27,6 +27,7 @@ import psutil
 import torch
 
 from . import distributed as dist
+from . import ops
 from .data import InfiniteSampler, prompt_batches
 from .dnnlib_util import EasyDict, construct_class_by_name, format_time
 from .distributed import FlatGradReducer
@@ -100,7 +101,7 @@ def training_loop(
     pretrained_vae_model_name_or_path='runwayml/stable-diffusion-v1-5', fake_score_use_lora=False,
     dataset_prompt_text_kwargs={}, cfg_train_fake=1, cfg_eval_fake=1, cfg_eval_real=1, num_steps=1, train_mode=True,
     network_pkl=None, enable_xformers=True, gradient_checkpointing=False, resolution=512, on_iteration=None,
-    rng_device=None, metric_real_stats=None, metric_num_test=None,
+    rng_device=None, metric_real_stats=None, metric_num_test=None, deterministic=False,
 ):
     if not train_mode:
         return evaluate_network(run_dir=run_dir, dataset_kwargs=dataset_kwargs, network_kwargs=network_kwargs, device=device, metrics=metrics,
@@ -112,6 +113,9 @@ def training_loop(
         raise NotImplementedError(f'num_steps={num_steps}: only the one-step generator is trained (the reference marks its '
                                   'multi-step training sampler as unfinished, sid_sd_util.py:165)')
     rank, world = dist.get_rank(), dist.get_world_size()
+    if deterministic:       # bit-reproducible step for this process (else the default policy: SIDLSG_DETERMINISTIC, the torch flag)
+        ops.set_deterministic(True)
+    dist.print0(f'Deterministic mode: {"on" if ops.is_deterministic() else "off"}')
     if dict(network_kwargs).get('use_fp16'):
         dist.print0('note: --fp16 is accepted for compatibility; this path keeps fp32 masters and computes in bf16 (no fp16 '
                     'weights / optimizer state, hence no fp16 gradient clipping)')

@@ -12,6 +12,8 @@ Differences (documented, not silent):
   * `--sd_model` must be a local diffusers-layout directory or `random:<arch>` (no network in this environment);
   * `--fp16` only selects the optimizer eps; masters are fp32 and compute is bf16 MFMA, or -- with the added option
     `--precision fp32` -- the fp32-accurate mode (the reference's own default precision, ~20x slower);
+  * `--deterministic 1` (added option) makes the training step bit-reproducible: same tree, GPU model, configuration and
+    world size give the same bits (sid_lsg_amd.ops.set_deterministic);
   * `--metrics` run through sid_lsg_amd/metrics.py at the snapshot ticks and need LOCAL detector / statistics files
     (--metric_pt_path, --data_stat); `--train_mode 0 --network_pkl <snapshot>` evaluates a snapshot (1 / 2 / 4 steps);
   * `--data` is optional (it is the COCO image set used only by the metrics).
@@ -66,6 +68,7 @@ OPTIONS = [
     (('--init_timestep',), dict(type=int, default=625, show_default=True, metavar='INT', help='t_init, in [0,999]')),
     (('--fp16',), dict(type=bool, default=False, show_default=True, metavar='BOOL', help='Reference fp16 recipe (optimizer eps 1e-6)')),
     (('--precision',), dict(type=click.Choice(['bf16', 'fp32']), default='bf16', show_default=True, help='Compute dtype of the HIP path (not a reference option)')),
+    (('--deterministic',), dict(type=bool, default=False, show_default=True, metavar='BOOL', help='Bit-reproducible training step: order-fixed gradient reductions (not a reference option)')),
     (('--teacher-weights', 'teacher_weights'), dict(type=click.Choice(['bf16', 'fp8', 'fp8-frozen']), default='bf16', show_default=True, help='fp8: frozen teacher forward weights as e4m3 + per-channel scales; fp8-frozen: every pass without weight gradients (not a reference option)')),
     (('--ls',), dict(type=click.FloatRange(min=0, min_open=True), default=1, show_default=True, help='Loss scaling')),
     (('--lsg',), dict(type=click.FloatRange(min=0, min_open=True), default=1, show_default=True, help='Loss scaling G')),
@@ -138,6 +141,7 @@ def build_config(o):
     c.g_optimizer_kwargs = EasyDict(class_name=cls, lr=o.glr, betas=[0.0, 0.999], eps=eps, **extra)
     c.network_kwargs = EasyDict(use_fp16=o.fp16, compute_dtype=o.get('precision', 'bf16'), teacher_weights=o.get('teacher_weights', 'bf16'))
     c.loss_kwargs = EasyDict()
+    c.deterministic = bool(o.get('deterministic', False))
     c.init_timestep = o.init_timestep
     c.total_kimg = max(int(o.duration * 1000), 1)
     c.ema_halflife_kimg = int(o.ema * 1000)
