@@ -237,6 +237,17 @@ int sidlsg_cfg_x0(const float* eps, const float* xt, const float* s0, const floa
                   int Ce, int dup, float kappa, int mode, void* stream);
 int sidlsg_cfg_x0_bwd(const float* g, const float* s0, const float* s1, void* deps, float* dxt, int B, int C, int HW, int Cp,
                       int dup, float kappa, int mode, void* stream);
+/* step_renoise: one step boundary of the multi-step generator (sid_sd_util.py:176-185) as one launch.  eps [B][HW][8] fp32 (the
+ *   generator's output at t_i), xt fp32 NCHW (x_{t_i}), s0/s1 the coefficients of t_i, s0n/s1n those of t_{i+1}, noise fp32 NCHW
+ *   (eps_{i+1}): x_hat = x0 prediction by `mode` (1 epsilon, 2 v; as cfg_x0 with dup = 1), x_{t+1} = s0n*x_hat + s1n*noise ->
+ *   out NHWC [B][HW][Cp] activations (channels C.. zero) and xtn fp32 NCHW.  Bit-equal to cfg_x0 followed by noisy_input.
+ * step_renoise_bwd: g NHWC [B][HW][Cp] (gradient at the next step's input) and gxtn fp32 NCHW (gradient of x_{t+1}, may be
+ *   NULL): d x_hat = s0n*(g + gxtn), then cfg_x0_bwd's formulas: deps NHWC [B][HW][Cp] (zero padded) and, when dxt != NULL,
+ *   d x_t fp32 NCHW.  Any other mode -> SIDLSG_EINVAL. */
+int sidlsg_step_renoise(const float* eps, const float* xt, const float* s0, const float* s1, const float* s0n, const float* s1n,
+                        const float* noise, void* out, float* xtn, int B, int C, int HW, int Cp, int mode, void* stream);
+int sidlsg_step_renoise_bwd(const void* g, const float* gxtn, const float* s0, const float* s1, const float* s0n, void* deps,
+                            float* dxt, int B, int C, int HW, int Cp, int mode, void* stream);
 
 /* ---- losses with closed-form gradients (sid_training_loop.py:423-445, 508-530) -------------
  * Per-sample NaN filtering is done in-kernel (a sample containing NaN contributes 0 and gets zero
@@ -371,6 +382,11 @@ int sidlsg_noisy_input_bwd_f32(const void* g, const float* s0, float* dx0, int B
                                int accumulate, void* stream);
 int sidlsg_cfg_x0_bwd_f32(const float* g, const float* s0, const float* s1, void* deps, float* dxt, int B, int C, int HW,
                           int Cp, int dup, float kappa, int mode, void* stream);
+int sidlsg_step_renoise_f32(const float* eps, const float* xt, const float* s0, const float* s1, const float* s0n,
+                            const float* s1n, const float* noise, void* out, float* xtn, int B, int C, int HW, int Cp, int mode,
+                            void* stream);
+int sidlsg_step_renoise_bwd_f32(const void* g, const float* gxtn, const float* s0, const float* s1, const float* s0n, void* deps,
+                                float* dxt, int B, int C, int HW, int Cp, int mode, void* stream);
 int sidlsg_timestep_embed_f32(const long long* t, void* out, int B, int dim, void* stream);
 int sidlsg_silu_fwd_f32(const void* x, void* y, long long n, void* stream);
 int sidlsg_silu_bwd_f32(const void* x, const void* dy, void* dx, long long n, void* stream);

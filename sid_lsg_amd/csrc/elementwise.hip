@@ -103,6 +103,65 @@ __global__ void cfg_x0_bwd_kernel(const float* __restrict__ g, const float* __re
     }
 }
 
+// ---- multi-step generator: one step boundary as one kernel each way (sid_sd_util.py:176-185) ---------------------------------
+// Forward: x_hat = x0 prediction of step i from the generator output eps [B][HW][8] fp32 and x_t (a* = coefficients of t_i), then
+// x_{t+1} = s0n*x_hat + s1n*noise (coefficients of t_{i+1}) -> NHWC activations [B][HW][Cp] of T (channels C.. zero) and x_{t+1}
+// fp32 NCHW.  The fp32 expressions are those of cfg_x0_kernel<MODE> (dup = 1) and noisy_input_kernel, so the result is bit-equal
+// to the two launches.  MODE 1: x_hat = (x_t - s1*e)/s0 (epsilon), 2: x_hat = s0*x_t - s1*e (v).
+template <typename T, int MODE>
+__global__ __launch_bounds__(256) void step_renoise_kernel(const float* __restrict__ eps, const float* __restrict__ xt,
+                                                           const float* __restrict__ s0, const float* __restrict__ s1,
+                                                           const float* __restrict__ s0n, const float* __restrict__ s1n,
+                                                           const float* __restrict__ noise, T* __restrict__ out,
+                                                           float* __restrict__ xtn, int B, int C, int HW, int Cp) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;  // over B*HW
+    if (idx >= B * HW) return;
+    const int b = idx / HW, p = idx - b * HW;
+    float e[8], o[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    ldv8<float>(eps + (size_t)idx * 8, e);
+#pragma unroll
+    for (int c = 0; c < 8; c++) {
+        if (c >= C) break;
+        const size_t i = ((size_t)b * C + c) * HW + p;
+        // the roundings are spelled out: they are the ones the compiler chose for cfg_x0_kernel (mode 1: one fma, then the division;
+        // mode 2: two rounded products, no fma) and noisy_input_kernel (rounded s1*noise, then one fma)
+        const float xh = MODE == 1 ? __builtin_fmaf(-s1[b], e[c], xt[i]) / s0[b] : __fmul_rn(s0[b], xt[i]) - __fmul_rn(s1[b], e[c]);
+        const float v = __builtin_fmaf(s0n[b], xh, __fmul_rn(s1n[b], noise[i]));
+        xtn[i] = v;
+        o[c] = v;
+    }
+    T* dst = out + (size_t)idx * Cp;
+    stv8<T>(dst, o);
+    for (int c = 8; c < Cp; c += 8) zerov8<T>(dst + c);
+}
+
+// Backward: g = gradient at the next step's input (NHWC [B][HW][Cp] of T), gxtn = gradient of x_{t+1} (fp32 NCHW, may be null).
+// d x_hat = s0n*(g + gxtn); then cfg_x0_bwd_kernel<T, MODE>'s formulas: d_eps (NHWC [B][HW][Cp] of T, zero padded) and, when
+// dxt != null, d x_t (fp32 NCHW).
+template <typename T, int MODE>
+__global__ __launch_bounds__(256) void step_renoise_bwd_kernel(const T* __restrict__ g, const float* __restrict__ gxtn,
+                                                               const float* __restrict__ s0, const float* __restrict__ s1,
+                                                               const float* __restrict__ s0n, T* __restrict__ deps,
+                                                               float* __restrict__ dxt, int B, int C, int HW, int Cp) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= B * HW) return;
+    const int b = idx / HW, p = idx - b * HW;
+    float v[8], du[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    ldv8<T>(g + (size_t)idx * Cp, v);
+#pragma unroll
+    for (int c = 0; c < 8; c++) {
+        if (c >= C) break;
+        const size_t i = ((size_t)b * C + c) * HW + p;
+        const float d = gxtn ? v[c] + gxtn[i] : v[c];
+        const float go = s0n[b] * d;
+        du[c] = MODE == 1 ? -go * s1[b] / s0[b] : -go * s1[b];
+        if (dxt) dxt[i] = MODE == 1 ? go / s0[b] : go * s0[b];
+    }
+    T* d0 = deps + (size_t)idx * Cp;
+    stv8<T>(d0, du);
+    for (int c = 8; c < Cp; c += 8) zerov8<T>(d0 + c);
+}
+
 // ---- timestep embedding: [cos | sin] of t * exp(-ln(1e4) * i/half), [B][dim] ---------------
 template <typename T>
 __global__ void timestep_embed_kernel(const long long* __restrict__ t, T* __restrict__ out, int B, int dim) {
@@ -698,6 +757,27 @@ __global__ __launch_bounds__(256) void scale_cast_ranges_kernel(const ScJob* __r
     }
 }
 
+template <typename T>
+static int step_renoise_t(const float* eps, const float* xt, const float* s0, const float* s1, const float* s0n, const float* s1n,
+                          const float* noise, void* out, float* xtn, int B, int C, int HW, int Cp, int mode, void* stream) {
+    if (!eps || !xt || !noise || !out || !xtn || C < 1 || C > 8 || Cp % 8 || Cp < 8 || (mode != 1 && mode != 2)) return SIDLSG_EINVAL;
+    const dim3 grid = GRID1D((size_t)B * HW, 256);
+    hipStream_t s = (hipStream_t)stream;
+    if (mode == 1) hipLaunchKernelGGL((step_renoise_kernel<T, 1>), grid, dim3(256), 0, s, eps, xt, s0, s1, s0n, s1n, noise, (T*)out, xtn, B, C, HW, Cp);
+    else hipLaunchKernelGGL((step_renoise_kernel<T, 2>), grid, dim3(256), 0, s, eps, xt, s0, s1, s0n, s1n, noise, (T*)out, xtn, B, C, HW, Cp);
+    return sidlsg_last_error();
+}
+template <typename T>
+static int step_renoise_bwd_t(const void* g, const float* gxtn, const float* s0, const float* s1, const float* s0n, void* deps,
+                              float* dxt, int B, int C, int HW, int Cp, int mode, void* stream) {
+    if (!g || !deps || C < 1 || C > 8 || Cp % 8 || Cp < 8 || (mode != 1 && mode != 2)) return SIDLSG_EINVAL;
+    const dim3 grid = GRID1D((size_t)B * HW, 256);
+    hipStream_t s = (hipStream_t)stream;
+    if (mode == 1) hipLaunchKernelGGL((step_renoise_bwd_kernel<T, 1>), grid, dim3(256), 0, s, (const T*)g, gxtn, s0, s1, s0n, (T*)deps, dxt, B, C, HW, Cp);
+    else hipLaunchKernelGGL((step_renoise_bwd_kernel<T, 2>), grid, dim3(256), 0, s, (const T*)g, gxtn, s0, s1, s0n, (T*)deps, dxt, B, C, HW, Cp);
+    return sidlsg_last_error();
+}
+
 extern "C" {
 
 int sidlsg_scale_cast_ranges(const void* jobs, int njobs, int nblocks, void* stream) {
@@ -734,6 +814,12 @@ int sidlsg_cfg_x0(const float* eps, const float* xt, const float* s0, const floa
 SIDLSG_BOTH(sidlsg_cfg_x0_bwd, cfg_x0_bwd_t,
             (const float* g, const float* s0, const float* s1, void* deps, float* dxt, int B, int C, int HW, int Cp, int dup, float kappa, int mode, void* stream),
             (g, s0, s1, deps, dxt, B, C, HW, Cp, dup, kappa, mode, stream))
+SIDLSG_BOTH(sidlsg_step_renoise, step_renoise_t,
+            (const float* eps, const float* xt, const float* s0, const float* s1, const float* s0n, const float* s1n, const float* noise, void* out, float* xtn, int B, int C, int HW, int Cp, int mode, void* stream),
+            (eps, xt, s0, s1, s0n, s1n, noise, out, xtn, B, C, HW, Cp, mode, stream))
+SIDLSG_BOTH(sidlsg_step_renoise_bwd, step_renoise_bwd_t,
+            (const void* g, const float* gxtn, const float* s0, const float* s1, const float* s0n, void* deps, float* dxt, int B, int C, int HW, int Cp, int mode, void* stream),
+            (g, gxtn, s0, s1, s0n, deps, dxt, B, C, HW, Cp, mode, stream))
 SIDLSG_BOTH(sidlsg_timestep_embed, timestep_embed_t, (const long long* t, void* out, int B, int dim, void* stream), (t, out, B, dim, stream))
 SIDLSG_BOTH(sidlsg_silu_fwd, silu_fwd_t, (const void* x, void* y, long long n, void* stream), (x, y, n, stream))
 SIDLSG_BOTH(sidlsg_silu_bwd, silu_bwd_t, (const void* x, const void* dy, void* dx, long long n, void* stream), (x, dy, dx, n, stream))

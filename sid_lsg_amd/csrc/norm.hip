@@ -392,6 +392,11 @@ static bool defer_pairs(hipStream_t s, const float* part, float* out0, float* ou
     std::lock_guard<std::mutex> lk(d.mu);
     auto it = d.q.find(s);
     if (it == d.q.end() || !it->second.accepting) return false;
+    // A parameter reached twice in one backward pass (a network applied several times: the N steps of a multi-step generator): what
+    // is queued is launched first, so the two sums reach out0 / out1 in stream order.  In one batched launch their atomic adds would
+    // commit in either order, and deterministic mode promises one add per channel per reduction in a fixed order.
+    for (const PairJob& j : it->second.jobs)
+        if ((out0 && j.out0 == out0) || (out1 && j.out1 == out1)) { flush_pairs_locked(s, it->second.jobs); break; }
     const dim3 g = reduce_grid(n, P);
     it->second.jobs.push_back(PairJob{part, out0, out1, (unsigned)n, (unsigned)P, (unsigned)pstride, 0u, g.x, g.y});
     return true;

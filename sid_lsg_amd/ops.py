@@ -242,6 +242,12 @@ def wgrad_stream(device):
     return lst[i]
 
 
+def wgrad_stream_count():
+    """How many streams the weight-gradient launches of a backward pass are spread over (two launches on one dW are ordered
+    only when this is 1)."""
+    return 1 if (not _WGRAD_SIDE or is_deterministic()) else _WGRAD_NSTREAMS
+
+
 def grad_streams(device):
     """Side streams that may still be writing parameter gradients of `device` (a gradient exchange must wait for them)."""
     return list(_wgrad_streams.get(_dev_key(device), ()))
@@ -1601,6 +1607,43 @@ def cfg_x0(eps, xt, s0, s1, kappa, predict_x0, act_dtype=BF16, prediction_type='
     predict_x0 False returns the guided network output itself."""
     mode = prediction_mode(prediction_type) if predict_x0 else 0
     return _CfgX0.apply(eps, xt, s0, s1, kappa, mode, act_dtype)
+
+
+class _StepRenoise(torch.autograd.Function):
+    """One step boundary of the multi-step generator (sidlsg_step_renoise): the generator output eps [B,HW,8] fp32 at t_i and x_{t_i}
+    -> x_hat (x0 prediction, mode 1 epsilon / 2 v) -> x_{t_{i+1}} = s0n*x_hat + s1n*noise, returned as (NHWC activations [B,H,W,8] of
+    `dtype`, x_{t_{i+1}} fp32 NCHW).  Forward bit-equal to cfg_x0(..., True) followed by noisy_input(x_hat, noise, s0n, s1n, 1)."""
+
+    @staticmethod
+    def forward(ctx, eps, xt, s0, s1, s0n, s1n, noise, mode, dtype):
+        B, C, H, W = xt.shape
+        if tuple(eps.shape) != (B, H * W, 8) or tuple(noise.shape) != tuple(xt.shape):
+            raise RuntimeError(f'step_renoise: eps {tuple(eps.shape)} / noise {tuple(noise.shape)} do not match x_t {tuple(xt.shape)}')
+        out = torch.empty((B, H, W, 8), device=xt.device, dtype=dtype)
+        xtn = torch.empty_like(xt)
+        _fn('step_renoise', dtype)(_p(_chk(eps, F32)), _p(_chk(xt, F32)), _p(s0), _p(s1), _p(s0n), _p(s1n), _p(_chk(noise, F32)),
+                                   _p(out), _p(xtn), B, C, H * W, 8, mode, _s())
+        ctx.save_for_backward(s0, s1, s0n)
+        ctx.cfg = (B, C, H, W, mode, dtype)
+        return out, xtn
+
+    @staticmethod
+    def backward(ctx, g, gxtn):
+        s0, s1, s0n = ctx.saved_tensors
+        B, C, H, W, mode, dtype = ctx.cfg
+        g = g.contiguous()
+        if g.dtype != dtype:
+            g = g.to(dtype)
+        gxtn = gxtn.contiguous() if gxtn is not None else None
+        deps = torch.empty((B, H * W, 8), device=g.device, dtype=dtype)      # the network's activation dtype (as _CfgX0)
+        dxt = torch.empty((B, C, H, W), device=g.device, dtype=F32) if ctx.needs_input_grad[1] else None
+        _fn('step_renoise_bwd', dtype)(_p(g), _p(gxtn), _p(s0), _p(s1), _p(s0n), _p(deps), _p(dxt), B, C, H * W, 8, mode, _s())
+        return deps, dxt, None, None, None, None, None, None, None
+
+
+def step_renoise(eps, xt, s0, s1, s0n, s1n, noise, act_dtype=BF16, prediction_type='epsilon'):
+    """x_hat of step i (coefficients s0, s1 of t_i) re-noised to t_{i+1} (s0n, s1n) with `noise`: -> (next input, x_{t_{i+1}})."""
+    return _StepRenoise.apply(eps, xt, s0, s1, s0n, s1n, noise, prediction_mode(prediction_type), act_dtype)
 
 
 class _GLoss(torch.autograd.Function):

@@ -1,6 +1,7 @@
 """SD glue with the reference's names and signatures (training/sid_sd_util.py):
     load_sd15        :51-118   -> (unet, vae, noise_scheduler, text_encoder, tokenizer)
-    sid_sd_sampler   :163-211  one-step (or few-step) generator  z -> x_hat (or decoded images)
+    sid_sd_sampler   :163-211  one-step (or few-step) generator  z -> x_hat (or decoded images); the N-step training
+                               sampler is hip_generate_steps (one sidlsg_step_renoise launch per step boundary)
     sid_sd_denoise   :214-274  add_noise -> (CFG-batched) UNet -> guided eps or x0 prediction
 
 `unet` must be a HipUNet2DCondition (bare or wrapped in DistributedDataParallel, as the reference's loop passes it):
@@ -233,6 +234,45 @@ def hip_generate(unet, z, ctx16, init_t, sched, x0=None):
     return ops.cfg_x0(eps, xt, s0, s1, 1.0, True, net.compute_dtype, prediction_type=sched.config.prediction_type)
 
 
+def step_timesteps(init_t, num_steps):
+    """t_i = (init_t * (1 - i/N)).long() for i < N: float arithmetic, then truncation (sid_sd_util.py:178)."""
+    return [(init_t * (1 - i / num_steps)).to(torch.long) for i in range(num_steps)]
+
+
+def hip_generate_steps(unet, z, eps_next, ctx16, init_t, sched):
+    """The N-step generator of the reference's training sampler (sid_sd_util.py:176-185), N = 1 + len(eps_next):
+    x_{t_0} = s1 z; for each step x_hat_i = x0 prediction of G(x_{t_i}, t_i); x_{t_{i+1}} = add_noise(x_hat_i, eps_next[i], t_{i+1}).
+    eps_next: [N-1, B, 4, h, w] fp32 (the eps_1 .. eps_{N-1} the caller drew), or None: one step = hip_generate, same launches.
+    Each step boundary is one sidlsg_step_renoise launch each way; the last x_hat comes from cfg_x0.
+    Only the step-0 forward of G places gradient-exchange markers (set_grad_ready_callback) and the mode-2 exchange: its backward
+    is the last one to add to G's weight gradients, so a segment is final only once step 0's backward has passed it."""
+    if eps_next is None or len(eps_next) == 0:
+        return hip_generate(unet, z, ctx16, init_t, sched)
+    net = _unwrap(unet)
+    if torch.is_grad_enabled() and net._train_params and ops.wgrad_stream_count() > 1:
+        raise RuntimeError('multi-step generator training with SIDLSG_WGRAD_STREAMS > 1: the N weight gradients of one layer would '
+                           'land on different weight-gradient streams unordered; use SIDLSG_WGRAD_STREAMS=1')
+    n = len(eps_next) + 1
+    pt, dt = sched.config.prediction_type, net.compute_dtype
+    ts = step_timesteps(init_t, n)
+    s0, s1 = sched.coefficients(ts[0])
+    xin, xt = ops.noisy_input(None, z, s0, s1, 1, dt)
+    cb = net._grad_ready_cb
+    try:
+        for i in range(n):
+            eps = net.forward_nhwc(xin, ts[i], ctx16)
+            if i == 0:
+                eps = _ddp_exchange(unet, eps)
+                net._grad_ready_cb = None
+            if i == n - 1:
+                return ops.cfg_x0(eps, xt, s0, s1, 1.0, True, dt, prediction_type=pt)
+            s0n, s1n = sched.coefficients(ts[i + 1])
+            xin, xt = ops.step_renoise(eps, xt, s0, s1, s0n, s1n, eps_next[i], dt, prediction_type=pt)
+            s0, s1 = s0n, s1n
+    finally:
+        net._grad_ready_cb = cb
+
+
 def hip_prepare_denoise(images, noise, t, cond16, uncond16, sched, guided, act_dtype=torch.bfloat16):
     """Shared by every network evaluated on the same (images, noise, t): the noisy CFG batch and its conditioning
     (`act_dtype` = the compute dtype of the networks that will consume it)."""
@@ -262,10 +302,16 @@ def sid_sd_sampler(unet, latents, contexts, init_timesteps, noise_scheduler, tex
     D_x = None
     ctxmgr = torch.enable_grad() if train_sampler else torch.no_grad()
     with ctxmgr:
-        for i in range(steps):
-            noise = latents if i == 0 else torch.randn_like(latents)
-            t_i = (init_timesteps * (1 - i / steps)).to(torch.long)
-            D_x = hip_generate(unet, noise.to(torch.float32).contiguous(), emb, t_i.contiguous(), noise_scheduler, x0=D_x)
+        if train_sampler and steps > 1:
+            # the eps_i the reference draws between its steps (randn_like, :179), drawn up front: the steps consume no RNG
+            eps_next = torch.stack([torch.randn_like(latents) for _ in range(steps - 1)]).to(torch.float32).contiguous()
+            D_x = hip_generate_steps(unet, latents.to(torch.float32).contiguous(), eps_next, emb, init_timesteps.contiguous(),
+                                     noise_scheduler)
+        else:
+            for i in range(steps):
+                noise = latents if i == 0 else torch.randn_like(latents)
+                t_i = (init_timesteps * (1 - i / steps)).to(torch.long)
+                D_x = hip_generate(unet, noise.to(torch.float32).contiguous(), emb, t_i.contiguous(), noise_scheduler, x0=D_x)
     if not return_images:
         return D_x.to(torch.float32)
     upcast = vae.dtype == torch.float16 and getattr(vae.config, 'force_upcast', False)

@@ -19,7 +19,7 @@ import os
 import torch
 
 from . import ops
-from .sd_util import check_prediction_type, hip_denoise, hip_generate, hip_prepare_denoise
+from .sd_util import check_prediction_type, hip_denoise, hip_generate_steps, hip_prepare_denoise
 
 
 class _SegmentedUpdate:
@@ -70,12 +70,16 @@ class _SegmentedUpdate:
 class SiDStep:
     def __init__(self, G, fake_score, true_score, G_ema, scheduler, opt_fake, opt_G, *, alpha=1.0, cfg_train_fake=1.0,
                  cfg_eval_fake=1.0, cfg_eval_real=1.0, loss_scaling=1.0, loss_scaling_G=1.0, batch_gpu_total=1,
-                 init_timestep=625, reducer=None, world_size=1):
+                 init_timestep=625, reducer=None, world_size=1, num_steps=1):
         self.G, self.psi, self.phi, self.G_ema = G, fake_score, true_score, G_ema
         self.sched, self.opt_fake, self.opt_G = scheduler, opt_fake, opt_G
         self.alpha, self.k1, self.k2, self.k4 = float(alpha), float(cfg_train_fake), float(cfg_eval_fake), float(cfg_eval_real)
         self.ls, self.lsg, self.bgt = float(loss_scaling), float(loss_scaling_G), int(batch_gpu_total)
         self.init_timestep = int(init_timestep)
+        # generator steps per sample (sid_sd_util.py:176-185): a round of an N-step run carries eps_next [N-1, B, 4, h, w]
+        self.num_steps = int(num_steps)
+        if self.num_steps < 1:
+            raise ValueError(f'num_steps={num_steps}: expected >= 1')
         self.reducer, self.world = reducer, world_size
         # gradients are exchanged when there is more than one rank -- or when the reducer was built to run its collectives
         # on a single rank too (FlatGradReducer(min_world=1): how the RCCL path is exercised on a one-GPU box)
@@ -146,13 +150,23 @@ class SiDStep:
     def _init_t(self, n, device):
         return torch.full((n,), self.init_timestep, device=device, dtype=torch.long)
 
+    def _generate(self, r):
+        """x_hat = G(z) through all generator steps (sid_sd_util.py:176-185): one step = hip_generate; N steps re-noise with r['eps_next'].
+        Only G's step-0 forward places exchange markers (hip_generate_steps)."""
+        eps_next = r.get('eps_next')
+        n = 1 if eps_next is None else 1 + len(eps_next)
+        if n != self.num_steps:
+            raise ValueError(f'a round with {n} generator step(s) for SiDStep(num_steps={self.num_steps}): '
+                             "eps_next must hold the num_steps - 1 noises [N-1, B, 4, h, w]")
+        return hip_generate_steps(self.G, r['z'], eps_next, r['cond'], self._init_t(len(r['z']), r['z'].device), self.sched)
+
     # ---- phase A: fake-score network -----------------------------------------------------------
     def fake_round(self, r):
         """r: dict(z, noise, t, cond, uncond) (fp32 NCHW / int64 / bf16 text states)."""
         # (fp8_forward: the e4m3 forward copies of a network converted with enable_fp8_weights(frozen_passes_only=True) --
         # BASELINE.json configs[4]; a no-op otherwise)
         with torch.no_grad(), self.G.fp8_forward():                                 # :406-411
-            images = hip_generate(self.G, r['z'], r['cond'], self._init_t(len(r['z']), r['z'].device), self.sched)
+            images = self._generate(r)
         prep = hip_prepare_denoise(images, r['noise'], r['t'], r['cond'], r.get('uncond'), self.sched, self.k1 != 1,
                                    act_dtype=self.psi.compute_dtype)
         eps = hip_denoise(self.psi, prep, self.k1, predict_x0=False)                # :418-421
@@ -177,10 +191,11 @@ class SiDStep:
             self.G.set_grad_ready_callback(lambda k: self.reducer.start_segment(self.G.flat_grads, segs[k]))
         cur = torch.cuda.current_stream()
         self.side.wait_stream(cur)
-        for t in (r['z'], r['cond']):
-            t.record_stream(self.side)
+        for t in (r['z'], r['cond'], r.get('eps_next')):
+            if t is not None:
+                t.record_stream(self.side)
         with torch.cuda.stream(self.side):
-            images = hip_generate(self.G, r['z'], r['cond'], self._init_t(len(r['z']), r['z'].device), self.sched)
+            images = self._generate(r)
             ev = torch.cuda.Event()
             ev.record()
         return images, ev
@@ -227,7 +242,7 @@ class SiDStep:
             cur.wait_event(ev)
             images.record_stream(cur)
         else:
-            images = hip_generate(self.G, r['z'], r['cond'], self._init_t(len(r['z']), r['z'].device), self.sched)  # :488-491
+            images = self._generate(r)                                             # :488-491
         guided = (self.k2 != 1) or (self.k4 != 1)
         prep = hip_prepare_denoise(images, r['noise'], r['t'], r['cond'], r.get('uncond'), self.sched, guided,
                                    act_dtype=self.psi.compute_dtype)

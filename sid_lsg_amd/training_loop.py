@@ -12,8 +12,10 @@ below is that stream; tests/test_host_logic.py pins it (prompt order, dropout fl
 generator) to the restatement that reproduces the reference's golden loss curves, and tests/test_gpu_unet.py runs this
 loop against tests/golden/loop_*.npz (curves produced by the UNMODIFIED reference training_loop).
 Not reproduced: preview PNG grids / FID metrics (cold path), torch.cuda.empty_cache +
-gc.collect every iteration (:384-385, a pure slowdown).  Rejected loudly rather than ignored: num_steps != 1 (the
-reference's own multi-step training sampler is marked unfinished, sid_sd_util.py:165).
+gc.collect every iteration (:384-385, a pure slowdown).  num_steps = N > 1 trains an N-step generator through the reference's
+multi-step training sampler (sid_sd_util.py:176-185, which the reference marks as work in progress): PromptStream draws its
+eps_1 .. eps_{N-1} in the reference's order of each phase and SiDStep generates through sd_util.hip_generate_steps.  The metrics
+evaluated during training keep using one generation step, as the reference's do (:631).
 """
 import copy
 import contextlib
@@ -62,12 +64,15 @@ class PromptStream:
     472-484).  `rng_device` is where z / noise / t are drawn: the training device in production (as the reference
     does, device=device at :398-399, 413), 'cpu' when a run has to reproduce a CPU-generated reference curve."""
 
-    def __init__(self, dataset_obj, *, seed, rank, world, batch_gpu, lat, tmin, tmax, device, rng_device=None):
+    def __init__(self, dataset_obj, *, seed, rank, world, batch_gpu, lat, tmin, tmax, device, rng_device=None, num_steps=1):
+        if int(num_steps) < 1:
+            raise ValueError(f'num_steps={num_steps}: expected >= 1')
         np.random.seed((seed * world + rank) % (1 << 31))                                   # :238
         torch.manual_seed(np.random.randint(1 << 31))                                       # :239
         self.device = torch.device(device)
         self.rng_device = torch.device(rng_device) if rng_device is not None else self.device
         self.lat, self.tmin, self.tmax = lat, tmin, tmax
+        self.num_steps = int(num_steps)
         sampler = InfiniteSampler(dataset_obj, rank=rank, num_replicas=world, seed=seed)    # :274
         # :275 iter(DataLoader(...)) draws the iterator's base seed from the default CPU generator: part of the stream
         # the dropout flags below come from
@@ -77,15 +82,28 @@ class PromptStream:
     def next_prompts(self):
         return next(self.prompts_it)
 
-    def round(self, dropout):
+    def round(self, dropout, phase='A'):
+        """-> (prompts, z, noise, t); with num_steps N > 1 also eps_next [N-1, B, 4, lat, lat]: the eps_1 .. eps_{N-1} the reference's
+        multi-step training sampler draws with randn_like (sid_sd_util.py:179).  Where: phase 'A' (fake-score round) between noise
+        and t -- the sampler runs at :406-411, t is drawn at :413 --, phase 'B' (generator round) after t (:484, sampler at :488)."""
+        if phase not in ('A', 'B'):
+            raise ValueError(f"phase {phase!r}: expected 'A' or 'B'")
         prompts = self.next_prompts()
         if dropout:
             flags = (torch.rand(len(prompts)) < 0.1).tolist()                               # :394 (CPU generator)
             prompts = ['' if f else p for f, p in zip(flags, prompts)]
         z = torch.randn([len(prompts), 4, self.lat, self.lat], device=self.rng_device, dtype=torch.float32)   # :398 / :479
         noise = torch.randn_like(z)                                                         # :399 / :480
+
+        def eps_next():
+            return torch.stack([torch.randn_like(z) for _ in range(self.num_steps - 1)])
+
+        eps = eps_next() if self.num_steps > 1 and phase == 'A' else None                  # :406-411
         t = torch.randint(self.tmin, self.tmax, (len(prompts),), device=self.rng_device, dtype=torch.long)    # :413 / :484
-        return prompts, z.to(self.device), noise.to(self.device), t.to(self.device)
+        if self.num_steps > 1 and phase == 'B':
+            eps = eps_next()                                                                # :488-491
+        out = (prompts, z.to(self.device), noise.to(self.device), t.to(self.device))
+        return out if eps is None else out + (eps.to(self.device),)
 
 
 SNAPSHOT_EXTRA_TICKS = (2, 4, 10, 20, 30, 40, 50, 60, 70, 80, 90, 100)
@@ -109,9 +127,9 @@ def training_loop(
                                 pretrained_model_name_or_path=pretrained_model_name_or_path, network_pkl=network_pkl, resolution=resolution,
                                 num_steps=num_steps, metric_real_stats=metric_real_stats, metric_num_test=metric_num_test,
                                 dataset_prompt_text_kwargs=dataset_prompt_text_kwargs)
-    if num_steps != 1:
-        raise NotImplementedError(f'num_steps={num_steps}: only the one-step generator is trained (the reference marks its '
-                                  'multi-step training sampler as unfinished, sid_sd_util.py:165)')
+    num_steps = int(num_steps)
+    if num_steps < 1:
+        raise ValueError(f'num_steps={num_steps}: expected >= 1')
     rank, world = dist.get_rank(), dist.get_world_size()
     if deterministic:       # bit-reproducible step for this process (else the default policy: SIDLSG_DETERMINISTIC, the torch flag)
         ops.set_deterministic(True)
@@ -147,7 +165,7 @@ def training_loop(
     lat = resolution // (2 ** (len(vae.config.block_out_channels) - 1))
 
     stream = PromptStream(dataset_obj, seed=seed, rank=rank, world=world, batch_gpu=batch_gpu, lat=lat, tmin=tmin, tmax=tmax,
-                          device=device, rng_device=rng_device)
+                          device=device, rng_device=rng_device, num_steps=num_steps)
     dist.print0('Example text prompts used for distillation:')
     for i in range(16):
         dist.print0(i, stream.next_prompts())
@@ -200,11 +218,14 @@ def training_loop(
     step = SiDStep(G, fake_score, true_score, G_ema, noise_scheduler, opt_f, opt_g, alpha=alpha, cfg_train_fake=cfg_train_fake,
                    cfg_eval_fake=cfg_eval_fake, cfg_eval_real=cfg_eval_real, loss_scaling=loss_scaling, loss_scaling_G=loss_scaling_G,
                    batch_gpu_total=batch_gpu_total, init_timestep=init_timestep, reducer=FlatGradReducer() if world > 1 else None,
-                   world_size=world)
+                   world_size=world, num_steps=num_steps)
 
-    def make_round(dropout):
-        prompts, z, noise, t = stream.round(dropout)
-        return dict(z=z, noise=noise, t=t, cond=cond.encode(prompts), uncond=cond.uncond(len(prompts)))
+    def make_round(dropout, phase):
+        prompts, z, noise, t, *eps = stream.round(dropout, phase)
+        r = dict(z=z, noise=noise, t=t, cond=cond.encode(prompts), uncond=cond.uncond(len(prompts)))
+        if eps:             # num_steps > 1: eps_1 .. eps_{N-1} of the multi-step generator, one stacked tensor
+            r['eps_next'] = eps[0]
+        return r
 
     dist.print0(f'Training for {total_kimg} kimg...')
     stats = Stats()
@@ -221,9 +242,10 @@ def training_loop(
 
     def build_inputs():
         with torch.cuda.stream(prep_stream) if prep_stream is not None else contextlib.nullcontext():
-            # RNG order of the reference: all phase-A draws, then all phase-B draws (the compute in between consumes no RNG)
-            inputs = dict(A=[make_round(use_dropout) for _ in range(rounds)])
-            inputs['B'] = [make_round(False) for _ in range(rounds)]
+            # RNG order of the reference: all phase-A draws, then all phase-B draws.  The compute in between consumes no RNG except the
+            # multi-step sampler's eps_i (num_steps > 1), which PromptStream.round draws at the sampler's place in each phase.
+            inputs = dict(A=[make_round(use_dropout, 'A') for _ in range(rounds)])
+            inputs['B'] = [make_round(False, 'B') for _ in range(rounds)]
             ev = None
             if prep_stream is not None:
                 ev = torch.cuda.Event()

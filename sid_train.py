@@ -88,7 +88,7 @@ OPTIONS = [
     (('--enable_xformers',), dict(type=bool, default=True, show_default=True, help='Accepted for compatibility (attention is the fused HIP kernel)')),
     (('--gradient_checkpointing',), dict(type=bool, default=False, show_default=True, help='Accepted for compatibility')),
     (('--optimizer',), dict(type=click.Choice(['adam', 'adamw']), default='adam', show_default=True, help='Optimizer')),
-    (('--num_steps',), dict(type=int, default=1, show_default=True, help='Number of generation steps')),
+    (('--num_steps',), dict(type=click.IntRange(min=1), default=1, show_default=True, help='Number of generation steps of the trained generator')),
     (('--fake_score_use_lora',), dict(type=bool, default=False, show_default=True, help='Unsupported (must be False)')),
 ]
 
