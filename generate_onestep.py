@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from sid_lsg_amd import distributed as dist
+from sid_lsg_amd.preview import save_png
 from sid_lsg_amd.sd_util import check_prediction_type, load_sd15, sid_sd_sampler
 
 
@@ -48,23 +49,6 @@ def parse_int_list(s):
 def read_prompts(path):
     with open(path, 'rt') as f:
         return [line.strip() for line in f if line.strip()]
-
-
-def save_png(path, hwc_uint8):
-    try:
-        import PIL.Image
-        PIL.Image.fromarray(hwc_uint8, 'RGB').save(path)
-    except ImportError:                    # no Pillow: minimal PNG writer (zlib + CRC), enough for RGB8
-        import struct
-        import zlib
-        h, w, _ = hwc_uint8.shape
-        raw = b''.join(b'\x00' + hwc_uint8[y].tobytes() for y in range(h))
-
-        def chunk(tag, data):
-            return struct.pack('>I', len(data)) + tag + data + struct.pack('>I', zlib.crc32(tag + data) & 0xFFFFFFFF)
-        with open(path, 'wb') as f:
-            f.write(b'\x89PNG\r\n\x1a\n' + chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, 8, 2, 0, 0, 0)) +
-                    chunk(b'IDAT', zlib.compress(raw, 6)) + chunk(b'IEND', b''))
 
 
 @click.command()

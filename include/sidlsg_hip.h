@@ -303,6 +303,17 @@ int sidlsg_transpose_w16_batched(const void* jobs, int njobs, int nblocks, void*
  * sorted by blk0 = index of the job's first block of 2048 elements; nblocks = total. */
 int sidlsg_scale_cast_ranges(const void* jobs, int njobs, int nblocks, void* stream);
 
+/* ---- snapshot preview grids (save_image_grid, sid_training_loop.py:99-115, 597-614) -------------------------------------
+ * B decoded fp32 images -> their tiles of ONE uint8 grid image [gh*H][gw*W][3] (HWC, what a PNG writer takes): image i goes to
+ * tile first + i, row (first + i) / gw, column (first + i) % gw, so the batches of a grid are placed as they leave the decoder and
+ * the fp32 images are never concatenated, permuted or copied to the host.  layout 0: src [B][H][W][8] (NHWC, channels 3..7 are
+ * padding: the VAE decoder's native output); layout 1: src [B][3][H][W].  In fp32, exactly: v = (x - lo) * scale (two roundings,
+ * scale = 255 / (hi - lo) formed in double on the host and rounded once: 127.5 for [-1, 1], 1 for [0, 255]), round to nearest
+ * even, clamp to [0, 255]; NaN -> 0 (numpy leaves that cast undefined).  W % 4 == 0, src 16-byte aligned.  SIDLSG_EINVAL, and no
+ * launch, for first + B > gw*gh, hi == lo, null pointers or a grid of 2 GiB or more. */
+int sidlsg_image_grid_u8(const float* src, void* grid, int B, int H, int W, int layout, int first, int gw, int gh, float lo, float hi,
+                         void* stream);
+
 /* ---- reference plugin op: torch_utils/ops/bias_act.cpp:32 `bias_act(x,b,xref,yref,dy,grad,dim,act,alpha,gain,clamp)`
  * act: 1 linear 2 relu 3 lrelu 4 tanh 5 sigmoid 6 elu 7 selu 8 softplus 9 swish (bias_act.py:23-33).
  * grad 0: out = clamp(act(x + b[(i/stepB)%sizeB]) * gain); grad 1: out = dL/dx from dy (x, b = saved inputs).

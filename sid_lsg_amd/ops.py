@@ -1842,6 +1842,29 @@ def cast_bf16(src_f32, out=None):
     return out
 
 
+def image_grid_u8(images, grid, first, gw, drange=(-1, 1), layout='nchw'):
+    """Place decoded fp32 images into their tiles of the uint8 preview grid `grid` [gh*H, gw*W, 3] (sidlsg_image_grid_u8): image i
+    goes to tile first + i (row-major, gw tiles per row).  layout 'nhwc8': images [B, H, W, 8], channels 3..7 padding (the VAE
+    decoder's native output); 'nchw': [B, 3, H, W] (sid_sd_sampler(return_images=True)).  uint8 = clip(rint((x - lo) * 255 / (hi - lo)))
+    in fp32 with numpy's roundings (save_image_grid, sid_training_loop.py:99-103)."""
+    if layout == 'nhwc8':
+        B, H, W, C = images.shape
+        ok = C == 8
+    elif layout == 'nchw':
+        B, C, H, W = images.shape
+        ok = C == 3
+    else:
+        raise ValueError(f"image_grid_u8: layout {layout!r}: expected 'nhwc8' or 'nchw'")
+    if not ok:
+        raise RuntimeError(f'image_grid_u8: images {tuple(images.shape)} are not {layout}')
+    if grid.dim() != 3 or grid.shape[2] != 3 or grid.shape[1] != gw * W or grid.shape[0] % H:
+        raise RuntimeError(f'image_grid_u8: grid {tuple(grid.shape)} is not [gh*{H}, {gw}*{W}, 3]')
+    lo, hi = drange
+    lib.sidlsg_image_grid_u8(_p(_chk(images, F32)), _p(_chk(grid, torch.uint8)), B, H, W, 1 if layout == 'nchw' else 0, int(first), int(gw),
+                             grid.shape[0] // H, float(lo), float(hi), _s())
+    return grid
+
+
 def _det_synced(backward):
     @functools.wraps(backward)
     def wrapper(*args):

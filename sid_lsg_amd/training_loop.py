@@ -11,8 +11,12 @@ CPU generator; z, noise, t on `device`), EMA beta schedule (:553-558), `cur_nimg
 below is that stream; tests/test_host_logic.py pins it (prompt order, dropout flags, z / noise / t on the CPU
 generator) to the restatement that reproduces the reference's golden loss curves, and tests/test_gpu_unet.py runs this
 loop against tests/golden/loop_*.npz (curves produced by the UNMODIFIED reference training_loop).
-Not reproduced: preview PNG grids / FID metrics (cold path), torch.cuda.empty_cache +
-gc.collect every iteration (:384-385, a pure slowdown).  num_steps = N > 1 trains an N-step generator through the reference's
+snapshot_images=True (off by default; rank 0 only) writes the reference's preview grids through sid_lsg_amd.preview: `fakes_init.png`
+on a fresh start and `fakes_<alpha>_<kimg>_<n>.png` for n = 1, 2, 4 generation steps next to every network snapshot, from G_ema
+(:258-271, 347-364, 597-616); their time is maintenance time, not `Timing/sec_per_kimg`, and the training RNG stream does not see
+them.  `reals.png` is not written: the datasets here yield captions, not pixels (an image loader is a feature of its own).
+Not reproduced: torch.cuda.empty_cache + gc.collect every iteration (:384-385, a pure slowdown).
+num_steps = N > 1 trains an N-step generator through the reference's
 multi-step training sampler (sid_sd_util.py:176-185, which the reference marks as work in progress): PromptStream draws its
 eps_1 .. eps_{N-1} in the reference's order of each phase and SiDStep generates through sd_util.hip_generate_steps.  The metrics
 evaluated during training keep using one generation step, as the reference's do (:631).
@@ -119,14 +123,15 @@ def training_loop(
     pretrained_vae_model_name_or_path='runwayml/stable-diffusion-v1-5', fake_score_use_lora=False,
     dataset_prompt_text_kwargs={}, cfg_train_fake=1, cfg_eval_fake=1, cfg_eval_real=1, num_steps=1, train_mode=True,
     network_pkl=None, enable_xformers=True, gradient_checkpointing=False, resolution=512, on_iteration=None,
-    rng_device=None, metric_real_stats=None, metric_num_test=None, deterministic=False,
+    rng_device=None, metric_real_stats=None, metric_num_test=None, deterministic=False, snapshot_images=False,
 ):
     if not train_mode:
         return evaluate_network(run_dir=run_dir, dataset_kwargs=dataset_kwargs, network_kwargs=network_kwargs, device=device, metrics=metrics,
                                 init_timestep=init_timestep, metric_pt_path=metric_pt_path, metric_open_clip_path=metric_open_clip_path,
                                 pretrained_model_name_or_path=pretrained_model_name_or_path, network_pkl=network_pkl, resolution=resolution,
                                 num_steps=num_steps, metric_real_stats=metric_real_stats, metric_num_test=metric_num_test,
-                                dataset_prompt_text_kwargs=dataset_prompt_text_kwargs)
+                                dataset_prompt_text_kwargs=dataset_prompt_text_kwargs, snapshot_images=snapshot_images,
+                                batch_size=batch_size, batch_gpu=batch_gpu)
     num_steps = int(num_steps)
     if num_steps < 1:
         raise ValueError(f'num_steps={num_steps}: expected >= 1')
@@ -227,6 +232,27 @@ def training_loop(
             r['eps_next'] = eps[0]
         return r
 
+    write_previews = None
+    if snapshot_images and rank == 0 and run_dir:
+        # the grid's prompts: the caption set of dataset_kwargs when given, else the training prompts (:198-200, 265); no collective
+        # inside, so the other ranks simply skip it
+        from . import preview
+        grid = preview.setup_snapshot_grid(construct_class_by_name(**dataset_kwargs) if dataset_kwargs else dataset_obj, resolution,
+                                           batch_gpu, (4, lat, lat), device)
+
+        def write_previews(name_format, step_counts=preview.STEP_COUNTS):
+            if G_ema is not G:      # the fused Adam + EMA kernel writes G_ema's masters only: bring its forward copies up to date
+                G_ema.refresh_compute_weights()
+            preview.write_grids(run_dir, name_format, G_ema, grid, step_counts, noise_scheduler=noise_scheduler,
+                                text_encoder=text_encoder, tokenizer=tokenizer, vae=vae, init_timestep=init_timestep,
+                                resolution=resolution, num_steps=num_steps)
+        if resume_training is None:
+            dist.print0('Text prompts for example images:')
+            for c in grid.c:
+                dist.print0(c)
+            dist.print0('Exporting sample fake images at initialization...')
+            write_previews('fakes_init.png', (1,))
+
     dist.print0(f'Training for {total_kimg} kimg...')
     stats = Stats()
     cur_nimg, cur_tick = resume_kimg * 1000, 0
@@ -308,6 +334,8 @@ def training_loop(
         if snapshot_ticks is not None and (done or cur_tick % snapshot_ticks == 0 or cur_tick in SNAPSHOT_EXTRA_TICKS) and rank == 0 and run_dir:
             with open(os.path.join(run_dir, f'network-snapshot-{alpha:03f}-{cur_nimg // 1000:06d}.pkl'), 'wb') as f:
                 pickle.dump(dict(ema=G_ema), f)
+            if write_previews is not None:
+                write_previews(f'fakes_{alpha:03f}_{cur_nimg // 1000:06d}_{{n}}.png')
         # metrics at the snapshot cadence, from tick 1 on (sid_training_loop.py:616-639, `if cur_tick>0`): the EMA generator
         # through the one-step sampler + VAE
         if metrics and cur_tick > 0 and snapshot_ticks is not None and (done or cur_tick % snapshot_ticks == 0 or cur_tick in SNAPSHOT_EXTRA_TICKS):
@@ -358,11 +386,12 @@ def training_loop(
 
 def evaluate_network(run_dir, dataset_kwargs, network_kwargs, device, metrics, init_timestep, metric_pt_path, metric_open_clip_path,
                      pretrained_model_name_or_path, network_pkl, resolution, num_steps=1, metric_real_stats=None, metric_num_test=None,
-                     dataset_prompt_text_kwargs=None):
+                     dataset_prompt_text_kwargs=None, snapshot_images=False, batch_size=512, batch_gpu=None):
     """`--train_mode 0` (sid_training_loop.py:680-745): load the text encoder / VAE / scheduler, un-pickle the distilled generator
     from `network_pkl` (`pickle.load(f)['ema']`, the file the training loop writes at the snapshot ticks) and evaluate every metric
     with 1, 2 and 4 generation steps; each result goes to `<dirname(run_dir)>/<metric><number>_<steps>.txt` in the reference's
-    `key: value` format.  The preview PNG grids of that branch are not produced (cold path, like the training loop's)."""
+    `key: value` format.  snapshot_images=True also writes that branch's preview grid `<run_dir>/<metric><number>_<steps>.png` per metric
+    and step count on rank 0 (:704-733, sid_lsg_amd.preview); the metric values do not depend on it."""
     import re
     from functools import partial
 
@@ -391,12 +420,25 @@ def evaluate_network(run_dir, dataset_kwargs, network_kwargs, device, metrics, i
                              '(--data_prompt_text) was given -- there are no prompts to evaluate on')
         dist.print0('WARNING: no dataset_kwargs (--data): evaluating on the training prompts; not comparable with the reference\'s COCO numbers')
         msrc = dict(dataset_kwargs=dict(dataset_prompt_text_kwargs))
+    grid = None
+    if snapshot_images and dist.get_rank() == 0 and run_dir:
+        from . import preview
+        lat = resolution // (2 ** (len(vae.config.block_out_channels) - 1))
+        grid = preview.setup_snapshot_grid(construct_class_by_name(**msrc['dataset_kwargs']), resolution,
+                                           batch_gpu or max(batch_size // dist.get_world_size(), 1), (4, lat, lat), device)
+        for c in grid.c:
+            dist.print0(c)
+        os.makedirs(run_dir, exist_ok=True)
     out = {}
     for num_steps_eval in (1, 2, 4):
         for metric in metrics:
             G_eval = partial(sid_sd_sampler, unet=G_ema, noise_scheduler=noise_scheduler, text_encoder=text_encoder, tokenizer=tokenizer,
                              resolution=resolution, dtype=torch.float32, return_images=True, vae=vae, num_steps=num_steps, train_sampler=False,
                              num_steps_eval=num_steps_eval)
+            if grid is not None:
+                preview.write_grids(run_dir, f'{metric}{number_part}_{{n}}.png', G_ema, grid, (num_steps_eval,),
+                                    noise_scheduler=noise_scheduler, text_encoder=text_encoder, tokenizer=tokenizer, vae=vae,
+                                    init_timestep=init_timestep, resolution=resolution, num_steps=num_steps)
             extra = dict(num_test=metric_num_test) if metric_num_test is not None else {}
             result = metric_main.calc_metric(metric, G=G_eval, resolution=resolution, init_timestep=init_timestep, detector=metric_pt_path,
                                              real_stats=metric_real_stats, open_clip_detector=metric_open_clip_path, device=device, **msrc, **extra)

@@ -201,9 +201,7 @@ class HipAutoencoderKLDecoder(nn.Module):
                 m.prepare()
         self._ready = True
 
-    @torch.no_grad()
-    def decode(self, z, return_dict=False):
-        """z: [B, 4, h, w] (already divided by scaling_factor by the caller) -> images [B, 3, 8h, 8w] fp32 in ~[-1, 1]."""
+    def _decode_nhwc(self, z):
         if z.device.type != 'cuda':
             raise RuntimeError('HipAutoencoderKLDecoder runs on the MI355X only (no CPU fallback)')
         if not self._ready:
@@ -212,8 +210,19 @@ class HipAutoencoderKLDecoder(nn.Module):
         B, C, h, w = z.shape
         x = torch.zeros((B, h, w, _pad8(C)), device=z.device, dtype=BF16)
         x[..., :C] = z.permute(0, 2, 3, 1).to(BF16)
-        y = self.decoder(x)                                               # [B, 8h, 8w, 8] fp32, channels 3..7 are padding
+        return self.decoder(x)                                            # [B, 8h, 8w, 8] fp32, channels 3..7 are padding
+
+    @torch.no_grad()
+    def decode(self, z, return_dict=False):
+        """z: [B, 4, h, w] (already divided by scaling_factor by the caller) -> images [B, 3, 8h, 8w] fp32 in ~[-1, 1]."""
+        y = self._decode_nhwc(z)
         img = y[..., :self.config.out_channels].permute(0, 3, 1, 2).contiguous()
         if return_dict:
             return SimpleNamespace(sample=img)
         return (img,)
+
+    @torch.no_grad()
+    def decode_to_grid(self, z, grid, first, gw, drange=(-1, 1)):
+        """decode(z) written as uint8 into tiles first .. first + B - 1 of the preview grid `grid` [gh*8h, gw*8w, 3] (ops.image_grid_u8):
+        the decoder's NHWC output goes to the grid kernel as it is, no fp32 NCHW image is formed."""
+        return ops.image_grid_u8(self._decode_nhwc(z), grid, first, gw, drange, layout='nhwc8')

@@ -14,6 +14,8 @@ Differences (documented, not silent):
     `--precision fp32` -- the fp32-accurate mode (the reference's own default precision, ~20x slower);
   * `--deterministic 1` (added option) makes the training step bit-reproducible: same tree, GPU model, configuration and
     world size give the same bits (sid_lsg_amd.ops.set_deterministic);
+  * `--snapshot_images 1` (added option) writes the preview grids `fakes_init.png` and `fakes_<alpha>_<kimg>_{1,2,4}.png` next to the
+    snapshots, and `<metric><kimg>_<steps>.png` with `--train_mode 0` (sid_lsg_amd/preview.py); the reference always writes them;
   * `--metrics` run through sid_lsg_amd/metrics.py at the snapshot ticks and need LOCAL detector / statistics files
     (--metric_pt_path, --data_stat); `--train_mode 0 --network_pkl <snapshot>` evaluates a snapshot (1 / 2 / 4 steps);
   * `--data` is optional (it is the COCO image set used only by the metrics).
@@ -69,6 +71,7 @@ OPTIONS = [
     (('--fp16',), dict(type=bool, default=False, show_default=True, metavar='BOOL', help='Reference fp16 recipe (optimizer eps 1e-6)')),
     (('--precision',), dict(type=click.Choice(['bf16', 'fp32']), default='bf16', show_default=True, help='Compute dtype of the HIP path (not a reference option)')),
     (('--deterministic',), dict(type=bool, default=False, show_default=True, metavar='BOOL', help='Bit-reproducible training step: order-fixed gradient reductions (not a reference option)')),
+    (('--snapshot_images',), dict(type=bool, default=False, show_default=True, metavar='BOOL', help='Write the preview grids fakes_init.png and fakes_<alpha>_<kimg>_{1,2,4}.png at the snapshot ticks; the reference does this whenever --metrics is set (not a reference option)')),
     (('--teacher-weights', 'teacher_weights'), dict(type=click.Choice(['bf16', 'fp8', 'fp8-frozen']), default='bf16', show_default=True, help='fp8: frozen teacher forward weights as e4m3 + per-channel scales; fp8-frozen: every pass without weight gradients (not a reference option)')),
     (('--ls',), dict(type=click.FloatRange(min=0, min_open=True), default=1, show_default=True, help='Loss scaling')),
     (('--lsg',), dict(type=click.FloatRange(min=0, min_open=True), default=1, show_default=True, help='Loss scaling G')),
@@ -142,6 +145,8 @@ def build_config(o):
     c.network_kwargs = EasyDict(use_fp16=o.fp16, compute_dtype=o.get('precision', 'bf16'), teacher_weights=o.get('teacher_weights', 'bf16'))
     c.loss_kwargs = EasyDict()
     c.deterministic = bool(o.get('deterministic', False))
+    if o.get('snapshot_images', False):      # (absent when off: the printed options of a run without it stay as they were)
+        c.snapshot_images = True
     c.init_timestep = o.init_timestep
     c.total_kimg = max(int(o.duration * 1000), 1)
     c.ema_halflife_kimg = int(o.ema * 1000)
