@@ -303,6 +303,21 @@ int sidlsg_transpose_w16_batched(const void* jobs, int njobs, int nblocks, void*
  * sorted by blk0 = index of the job's first block of 2048 elements; nblocks = total. */
 int sidlsg_scale_cast_ranges(const void* jobs, int njobs, int nblocks, void* stream);
 
+/* ---- precision / recall (metrics/sid_precision_recall.py): fp16 feature distances on the MFMA, reduced in registers ----------
+ * Feature matrices are [n][F] fp16 row-major, F a positive multiple of 32 (pad with zero columns on the host), 16-byte aligned.
+ * In all three, exactly:  d2(i, j) = max(|a_i|^2 + |b_j|^2 - 2 a_i . b_j, 0)  with a . b on v_mfma_f32_16x16x32_f16 (fp32
+ * accumulate) and the norms in fp32;  d(i, j) = fp16_rne(sqrt(d2)).  The three share one tile routine, so a distance has the same
+ * bits whichever entry forms it.
+ * sidlsg_pr_distances: out[R][C] fp16 = d(rows_i, cols_j), the dense form (compute_distances, :19-32).
+ * sidlsg_pr_kth_radius: radius_out[N] fp16 = the (k+1)-th smallest d over ALL N columns of the set against itself, the row
+ *   itself included and equal values counted as often as they occur (`dist.kthvalue(nhood_size + 1)`, :59); 0 <= k <= 7,
+ *   N >= k + 1.  No [N][N] buffer.
+ * sidlsg_pr_member: inside_out[P] bytes, 1 where some column j has d(probe_i, manifold_j) <= radius[j] (:64), else 0.
+ * SIDLSG_EINVAL, and no launch, for null or misaligned pointers, F % 32 != 0, k > 7 or N < k + 1. */
+int sidlsg_pr_distances(const void* rows, int R, const void* cols, int C, int F, void* out, void* stream);
+int sidlsg_pr_kth_radius(const void* manifold, int N, int F, int k, void* radius_out, void* stream);
+int sidlsg_pr_member(const void* probes, int P, const void* manifold, int N, int F, const void* radius, void* inside_out, void* stream);
+
 /* ---- snapshot preview grids (save_image_grid, sid_training_loop.py:99-115, 597-614) -------------------------------------
  * B decoded fp32 images -> their tiles of ONE uint8 grid image [gh*H][gw*W][3] (HWC, what a PNG writer takes): image i goes to
  * tile first + i, row (first + i) / gw, column (first + i) % gw, so the batches of a grid are placed as they leave the decoder and

@@ -7,6 +7,8 @@
     set of `--data`, read only by the metrics: metrics/sid_metric_utils.py:419-421 draws the evaluation prompts from it through
     `InfiniteSampler(seed=0)`): every image file that has a same-named `.txt` next to it, in the reference's sorted recursive
     order; the pixels are never decoded here (the generator metrics only use the text).
+  * `ImageCaptionDataset`: the same walk WITH the pixels (training/mscoco_dataset.py:46-68): `(uint8 [3, H, W], caption)`, what the
+    real-set statistics, precision / recall and `reals.png` read.  PIL only; no resize or crop (the reference's are commented out).
   * `InfiniteSampler`: rank-strided, windowed-shuffle index stream with the semantics of
     torch_utils/misc.py:110-141 (it defines which prompt each rank sees at each step); pinned against the
     reference by tests/golden/sampler.npz.
@@ -60,7 +62,8 @@ class CaptionDataset(torch.utils.data.Dataset):
             raise IOError(f'no captions under {path}')
 
     @classmethod
-    def _caption_files(cls, path):
+    def _caption_files(cls, path, with_images=False):
+        """The caption file of every captioned image under `path`, or (with_images) the (image, caption file) pairs."""
         out = []
         for entry in sorted(os.listdir(path)):
             full = os.path.join(path, entry)
@@ -68,9 +71,9 @@ class CaptionDataset(torch.utils.data.Dataset):
             if parts[-1].strip().lower() in cls.IMAGE_EXT and len(parts) > 1:
                 txt = os.path.join(path, parts[0] + '.txt')
                 if os.path.exists(txt):
-                    out.append(txt)
+                    out.append((full, txt) if with_images else txt)
             elif os.path.isdir(full):
-                out.extend(cls._caption_files(full))
+                out.extend(cls._caption_files(full, with_images))
         return out
 
     def __len__(self):
@@ -78,6 +81,43 @@ class CaptionDataset(torch.utils.data.Dataset):
 
     def __getitem__(self, idx):
         return torch.zeros(1, 4, 4), self.captions[idx]
+
+
+class ImageCaptionDataset(CaptionDataset):
+    """(uint8 [3, H, W] image, caption) items of an image + caption directory, in CaptionDataset's order
+    (training/mscoco_dataset.py:27-68): the file through PIL, `convert('RGB')`, an x-flip with probability `random_flip`, the
+    stored pixels as they are."""
+    has_images = True
+
+    def __init__(self, path, resolution=512, random_crop=False, random_flip=0.0):
+        self.name, self.resolution, self.random_flip = 'MSCOCO-2014', resolution, random_flip
+        if not os.path.isdir(path):
+            raise IOError(f'{path} is not an image directory')
+        self.files = self._caption_files(path, with_images=True)
+        if not self.files:
+            raise IOError(f'no captioned images under {path}')
+
+    def __len__(self):
+        return len(self.files)
+
+    def caption(self, idx):
+        with open(self.files[idx][1], 'rt') as f:
+            return f.read().strip()
+
+    def __getitem__(self, idx):
+        import random
+
+        import PIL.Image
+        with PIL.Image.open(self.files[idx][0]) as im:
+            arr = np.array(im.convert('RGB'))
+        if random.random() < self.random_flip:
+            arr = arr[:, ::-1]
+        return torch.from_numpy(np.ascontiguousarray(np.transpose(arr, [2, 0, 1]))), self.caption(idx)
+
+
+def has_image_files(path):
+    """`path` is a directory that holds at least one captioned image (what ImageCaptionDataset reads)."""
+    return bool(path) and os.path.isdir(path) and bool(CaptionDataset._caption_files(path))
 
 
 class InfiniteSampler:

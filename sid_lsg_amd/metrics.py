@@ -1,4 +1,4 @@
-"""Evaluation metrics of the distilled generator: FID and CLIP scores.
+"""Evaluation metrics of the distilled generator: FID, CLIP scores and precision / recall.
 
 Reference: metrics/sid_metric_main.py:25-123 (registry, `calc_metric`, `report_metric`, the `fid30k_full` /
 `fid_clip_30k_full` / `fid_test` / `fid_clip_test` entries), metrics/sid_fid_and_clip.py:32-74 (the Frechet distance between
@@ -17,8 +17,14 @@ What is different here (not a translation):
     kernels); the feature detectors are PLUGGABLE callables -- the reference downloads a TorchScript Inception-v3
     (`inception-2015-12-05.pt`) and pickled open_clip models, neither of which exists offline.  `load_detector(path)`
     accepts exactly those files (torch.jit / pickle) when a deployment has them; the real-set statistics come from a cached
-    `.npz` (`mu`, `sigma`) or are computed from an image iterator with the same detector.
-Nothing here is on the hot path.
+    `.npz` (`mu`, `sigma`) or are computed from the image set of `--data` with the same detector (`dataset_feature_stats`,
+    metrics/sid_metric_utils.py:266-280) and cached as `<run_dir>/real_stats.npz`;
+  * precision / recall (metrics/sid_precision_recall.py, Kynkaanniemi et al.; the SAME Inception detector as FID) keeps every
+    feature vector on the device and runs on the `sidlsg_pr_*` kernels: the k-th neighbour radius and the membership test are
+    reductions inside the fp16 MFMA distance contraction, so no N x N matrix is formed, let alone copied to the host as the
+    reference does.  The distance is computed to fp32 accuracy and rounded to fp16 once; the reference's fp16 `cdist` is not
+    correctly rounded, so single distances differ by an fp16 ulp (tests/test_gpu_pr.py pins what follows from that).
+Only the precision / recall kernels are hot; the rest is host logic.
 """
 import json
 import os
@@ -36,8 +42,9 @@ from .dnnlib_util import EasyDict
 class FeatureStats:
     """Running mean / covariance of feature vectors (metrics/sid_metric_utils.py:112-188), accumulated in fp64 on `device`."""
 
-    def __init__(self, capture_all=False, capture_mean_cov=False, max_items=None, device=None):
+    def __init__(self, capture_all=False, capture_mean_cov=False, max_items=None, device=None, keep_on_device=False):
         self.capture_all, self.capture_mean_cov, self.max_items = capture_all, capture_mean_cov, max_items
+        self.keep_on_device = keep_on_device        # capture_all: the features stay where they were computed (precision / recall)
         self.device = torch.device(device) if device is not None else None
         self.num_items, self.num_features = 0, None
         self.all_features, self.raw_mean, self.raw_cov = None, None, None
@@ -66,7 +73,7 @@ class FeatureStats:
         self.num_items += x.shape[0]
         x = x.to(self.device, torch.float32)          # the reference rounds features to fp32 before accumulating in fp64
         if self.capture_all:
-            self.all_features.append(x.cpu())
+            self.all_features.append(x if self.keep_on_device else x.cpu())
         if self.capture_mean_cov:
             x64 = x.to(torch.float64)
             self.raw_mean += x64.sum(0)
@@ -76,18 +83,35 @@ class FeatureStats:
 
     def merge_ranks(self, group=None):
         """Sum the accumulators over the ranks of the process group (each rank appended its own shard of the samples)."""
-        if dist.get_world_size() == 1:
+        world = dist.get_world_size()
+        if world == 1:
             return self
-        assert self.capture_mean_cov and not self.capture_all
         n = torch.tensor([float(self.num_items)], dtype=torch.float64, device=self.device)
-        for t in (self.raw_mean, self.raw_cov, n):
-            torch.distributed.all_reduce(t, group=group)
+        torch.distributed.all_reduce(n, group=group)
+        if self.capture_all:
+            # rank r holds the samples r, r + world, ...: ONE all_gather of the (equally padded) shards, interleaved back into
+            # sample order, so every rank ends with the same [num_items, F] matrix
+            assert self.keep_on_device, 'captured features are exchanged on the device'
+            mine = torch.cat(self.all_features, 0)
+            total = int(n.item())
+            per = (total + world - 1) // world
+            shard = torch.zeros(per, mine.shape[1], dtype=mine.dtype, device=mine.device)
+            shard[:mine.shape[0]] = mine
+            parts = [torch.empty_like(shard) for _ in range(world)]
+            torch.distributed.all_gather(parts, shard, group=group)
+            self.all_features = [torch.stack(parts, 1).reshape(per * world, -1)[:total]]
+        if self.capture_mean_cov:
+            for t in (self.raw_mean, self.raw_cov):
+                torch.distributed.all_reduce(t, group=group)
         self.num_items = int(n.item())
         return self
 
-    def get_all(self):
+    def get_all_torch(self):
         assert self.capture_all
-        return torch.cat(self.all_features, 0).numpy()
+        return torch.cat(self.all_features, 0)
+
+    def get_all(self):
+        return self.get_all_torch().cpu().numpy()
 
     def get_mean_cov(self):
         assert self.capture_mean_cov and self.num_items > 0
@@ -212,8 +236,9 @@ class MetricOptions:
 
     def __init__(self, G, prompts=None, resolution=512, init_timestep=625, detector=None, real_stats=None, open_clip_detector=None,
                  clip_score_fn=None, device=None, seed=0, batch_gen=4, detector_size=256, progress=None, dataset_kwargs=None,
-                 dataset=None):
+                 dataset=None, run_dir=None):
         from .dnnlib_util import construct_class_by_name
+        self.run_dir = run_dir
         if dataset is None and dataset_kwargs:
             dataset = construct_class_by_name(**dataset_kwargs)
         if dataset is None:
@@ -228,7 +253,48 @@ class MetricOptions:
         self.rank, self.num_gpus = dist.get_rank(), dist.get_world_size()
 
 
-def generator_feature_stats(opts, num_gen, compute_clip=False):
+def _caption(dataset, i):
+    """Caption i without decoding the image next to it."""
+    return dataset.caption(i) if hasattr(dataset, 'caption') else dataset[i][1]
+
+
+def dataset_feature_stats(opts, max_items=None, capture_all=False):
+    """Detector features of the real images (compute_feature_stats_for_dataset, metrics/sid_metric_utils.py:266-280): the first
+    min(len, max_items) items of `opts.dataset`, rank-strided, to the device as uint8 exactly as stored (no resize), grey -> 3
+    channels, through the detector.  -> FeatureStats holding mean / covariance, or (capture_all) every feature vector in item
+    order ON THE DEVICE; ranks are merged, so every rank returns the same statistics."""
+    dataset = opts.dataset
+    if not getattr(dataset, 'has_images', False):
+        raise ValueError('real-set features need an image dataset (--data: a directory of images with .txt captions; '
+                         'sid_lsg_amd.data.ImageCaptionDataset), not a caption list')
+    num_items = len(dataset) if max_items is None else min(len(dataset), max_items)
+    if num_items < opts.num_gpus:
+        raise ValueError(f'{num_items} real images for {opts.num_gpus} ranks: every rank needs at least one')
+    detector = load_detector(opts.detector, opts.device)
+    stats = FeatureStats(capture_all=capture_all, capture_mean_cov=not capture_all, device=opts.device, keep_on_device=capture_all)
+    mine = list(range(opts.rank, num_items, opts.num_gpus))
+    batch = []
+
+    def flush():
+        if batch:
+            images = torch.stack(batch).to(opts.device)
+            if images.shape[1] == 1:
+                images = images.repeat(1, 3, 1, 1)
+            with torch.no_grad():
+                stats.append(detector(images, return_features=True))
+            batch.clear()
+    for n, i in enumerate(mine):
+        image = dataset[i][0]
+        if batch and (len(batch) == 64 or image.shape != batch[0].shape):      # a batch is a run of equally sized images
+            flush()
+        batch.append(image)
+        if opts.progress is not None and n % 64 == 0:
+            opts.progress(n * opts.num_gpus, num_items)
+    flush()
+    return stats.merge_ranks()
+
+
+def generator_feature_stats(opts, num_gen, compute_clip=False, capture_all=False):
     """sid_metric_utils.py:412-510: this rank's share of `num_gen` samples -- prompts in the order of the reference's
     `InfiniteSampler(dataset, rank, num_gpus, seed=0)` (shuffled, rank-strided; :420), z ~ N(0, I) from a per-rank generator --
     through G, the detector and (optionally) the CLIP detectors."""
@@ -236,14 +302,14 @@ def generator_feature_stats(opts, num_gen, compute_clip=False):
     order = iter(InfiniteSampler(opts.dataset, rank=opts.rank, num_replicas=opts.num_gpus, seed=0))
     detector = load_detector(opts.detector, opts.device)
     oc = load_detector(opts.open_clip_detector, opts.device) if (compute_clip and opts.open_clip_detector is not None) else None
-    stats = FeatureStats(capture_mean_cov=True, max_items=None, device=opts.device)
+    stats = FeatureStats(capture_mean_cov=not capture_all, capture_all=capture_all, keep_on_device=capture_all, max_items=None, device=opts.device)
     gen = torch.Generator(device=opts.device).manual_seed(opts.seed * opts.num_gpus + opts.rank)
     lat = opts.resolution // 8
     mine = list(range(opts.rank, num_gen, opts.num_gpus))          # global sample indices of this rank
     oc_scores, clip_scores = [], []
     for i in range(0, len(mine), opts.batch_gen):
         idx = mine[i:i + opts.batch_gen]
-        texts = [opts.dataset[next(order)][1] for _ in idx]
+        texts = [_caption(opts.dataset, next(order)) for _ in idx]
         z = torch.randn([len(idx), 4, lat, lat], device=opts.device, generator=gen)
         with torch.no_grad():
             img = opts.G(latents=z, contexts=texts, init_timesteps=opts.init_timestep * torch.ones(len(idx), device=opts.device, dtype=torch.long))
@@ -273,8 +339,27 @@ def generator_feature_stats(opts, num_gen, compute_clip=False):
     return stats, mean_over_ranks(oc_scores), mean_over_ranks(clip_scores)
 
 
-def load_real_stats(real_stats):
-    """(mu, sigma) of the real set: a cached .npz / .pkl of the reference's FeatureStats dict, or a (mu, sigma) pair."""
+REAL_STATS_FILE = 'real_stats.npz'
+
+
+def load_real_stats(real_stats, opts=None):
+    """(mu, sigma) of the real set: a cached .npz / .pkl of the reference's FeatureStats dict, or a (mu, sigma) pair.  None with
+    an image dataset in `opts`: `<opts.run_dir>/real_stats.npz` when a previous tick or run left it, else computed from the images
+    (dataset_feature_stats) and cached there in the same layout, ready to be passed as --data_stat."""
+    if real_stats is None and opts is not None and getattr(opts.dataset, 'has_images', False):
+        cache = os.path.join(opts.run_dir, REAL_STATS_FILE) if opts.run_dir else None
+        have = torch.tensor([1.0 if (cache and opts.rank == 0 and os.path.isfile(cache)) else 0.0], device=opts.device)
+        if opts.num_gpus > 1:
+            torch.distributed.broadcast(have, src=0)         # all ranks agree (the file is rank 0's)
+        if float(have) != 0:
+            return load_real_stats(cache)
+        stats = dataset_feature_stats(opts)
+        if cache and opts.rank == 0:
+            os.makedirs(opts.run_dir, exist_ok=True)
+            tmp = cache + '.tmp.npz'
+            stats.save(tmp)
+            os.replace(tmp, cache)
+        return stats.get_mean_cov()
     if isinstance(real_stats, (tuple, list)):
         return np.asarray(real_stats[0]), np.asarray(real_stats[1])
     if isinstance(real_stats, str) and real_stats.endswith('.npz'):
@@ -290,11 +375,31 @@ def load_real_stats(real_stats):
 
 def compute_fid_and_clip(opts, num_gen, compute_clip=False):
     """metrics/sid_fid_and_clip.py:32-74."""
-    mu_real, sigma_real = load_real_stats(opts.real_stats)
+    mu_real, sigma_real = load_real_stats(opts.real_stats, opts)
     stats, open_clip_score, clip_score = generator_feature_stats(opts, num_gen, compute_clip)
     mu_gen, sigma_gen = stats.get_mean_cov()
     fid = frechet_distance(mu_gen, sigma_gen, mu_real, sigma_real)
     return (fid, open_clip_score, clip_score) if compute_clip else fid
+
+
+def compute_pr(opts, max_real, num_gen, nhood_size):
+    """Precision and recall of Kynkaanniemi et al. (metrics/sid_precision_recall.py:36-66): a generated sample counts towards
+    precision when it lies within the k-th neighbour radius of some real feature vector, a real one towards recall when it lies
+    within that of some generated one.  Features rounded to fp16 as the reference does (:48, :52); radius and membership on the
+    sidlsg_pr_* kernels.  Every rank holds all features after the gather and computes the same two numbers."""
+    from . import ops
+    real = dataset_feature_stats(opts, max_items=max_real, capture_all=True).get_all_torch()
+    gen = generator_feature_stats(opts, num_gen, capture_all=True)[0].get_all_torch()
+    real, gen = (f.to(opts.device, torch.float16).contiguous() for f in (real, gen))
+    results = {}
+    for name, manifold, probes in (('precision', real, gen), ('recall', gen, real)):
+        k = nhood_size
+        if manifold.shape[0] <= k:       # the reference's kthvalue raises here; the smoke-sized pr_test takes the farthest member
+            k = manifold.shape[0] - 1
+            dist.print0(f'WARNING: precision / recall: {manifold.shape[0]} features for nhood_size {nhood_size}: using k = {k}')
+        radius = ops.pr_kth_radius(manifold, k)
+        results[name] = float(ops.pr_member(probes, manifold, radius).to(torch.float64).mean())       # the exact share: count / n
+    return results['precision'], results['recall']
 
 
 # ------------------------------------------------------------------------------------------------
@@ -334,6 +439,21 @@ def fid_test(opts):
 def fid_clip_test(opts):
     fid, oc, cs = compute_fid_and_clip(opts, max(1, getattr(opts, 'num_test', 1)), compute_clip=True)
     return dict(fid30k_full=fid, open_clipscore_30k=oc, clipscore30k=cs)
+
+
+@register_metric
+def pr30k3_full(opts):
+    precision, recall = compute_pr(opts, max_real=None, num_gen=30000, nhood_size=3)
+    return dict(pr30k3_full_precision=precision, pr30k3_full_recall=recall)
+
+
+@register_metric
+def pr_test(opts):
+    precision, recall = compute_pr(opts, max_real=None, num_gen=max(1, getattr(opts, 'num_test', 1)), nhood_size=3)
+    return dict(pr30k3_full_precision=precision, pr30k3_full_recall=recall)
+
+
+NEEDS_IMAGES = ('pr30k3_full', 'pr_test')      # metrics that read the real images themselves: --data_stat cannot stand in
 
 
 def calc_metric(metric, **kwargs):

@@ -1865,6 +1865,58 @@ def image_grid_u8(images, grid, first, gw, drange=(-1, 1), layout='nchw'):
     return grid
 
 
+F16 = torch.float16
+
+
+def _pr_features(x, name):
+    """A feature matrix for the precision / recall kernels: fp16 [n, F] on the device, F padded with zero columns to a multiple of
+    32 (zeros change neither a norm nor a dot product)."""
+    if x.dim() != 2 or x.shape[0] == 0 or x.shape[1] == 0:
+        raise RuntimeError(f'{name}: expected a non-empty [n, F] feature matrix, got {tuple(x.shape)}')
+    _chk(x, F16)
+    pad = -x.shape[1] % 32
+    return torch.nn.functional.pad(x, [0, pad]) if pad else x
+
+
+def pr_distances(rows, cols):
+    """[R, C] fp16 distances between fp16 feature sets (sidlsg_pr_distances): the dense form of the precision / recall kernels,
+    the reference's `compute_distances` (metrics/sid_precision_recall.py:19-32) without its host round trip."""
+    rows, cols = _pr_features(rows, 'pr_distances'), _pr_features(cols, 'pr_distances')
+    if rows.shape[1] != cols.shape[1]:
+        raise RuntimeError(f'pr_distances: feature widths differ ({rows.shape[1]} vs {cols.shape[1]})')
+    out = torch.empty((rows.shape[0], cols.shape[0]), device=rows.device, dtype=F16)
+    lib.sidlsg_pr_distances(_p(rows), rows.shape[0], _p(cols), cols.shape[0], rows.shape[1], _p(out), _s())
+    return out
+
+
+PR_MAX_FUSED_K = 7
+
+
+def pr_kth_radius(manifold, k):
+    """[N] fp16: per row of `manifold` the (k+1)-th smallest distance to the rows of the same set, itself included
+    (`dist.kthvalue(k + 1)`, :59).  k <= 7 runs fused (sidlsg_pr_kth_radius, no [N, N] matrix); a larger k goes through the
+    dense kernel in row blocks and torch.kthvalue on the device -- the same distances, bit for bit."""
+    manifold = _pr_features(manifold, 'pr_kth_radius')
+    n = manifold.shape[0]
+    if not 0 <= k < n:
+        raise RuntimeError(f'pr_kth_radius: k = {k} needs a set of at least k + 1 rows, got {n}')
+    if k > PR_MAX_FUSED_K:
+        return torch.cat([pr_distances(blk, manifold).float().kthvalue(k + 1).values.to(F16) for blk in manifold.split(8192)])
+    out = torch.empty(n, device=manifold.device, dtype=F16)
+    lib.sidlsg_pr_kth_radius(_p(manifold), n, manifold.shape[1], int(k), _p(out), _s())
+    return out
+
+
+def pr_member(probes, manifold, radius):
+    """[P] bool: probe i lies inside the manifold, i.e. within radius[j] of some manifold row j (sidlsg_pr_member; :64)."""
+    probes, manifold = _pr_features(probes, 'pr_member'), _pr_features(manifold, 'pr_member')
+    if probes.shape[1] != manifold.shape[1] or radius.shape != (manifold.shape[0],):
+        raise RuntimeError(f'pr_member: probes {tuple(probes.shape)}, manifold {tuple(manifold.shape)}, radius {tuple(radius.shape)}')
+    out = torch.empty(probes.shape[0], device=probes.device, dtype=torch.uint8)
+    lib.sidlsg_pr_member(_p(probes), probes.shape[0], _p(manifold), manifold.shape[0], probes.shape[1], _p(_chk(radius, F16)), _p(out), _s())
+    return out.bool()
+
+
 def _det_synced(backward):
     @functools.wraps(backward)
     def wrapper(*args):

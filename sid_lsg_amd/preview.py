@@ -12,7 +12,8 @@ at every snapshot tick (training/sid_training_loop.py:39-50 setup_snapshot_image
     forked generator state seeded per call, so a grid depends on (weights, n) alone and the caller's RNG stream does not see it.
   * save_png: PIL when present, else a zlib + CRC writer.
 
-`reals.png` is not written: the datasets here yield captions, not pixels.
+  * write_reals: `reals.png` (sid_training_loop.py:347-350), when the dataset yields pixels (data.ImageCaptionDataset): the first
+    gw x gh items of the set, taken cyclically, in range 0..255 through the same grid kernel.
 """
 import os
 import struct
@@ -69,6 +70,23 @@ def render_grid(G, grid, num_steps_eval, *, noise_scheduler, text_encoder, token
             vae.decode_to_grid(x.to(vae.dtype) / vae.config.scaling_factor, out, first, gw)
             first += len(c)
     return out
+
+
+def write_reals(out_dir, dataset, size, resolution, device):
+    """<out_dir>/reals.png: item i % len(dataset) in tile i.  The images are shown as stored, so they must be resolution x resolution."""
+    from . import ops
+    gw, gh = size
+    out = torch.zeros((gh * resolution, gw * resolution, 3), dtype=torch.uint8, device=device)
+    for i in range(gw * gh):
+        image = dataset[i % len(dataset)][0]
+        if tuple(image.shape[-2:]) != (resolution, resolution):
+            raise ValueError(f'reals.png: item {i % len(dataset)} is {tuple(image.shape[-2:])}, the grid needs {resolution} x {resolution} images')
+        if image.shape[0] == 1:
+            image = image.repeat(3, 1, 1)
+        ops.image_grid_u8(image[None].to(device, torch.float32).contiguous(), out, i, gw, drange=(0, 255), layout='nchw')
+    path = os.path.join(out_dir, 'reals.png')
+    save_png(path, out.cpu().numpy())
+    return path
 
 
 def write_grids(out_dir, name_format, G, grid, step_counts=STEP_COUNTS, **render_kwargs):

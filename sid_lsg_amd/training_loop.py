@@ -14,7 +14,8 @@ loop against tests/golden/loop_*.npz (curves produced by the UNMODIFIED referenc
 snapshot_images=True (off by default; rank 0 only) writes the reference's preview grids through sid_lsg_amd.preview: `fakes_init.png`
 on a fresh start and `fakes_<alpha>_<kimg>_<n>.png` for n = 1, 2, 4 generation steps next to every network snapshot, from G_ema
 (:258-271, 347-364, 597-616); their time is maintenance time, not `Timing/sec_per_kimg`, and the training RNG stream does not see
-them.  `reals.png` is not written: the datasets here yield captions, not pixels (an image loader is a feature of its own).
+them.  `reals.png` (:347-350) is written next to `fakes_init.png` when `dataset_kwargs` names an image dataset
+(data.ImageCaptionDataset).
 Not reproduced: torch.cuda.empty_cache + gc.collect every iteration (:384-385, a pure slowdown).
 num_steps = N > 1 trains an N-step generator through the reference's
 multi-step training sampler (sid_sd_util.py:176-185, which the reference marks as work in progress): PromptStream draws its
@@ -237,8 +238,8 @@ def training_loop(
         # the grid's prompts: the caption set of dataset_kwargs when given, else the training prompts (:198-200, 265); no collective
         # inside, so the other ranks simply skip it
         from . import preview
-        grid = preview.setup_snapshot_grid(construct_class_by_name(**dataset_kwargs) if dataset_kwargs else dataset_obj, resolution,
-                                           batch_gpu, (4, lat, lat), device)
+        grid_set = construct_class_by_name(**dataset_kwargs) if dataset_kwargs else dataset_obj
+        grid = preview.setup_snapshot_grid(grid_set, resolution, batch_gpu, (4, lat, lat), device)
 
         def write_previews(name_format, step_counts=preview.STEP_COUNTS):
             if G_ema is not G:      # the fused Adam + EMA kernel writes G_ema's masters only: bring its forward copies up to date
@@ -247,6 +248,9 @@ def training_loop(
                                 text_encoder=text_encoder, tokenizer=tokenizer, vae=vae, init_timestep=init_timestep,
                                 resolution=resolution, num_steps=num_steps)
         if resume_training is None:
+            if getattr(grid_set, 'has_images', False):
+                dist.print0('Exporting sample real images...')
+                preview.write_reals(run_dir, grid_set, grid.size, resolution, device)
             dist.print0('Text prompts for example images:')
             for c in grid.c:
                 dist.print0(c)
@@ -361,7 +365,7 @@ def training_loop(
                 extra = dict(num_test=metric_num_test) if metric_num_test is not None else {}
                 result = metric_main.calc_metric(metric, G=G_eval, resolution=resolution, init_timestep=init_timestep, detector=metric_pt_path,
                                                  real_stats=metric_real_stats, open_clip_detector=metric_open_clip_path, device=device,
-                                                 **msrc, **extra)
+                                                 run_dir=run_dir, **msrc, **extra)
                 metric_main.report_metric(result, run_dir=run_dir, alpha=alpha,
                                           snapshot_pkl=os.path.join(run_dir, f'network-snapshot-{alpha:03f}-{cur_nimg // 1000:06d}.pkl') if run_dir else None)
                 for k, v in result.results.items():
@@ -424,11 +428,13 @@ def evaluate_network(run_dir, dataset_kwargs, network_kwargs, device, metrics, i
     if snapshot_images and dist.get_rank() == 0 and run_dir:
         from . import preview
         lat = resolution // (2 ** (len(vae.config.block_out_channels) - 1))
-        grid = preview.setup_snapshot_grid(construct_class_by_name(**msrc['dataset_kwargs']), resolution,
-                                           batch_gpu or max(batch_size // dist.get_world_size(), 1), (4, lat, lat), device)
+        grid_set = construct_class_by_name(**msrc['dataset_kwargs'])
+        grid = preview.setup_snapshot_grid(grid_set, resolution, batch_gpu or max(batch_size // dist.get_world_size(), 1), (4, lat, lat), device)
         for c in grid.c:
             dist.print0(c)
         os.makedirs(run_dir, exist_ok=True)
+        if getattr(grid_set, 'has_images', False):
+            preview.write_reals(run_dir, grid_set, grid.size, resolution, device)
     out = {}
     for num_steps_eval in (1, 2, 4):
         for metric in metrics:
@@ -441,7 +447,8 @@ def evaluate_network(run_dir, dataset_kwargs, network_kwargs, device, metrics, i
                                     init_timestep=init_timestep, resolution=resolution, num_steps=num_steps)
             extra = dict(num_test=metric_num_test) if metric_num_test is not None else {}
             result = metric_main.calc_metric(metric, G=G_eval, resolution=resolution, init_timestep=init_timestep, detector=metric_pt_path,
-                                             real_stats=metric_real_stats, open_clip_detector=metric_open_clip_path, device=device, **msrc, **extra)
+                                             real_stats=metric_real_stats, open_clip_detector=metric_open_clip_path, device=device,
+                                             run_dir=run_dir, **msrc, **extra)
             out[(metric, num_steps_eval)] = result
             if dist.get_rank() == 0:
                 print(result.results)

@@ -16,9 +16,11 @@ Differences (documented, not silent):
     world size give the same bits (sid_lsg_amd.ops.set_deterministic);
   * `--snapshot_images 1` (added option) writes the preview grids `fakes_init.png` and `fakes_<alpha>_<kimg>_{1,2,4}.png` next to the
     snapshots, and `<metric><kimg>_<steps>.png` with `--train_mode 0` (sid_lsg_amd/preview.py); the reference always writes them;
-  * `--metrics` run through sid_lsg_amd/metrics.py at the snapshot ticks and need LOCAL detector / statistics files
-    (--metric_pt_path, --data_stat); `--train_mode 0 --network_pkl <snapshot>` evaluates a snapshot (1 / 2 / 4 steps);
-  * `--data` is optional (it is the COCO image set used only by the metrics).
+  * `--metrics` run through sid_lsg_amd/metrics.py at the snapshot ticks and need a LOCAL detector file (--metric_pt_path);
+    the real-set statistics come from --data_stat or, when --data is an image directory, from the images themselves (cached as
+    <run_dir>/real_stats.npz); pr30k3_full / pr_test (precision / recall) always read the images;
+    `--train_mode 0 --network_pkl <snapshot>` evaluates a snapshot (1 / 2 / 4 steps);
+  * `--data` is optional (it is the COCO image set used only by the metrics and by reals.png).
 """
 import json
 import os
@@ -113,9 +115,17 @@ def build_config(o):
         bad = [m for m in o.metrics if not _metrics.is_valid_metric(m)]
         if bad:
             raise click.ClickException(f'--metrics: unknown {bad}; valid: {_metrics.list_valid_metrics()}')
-        for flag, path in (('--metric_pt_path', o.metric_pt_path), ('--data_stat', o.data_stat)):
+        from sid_lsg_amd.data import has_image_files
+        has_images = has_image_files(o.data)
+        needs_images = [m for m in o.metrics if m in _metrics.NEEDS_IMAGES]
+        # --data_stat may be left out when the statistics can be computed from the images of --data
+        need_stat = o.data_stat is not None or (len(needs_images) < len(o.metrics) and not has_images)
+        for flag, path in (('--metric_pt_path', o.metric_pt_path),) + ((('--data_stat', o.data_stat),) if need_stat else ()):
             if not path or not os.path.isfile(path):
                 raise click.ClickException(f'--metrics needs {flag} to be a local file (got {path!r})')
+        if needs_images and not has_images:
+            raise click.ClickException(f'--metrics {",".join(needs_images)} read the real images: --data must be a directory of images '
+                                       f'with .txt captions (got {o.data!r})')
     if o.fake_score_use_lora:
         raise click.ClickException('--fake_score_use_lora is not supported')
     if not o.train_mode:
@@ -127,11 +137,13 @@ def build_config(o):
     c.metric_real_stats = o.data_stat
     if o.metrics is not None and o.data:
         # the evaluation caption set (reference: training.mscoco_dataset.ImageDataset on --data, sid_train.py:232-235)
-        c.dataset_kwargs = EasyDict(class_name='sid_lsg_amd.data.CaptionDataset', path=o.data, resolution=o.resolution, random_flip=o.xflip)
+        # with the pixels only where they are read: precision / recall, statistics without --data_stat, reals.png
+        images = has_images and bool(needs_images or o.data_stat is None or o.get('snapshot_images', False))
+        cls = 'ImageCaptionDataset' if images else 'CaptionDataset'
+        c.dataset_kwargs = EasyDict(class_name=f'sid_lsg_amd.data.{cls}', path=o.data, resolution=o.resolution, random_flip=o.xflip)
         # fail at start-up, not at the first metrics tick hours into the run: the set is only constructed there
         try:
-            from sid_lsg_amd.data import CaptionDataset
-            CaptionDataset(o.data, resolution=o.resolution)
+            construct_class_by_name(**c.dataset_kwargs)
         except OSError as e:
             raise click.ClickException(f'--metrics with --data {o.data!r}: {e} (an image + .txt caption directory, or a text file with one caption per line)')
     c.data_loader_kwargs = EasyDict(pin_memory=True, num_workers=o.workers, prefetch_factor=2)

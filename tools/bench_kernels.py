@@ -2,7 +2,7 @@
 """Per-shape kernel micro-benchmarks on the SD1.5 work list -- the optimisation harness.
 Prints achieved TFLOP/s (contractions) or GB/s (HBM-bound kernels) per shape.  GPU only.
 
-    python tools/bench_kernels.py [conv] [gemm] [wgrad] [attn] [norm] [geglu] [fp8] [--batch 16]
+    python tools/bench_kernels.py [conv] [gemm] [wgrad] [attn] [norm] [geglu] [fp8] [pr] [--batch 16]
 """
 import os
 import sys
@@ -166,6 +166,66 @@ def bench_geglu(B):
         tf = timeit(lambda: lib.sidlsg_geglu_fwd(h.data_ptr(), y.data_ptr(), M, F, ops._s()))
         tb = timeit(lambda: lib.sidlsg_geglu_bwd(h.data_ptr(), dy.data_ptr(), dh.data_ptr(), M, F, ops._s()))
         print(f'  {M}x{F}: fwd {tf * 1e6:7.1f} us {3.0 * M * F * 2 / tf / 1e9:6.0f} GB/s | bwd {tb * 1e6:7.1f} us {5.0 * M * F * 2 / tb / 1e9:6.0f} GB/s')
+
+
+def bench_pr(_B, N=30000, F=2048, k=3, rounds=5):
+    """Precision / recall at the size of pr30k3_full: one k-th neighbour radius sweep and one membership sweep of the fused kernels
+    against the same two results from torch on the device (the expansion with `a @ b.T` in 10 000-column blocks, `topk` / `any`),
+    alternating in one session.  Features on a low-dimensional manifold, like the tests' fixture."""
+    print(f'--- precision / recall sweeps, N = P = {N}, F = {F}, k = {k}: ms per sweep, {rounds} alternating rounds')
+    g = torch.Generator(device=dev).manual_seed(1)
+    A = torch.randn(6, F, device=dev, generator=g) / 6 ** 0.5
+    b = 0.3 * torch.randn(F, device=dev, generator=g).abs()
+
+    def feats(scale, shift):
+        z = scale * torch.randn(N, 6, device=dev, generator=g) + shift
+        return (z @ A + b + 0.01 * torch.randn(N, F, device=dev, generator=g)).clamp_min(0).to(torch.float16)
+    m, p = feats(1.0, 0.0), feats(0.8, 0.35)
+
+    def torch_dist(rows, cols, nr, nc):
+        return (nr[:, None] + nc[None, :] - 2.0 * (rows @ cols.t()).float()).clamp_min(0).sqrt().to(torch.float16)
+
+    def torch_radius():
+        nm, out = m.float().square().sum(1), []
+        for r0 in range(0, N, 10000):
+            best = None
+            for c0 in range(0, N, 10000):
+                d = torch_dist(m[r0:r0 + 10000], m[c0:c0 + 10000], nm[r0:r0 + 10000], nm[c0:c0 + 10000])
+                small = d.topk(k + 1, dim=1, largest=False).values
+                best = small if best is None else torch.cat([best, small], 1).topk(k + 1, dim=1, largest=False).values
+            out.append(best[:, k])
+        return torch.cat(out)
+
+    def torch_member(radius):
+        nm, npr, out = m.float().square().sum(1), p.float().square().sum(1), []
+        for r0 in range(0, N, 10000):
+            inside = torch.zeros(min(10000, N - r0), dtype=torch.bool, device=dev)
+            for c0 in range(0, N, 10000):
+                d = torch_dist(p[r0:r0 + 10000], m[c0:c0 + 10000], npr[r0:r0 + 10000], nm[c0:c0 + 10000])
+                inside |= (d <= radius[c0:c0 + 10000]).any(1)
+            out.append(inside)
+        return torch.cat(out)
+    radius = ops.pr_kth_radius(m, k)
+    inside = ops.pr_member(p, m, radius)
+    radius_t = torch_radius()
+    inside_t = torch_member(radius)
+    print(f'  results: {int((radius != radius_t).sum())} of {N} radii and {int((inside != inside_t).sum())} of {N} decisions differ '
+          f'(torch rounds the fp16 GEMM result, the kernels keep fp32); precision {float(inside.float().mean()):.4f}')
+    times = dict(hip_radius=[], torch_radius=[], hip_member=[], torch_member=[])
+    for _ in range(rounds):
+        times['hip_radius'].append(timeit(lambda: ops.pr_kth_radius(m, k), iters=3, warm=1))
+        times['torch_radius'].append(timeit(torch_radius, iters=3, warm=1))
+        times['hip_member'].append(timeit(lambda: ops.pr_member(p, m, radius), iters=3, warm=1))
+        times['torch_member'].append(timeit(lambda: torch_member(radius), iters=3, warm=1))
+    fl = 2.0 * N * N * F
+    med = {}
+    for name, ts in times.items():
+        med[name] = sorted(ts)[len(ts) // 2]
+        print(f'  {name:13s}: ' + ' '.join(f'{t * 1e3:8.2f}' for t in ts) + f'   median {med[name] * 1e3:8.2f} ms  {fl / med[name] / 1e12:6.1f} TFLOP/s of 2 N^2 F')
+    for what in ('radius', 'member'):
+        h, t = med['hip_' + what], med['torch_' + what]
+        print(f'  {what}: the fused kernel is {t / h:.2f}x the speed of torch' + (' (FASTER)' if h < t else ' (SLOWER)'))
+    print(f'  peak memory of the process: {torch.cuda.max_memory_allocated() / 2 ** 20:.0f} MiB (the torch blocks: 10 000 x 10 000 fp32 + fp16)')
 
 
 if __name__ == '__main__':
