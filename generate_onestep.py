@@ -10,6 +10,10 @@ latent drawn from torch.Generator(seed_i) (`StackedRandomGenerator`), x_hat = G(
 over ranks.  `--repo_id` must be a local diffusers-layout directory (text encoder, tokenizer, VAE, scheduler) or `random:<arch>`
 (`random:<arch>:v` for a v-prediction model); its parameterisation must be the snapshot's.  `--resolution` is the image size
 (latent = resolution / 8; 768 for an SD 2.x 768-v generator).
+
+`--network teacher` samples the teacher itself instead of a snapshot: the UNet of `--repo_id` under classifier-free guidance
+(`--guidance_scale`, default 7.5) and a deterministic DDIM sampler of `--teacher_steps` steps (default 50;
+sid_lsg_amd.sd_util.teacher_sample), with the same seeds, prompts and file names -- the teacher row of the SiD-LSG tables.
 """
 import os
 import pickle
@@ -21,7 +25,7 @@ import torch
 
 from sid_lsg_amd import distributed as dist
 from sid_lsg_amd.preview import save_png
-from sid_lsg_amd.sd_util import check_prediction_type, load_sd15, sid_sd_sampler
+from sid_lsg_amd.sd_util import TEACHER, TEACHER_CFG, TEACHER_STEPS, check_prediction_type, load_sd15, sid_sd_sampler, teacher_sample
 
 
 class StackedRandomGenerator:
@@ -51,8 +55,19 @@ def read_prompts(path):
         return [line.strip() for line in f if line.strip()]
 
 
+def teacher_options(network_pkl, teacher_steps, guidance_scale):
+    """-> (steps, guidance scale) when --network is the teacher sentinel, else None; the teacher's options with a snapshot are refused."""
+    if network_pkl != TEACHER:
+        given = [f for f, v in (('--teacher_steps', teacher_steps), ('--guidance_scale', guidance_scale)) if v is not None]
+        if given:
+            raise click.UsageError(f'{" / ".join(given)} apply to --network {TEACHER} only: a distilled generator is sampled without guidance '
+                                   'in --num_steps_eval steps')
+        return None
+    return (TEACHER_STEPS if teacher_steps is None else teacher_steps), (TEACHER_CFG if guidance_scale is None else guidance_scale)
+
+
 @click.command()
-@click.option('--network', 'network_pkl', type=str, required=True, metavar='PATH', help='Network snapshot pickle')
+@click.option('--network', 'network_pkl', type=str, required=True, metavar='PATH', help=f'Network snapshot pickle, or "{TEACHER}": sample the UNet of --repo_id itself')
 @click.option('--outdir', type=str, required=True, metavar='DIR', help='Where to save the output images')
 @click.option('--seeds', type=parse_int_list, default='0-63', show_default=True, metavar='LIST', help='Random seeds (e.g. 1,2,5-10)')
 @click.option('--subdirs', is_flag=True, help='Create subdirectory for every 1000 seeds')
@@ -66,10 +81,13 @@ def read_prompts(path):
 @click.option('--enable_compress_npz', type=bool, default=False, show_default=True, help='Also write the batch as images.npz')
 @click.option('--num_steps_eval', type=click.IntRange(min=0), default=1, show_default=True, help='Generation steps (1 = one-step)')
 @click.option('--custom_seed', type=bool, default=False, show_default=True, help='Prompt i <-> i-th seed of the list instead of seed value')
+@click.option('--teacher_steps', type=click.IntRange(min=1), default=None, help=f'DDIM steps of --network {TEACHER}  [default: {TEACHER_STEPS}]')
+@click.option('--guidance_scale', type=float, default=None, help=f'Classifier-free guidance scale of --network {TEACHER}  [default: {TEACHER_CFG}]')
 def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, init_timestep, text_prompts, repo_id, resolution, use_fp16,
-         enable_compress_npz, num_steps_eval, custom_seed):
+         enable_compress_npz, num_steps_eval, custom_seed, teacher_steps, guidance_scale):
     if resolution % 8:
         raise click.BadParameter(f'{resolution}: must be a multiple of 8', param_hint='--resolution')
+    teacher = teacher_options(network_pkl, teacher_steps, guidance_scale)
     dist.init()
     device = torch.device('cuda')
     rank, world = dist.get_rank(), dist.get_world_size()
@@ -81,16 +99,23 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
 
     if world > 1 and rank != 0:
         torch.distributed.barrier()                    # rank 0 touches the files first
-    dist.print0(f'Loading network from "{network_pkl}"...')
-    with open(network_pkl, 'rb') as f:
-        G_ema = pickle.load(f)['ema'].to(device)
-    G_ema.eval().requires_grad_(False)
-    _, vae, sched, text_encoder, tokenizer = load_sd15(repo_id, repo_id, device, torch.bfloat16)
-    del _
-    check_prediction_type(G_ema, sched)       # a v snapshot with an epsilon --repo_id (or the reverse) would sample garbage
+    if teacher is None:
+        dist.print0(f'Loading network from "{network_pkl}"...')
+        with open(network_pkl, 'rb') as f:
+            G_ema = pickle.load(f)['ema'].to(device)
+        G_ema.eval().requires_grad_(False)
+        _, vae, sched, text_encoder, tokenizer = load_sd15(repo_id, repo_id, device, torch.bfloat16)
+        del _
+        check_prediction_type(G_ema, sched)       # a v snapshot with an epsilon --repo_id (or the reverse) would sample garbage
+    else:
+        dist.print0(f'Sampling the teacher "{repo_id}": DDIM {teacher[0]} steps, guidance scale {teacher[1]:g}')
+        G_ema, vae, sched, text_encoder, tokenizer = load_sd15(repo_id, repo_id, device, torch.bfloat16)
+        G_ema.eval().requires_grad_(False)
+        if num_steps_eval != 1:
+            dist.print0(f'Note: --num_steps_eval {num_steps_eval} is ignored with --network {TEACHER} (the step count is --teacher_steps)')
     if world > 1 and rank == 0:
         torch.distributed.barrier()
-    if num_steps_eval > 1:
+    if teacher is None and num_steps_eval > 1:
         outdir = f'{outdir}_numstep{num_steps_eval}'
 
     lat = resolution // 8
@@ -105,11 +130,16 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
         z = StackedRandomGenerator(device, batch_seeds).randn([len(batch), 4, lat, lat], device=device)
         prompts = [captions[i % len(captions)] for i in batch]
         with torch.no_grad():
-            images = sid_sd_sampler(unet=G_ema, latents=z, contexts=prompts,
-                                    init_timesteps=init_timestep * torch.ones(len(batch), device=device, dtype=torch.long),
-                                    noise_scheduler=sched, text_encoder=text_encoder, tokenizer=tokenizer, resolution=resolution,
-                                    dtype=torch.bfloat16, return_images=True, vae=vae, num_steps=1, train_sampler=False,
-                                    num_steps_eval=num_steps_eval)
+            if teacher is not None:
+                images = teacher_sample(unet=G_ema, latents=z, contexts=prompts, noise_scheduler=sched, text_encoder=text_encoder,
+                                        tokenizer=tokenizer, resolution=resolution, guidance_scale=teacher[1],
+                                        num_inference_steps=teacher[0], return_images=True, vae=vae)
+            else:
+                images = sid_sd_sampler(unet=G_ema, latents=z, contexts=prompts,
+                                        init_timesteps=init_timestep * torch.ones(len(batch), device=device, dtype=torch.long),
+                                        noise_scheduler=sched, text_encoder=text_encoder, tokenizer=tokenizer, resolution=resolution,
+                                        dtype=torch.bfloat16, return_images=True, vae=vae, num_steps=1, train_sampler=False,
+                                        num_steps_eval=num_steps_eval)
         arr = (images.float() * 127.5 + 128).clip(0, 255).to(torch.uint8).permute(0, 2, 3, 1).cpu().numpy()
         for key, img in zip(batch, arr):
             d = os.path.join(outdir, f'{key - key % 1000:06d}') if subdirs else outdir

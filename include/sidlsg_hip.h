@@ -248,6 +248,17 @@ int sidlsg_step_renoise(const float* eps, const float* xt, const float* s0, cons
                         const float* noise, void* out, float* xtn, int B, int C, int HW, int Cp, int mode, void* stream);
 int sidlsg_step_renoise_bwd(const void* g, const float* gxtn, const float* s0, const float* s1, const float* s0n, void* deps,
                             float* dxt, int B, int C, int HW, int Cp, int mode, void* stream);
+/* ddim_step: one step boundary of the teacher's deterministic DDIM sampler (Song et al. 2021, eta = 0) as one launch, forward only.
+ *   eps [dup*B][HW][Ce>=C] fp32 (the teacher's output at t, halves [uncond ; cond] when dup = 2), xt fp32 NCHW (x_t), s0/s1 [B] the
+ *   coefficients sqrt(abar_t) / sqrt(1-abar_t), s0p/s1p [B] those of the previous (smaller) timestep.  All in fp32:
+ *   e = u + kappa*(c-u) when dup = 2, else eps (cfg_x0 mode 0);  x0 by `mode` (1 epsilon, 2 v) as cfg_x0;  eps_hat = e (mode 1) or
+ *   s0*e + s1*x_t (mode 2);  x_prev = s0p*x0 + s1p*eps_hat (noisy_input's expression) -> out NHWC [dup*B][HW][Cp] activations (both
+ *   halves equal, channels C.. zero; NULL on the last step), xtn fp32 NCHW, x0 fp32 NCHW (may be NULL).  In mode 1 the three outputs
+ *   are bit-equal to cfg_x0(mode 1), cfg_x0(mode 0), noisy_input(x0, e, s0p, s1p, dup); in mode 2 x0 is bit-equal to cfg_x0(mode 2).
+ *   dup other than 1 / 2, mode other than 1 / 2, a NULL eps / xt / coefficient / xtn -> SIDLSG_EINVAL, nothing launched. */
+int sidlsg_ddim_step(const float* eps, const float* xt, const float* s0, const float* s1, const float* s0p, const float* s1p,
+                     void* out, float* xtn, float* x0, int B, int C, int HW, int Ce, int Cp, int dup, float kappa, int mode,
+                     void* stream);
 
 /* ---- losses with closed-form gradients (sid_training_loop.py:423-445, 508-530) -------------
  * Per-sample NaN filtering is done in-kernel (a sample containing NaN contributes 0 and gets zero
@@ -413,6 +424,9 @@ int sidlsg_step_renoise_f32(const float* eps, const float* xt, const float* s0, 
                             void* stream);
 int sidlsg_step_renoise_bwd_f32(const void* g, const float* gxtn, const float* s0, const float* s1, const float* s0n, void* deps,
                                 float* dxt, int B, int C, int HW, int Cp, int mode, void* stream);
+int sidlsg_ddim_step_f32(const float* eps, const float* xt, const float* s0, const float* s1, const float* s0p, const float* s1p,
+                         void* out, float* xtn, float* x0, int B, int C, int HW, int Ce, int Cp, int dup, float kappa, int mode,
+                         void* stream);
 int sidlsg_timestep_embed_f32(const long long* t, void* out, int B, int dim, void* stream);
 int sidlsg_silu_fwd_f32(const void* x, void* y, long long n, void* stream);
 int sidlsg_silu_bwd_f32(const void* x, const void* dy, void* dx, long long n, void* stream);

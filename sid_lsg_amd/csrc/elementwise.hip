@@ -162,6 +162,60 @@ __global__ __launch_bounds__(256) void step_renoise_bwd_kernel(const T* __restri
     for (int c = 8; c < Cp; c += 8) zerov8<T>(d0 + c);
 }
 
+// ---- teacher sampler: one step boundary of deterministic DDIM (Song et al. 2021, eta = 0) as one launch ----------------------------
+// eps [dup*B][HW][Ce] fp32 is the teacher's output at t ([uncond ; cond] when dup = 2), xt fp32 NCHW is x_t, s0/s1 the coefficients
+// of t and s0p/s1p those of the previous (smaller) timestep:
+//   e = dup == 2 ? u + kappa*(c - u) : eps                          cfg_x0_kernel<0>
+//   x0 = (x_t - s1*e)/s0 (MODE 1) | s0*x_t - s1*e (MODE 2)            cfg_x0_kernel<MODE>
+//   eps_hat = e (MODE 1) | s0*e + s1*x_t (MODE 2)
+//   x_prev = s0p*x0 + s1p*eps_hat                                     noisy_input_kernel
+// -> out NHWC [dup*B][HW][Cp] of T (both halves equal, channels C.. zero; may be null), xtn fp32 NCHW, x0 fp32 NCHW (may be null).
+// The roundings are spelled out (contraction is off in the body), the ones the compiler chose for the kernels named on the right, so in
+// MODE 1 the three outputs are bit-equal to cfg_x0<1>, cfg_x0<0> and noisy_input launched in turn; eps_hat of MODE 2 is one rounded
+// product and one fma.  VEC: Ce == 8 and eps 16-byte aligned (the network's output), else element loads as cfg_x0_kernel.
+template <typename T, int MODE, bool VEC>
+__global__ __launch_bounds__(256) void ddim_step_kernel(const float* __restrict__ eps, const float* __restrict__ xt,
+                                                        const float* __restrict__ s0, const float* __restrict__ s1,
+                                                        const float* __restrict__ s0p, const float* __restrict__ s1p,
+                                                        T* __restrict__ out, float* __restrict__ xtn, float* __restrict__ x0,
+                                                        int B, int C, int HW, int Ce, int Cp, int dup, float kappa) {
+    // no contraction in this body: every fma below is written as one, every other product and difference is rounded on its own
+    // (__fmul_rn alone does not stop the compiler from folding a product into a neighbouring subtraction)
+#pragma clang fp contract(off)
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;  // over B*HW
+    if (idx >= B * HW) return;
+    const int b = idx / HW, p = idx - b * HW;
+    const float* eu = eps + (size_t)idx * Ce;
+    const float* ec = eps + ((size_t)B * HW + idx) * Ce;
+    float u[8] = {0, 0, 0, 0, 0, 0, 0, 0}, cn[8] = {0, 0, 0, 0, 0, 0, 0, 0}, o[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (VEC) {
+        ldv8<float>(eu, u);
+        if (dup == 2) ldv8<float>(ec, cn);
+    } else {
+        for (int c = 0; c < C; c++) { u[c] = eu[c]; if (dup == 2) cn[c] = ec[c]; }
+    }
+    const float a0 = s0[b], a1 = s1[b], p0 = s0p[b], p1 = s1p[b];
+#pragma unroll
+    for (int c = 0; c < 8; c++) {
+        if (c >= C) break;
+        const size_t i = ((size_t)b * C + c) * HW + p;
+        const float x = xt[i];
+        const float e = dup == 2 ? __builtin_fmaf(kappa, cn[c] - u[c], u[c]) : u[c];
+        const float xh = MODE == 1 ? __builtin_fmaf(-a1, e, x) / a0 : a0 * x - a1 * e;
+        const float eh = MODE == 1 ? e : __builtin_fmaf(a0, e, a1 * x);
+        const float v = __builtin_fmaf(p0, xh, p1 * eh);
+        xtn[i] = v;
+        if (x0) x0[i] = xh;
+        o[c] = v;
+    }
+    if (!out) return;
+    for (int d = 0; d < dup; d++) {
+        T* dst = out + ((size_t)d * B * HW + idx) * Cp;
+        stv8<T>(dst, o);
+        for (int c = 8; c < Cp; c += 8) zerov8<T>(dst + c);
+    }
+}
+
 // ---- timestep embedding: [cos | sin] of t * exp(-ln(1e4) * i/half), [B][dim] ---------------
 template <typename T>
 __global__ void timestep_embed_kernel(const long long* __restrict__ t, T* __restrict__ out, int B, int dim) {
@@ -778,6 +832,23 @@ static int step_renoise_bwd_t(const void* g, const float* gxtn, const float* s0,
     return sidlsg_last_error();
 }
 
+template <typename T>
+static int ddim_step_t(const float* eps, const float* xt, const float* s0, const float* s1, const float* s0p, const float* s1p,
+                       void* out, float* xtn, float* x0, int B, int C, int HW, int Ce, int Cp, int dup, float kappa, int mode,
+                       void* stream) {
+    if (!eps || !xt || !s0 || !s1 || !s0p || !s1p || !xtn || B < 1 || HW < 1 || C < 1 || C > 8 || Ce < C || Cp % 8 || Cp < 8 ||
+        (dup != 1 && dup != 2) || (mode != 1 && mode != 2) || (long long)B * HW > 0x7fffffffLL)
+        return SIDLSG_EINVAL;
+    const dim3 grid = GRID1D((size_t)B * HW, 256);
+    hipStream_t s = (hipStream_t)stream;
+    const bool vec = Ce == 8 && (((uintptr_t)eps) & 15) == 0;
+#define SIDLSG_DDIM(M, V) hipLaunchKernelGGL((ddim_step_kernel<T, M, V>), grid, dim3(256), 0, s, eps, xt, s0, s1, s0p, s1p, (T*)out, xtn, x0, B, C, HW, Ce, Cp, dup, kappa)
+    if (mode == 1) { if (vec) SIDLSG_DDIM(1, true); else SIDLSG_DDIM(1, false); }
+    else { if (vec) SIDLSG_DDIM(2, true); else SIDLSG_DDIM(2, false); }
+#undef SIDLSG_DDIM
+    return sidlsg_last_error();
+}
+
 extern "C" {
 
 int sidlsg_scale_cast_ranges(const void* jobs, int njobs, int nblocks, void* stream) {
@@ -820,6 +891,9 @@ SIDLSG_BOTH(sidlsg_step_renoise, step_renoise_t,
 SIDLSG_BOTH(sidlsg_step_renoise_bwd, step_renoise_bwd_t,
             (const void* g, const float* gxtn, const float* s0, const float* s1, const float* s0n, void* deps, float* dxt, int B, int C, int HW, int Cp, int mode, void* stream),
             (g, gxtn, s0, s1, s0n, deps, dxt, B, C, HW, Cp, mode, stream))
+SIDLSG_BOTH(sidlsg_ddim_step, ddim_step_t,
+            (const float* eps, const float* xt, const float* s0, const float* s1, const float* s0p, const float* s1p, void* out, float* xtn, float* x0, int B, int C, int HW, int Ce, int Cp, int dup, float kappa, int mode, void* stream),
+            (eps, xt, s0, s1, s0p, s1p, out, xtn, x0, B, C, HW, Ce, Cp, dup, kappa, mode, stream))
 SIDLSG_BOTH(sidlsg_timestep_embed, timestep_embed_t, (const long long* t, void* out, int B, int dim, void* stream), (t, out, B, dim, stream))
 SIDLSG_BOTH(sidlsg_silu_fwd, silu_fwd_t, (const void* x, void* y, long long n, void* stream), (x, y, n, stream))
 SIDLSG_BOTH(sidlsg_silu_bwd, silu_bwd_t, (const void* x, const void* dy, void* dx, long long n, void* stream), (x, dy, dx, n, stream))

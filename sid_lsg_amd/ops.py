@@ -1646,6 +1646,29 @@ def step_renoise(eps, xt, s0, s1, s0n, s1n, noise, act_dtype=BF16, prediction_ty
     return _StepRenoise.apply(eps, xt, s0, s1, s0n, s1n, noise, prediction_mode(prediction_type), act_dtype)
 
 
+def ddim_step(eps, xt, s0, s1, s0p, s1p, kappa, act_dtype=BF16, prediction_type='epsilon', last=False, want_x0=False):
+    """One step boundary of the teacher's deterministic DDIM sampler (sidlsg_ddim_step): the teacher's output eps [dup*B,HW,Ce] fp32
+    at t ([uncond ; cond] when dup = 2) and x_t fp32 NCHW -> guided e, x0 prediction, x_prev = s0p*x0 + s1p*eps_hat with the
+    coefficients (s0p, s1p) of the previous timestep.  Returns (next network input NHWC [dup*B,H,W,8] of `act_dtype`, or None when
+    `last`; x_prev fp32 NCHW; the x0 prediction fp32 NCHW, or None unless `want_x0`).  Forward only."""
+    if torch.is_grad_enabled() and any(torch.is_tensor(v) and v.requires_grad for v in (eps, xt, s0, s1, s0p, s1p)):
+        raise RuntimeError('ddim_step is forward only: call it under torch.no_grad() (the teacher sampler is not differentiated)')
+    B, C, H, W = xt.shape
+    if eps.dim() != 3 or eps.shape[1] != H * W or eps.shape[0] not in (B, 2 * B) or eps.shape[2] < C:
+        raise RuntimeError(f'ddim_step: eps {tuple(eps.shape)} does not match x_t {tuple(xt.shape)}')
+    for name, v in (('s0', s0), ('s1', s1), ('s0p', s0p), ('s1p', s1p)):
+        if v.numel() != B:
+            raise RuntimeError(f'ddim_step: {name} has {v.numel()} elements, the batch has {B}')
+    dup = eps.shape[0] // B
+    out = None if last else torch.empty((dup * B, H, W, 8), device=xt.device, dtype=act_dtype)
+    xtn = torch.empty_like(xt)
+    x0 = torch.empty_like(xt) if want_x0 else None
+    _fn('ddim_step', act_dtype)(_p(_chk(eps, F32)), _p(_chk(xt, F32)), _p(_chk(s0, F32)), _p(_chk(s1, F32)), _p(_chk(s0p, F32)),
+                                _p(_chk(s1p, F32)), _p(out), _p(xtn), _p(x0), B, C, H * W, eps.shape[2], 8, dup, float(kappa),
+                                prediction_mode(prediction_type), _s())
+    return out, xtn, x0
+
+
 class _GLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, yr, yf, alpha, scale):

@@ -12,6 +12,8 @@ at every snapshot tick (training/sid_training_loop.py:39-50 setup_snapshot_image
     forked generator state seeded per call, so a grid depends on (weights, n) alone and the caller's RNG stream does not see it.
   * save_png: PIL when present, else a zlib + CRC writer.
 
+  * write_sampled_grid: one grid through any deterministic latent sampler (the teacher's DDIM sampler: `<metric>_teacher.png`).
+
   * write_reals: `reals.png` (sid_training_loop.py:347-350), when the dataset yields pixels (data.ImageCaptionDataset): the first
     gw x gh items of the set, taken cyclically, in range 0..255 through the same grid kernel.
 """
@@ -70,6 +72,22 @@ def render_grid(G, grid, num_steps_eval, *, noise_scheduler, text_encoder, token
             vae.decode_to_grid(x.to(vae.dtype) / vae.config.scaling_factor, out, first, gw)
             first += len(c)
     return out
+
+
+def write_sampled_grid(path, grid, resolution, vae, sample):
+    """One PNG of the grid's (z, prompts) chunks through `sample(z, prompts) -> latents fp32 NCHW` (a deterministic sampler that draws
+    no noise, e.g. sd_util.teacher_sample), decoded straight into the tiles by the grid kernel as render_grid does."""
+    device = grid.z[0].device
+    gw, gh = grid.size
+    out = torch.zeros((gh * resolution, gw * resolution, 3), dtype=torch.uint8, device=device)
+    with torch.no_grad(), torch.cuda.device(device):
+        first = 0
+        for z, c in zip(grid.z, grid.c):
+            x = sample(z, c)
+            vae.decode_to_grid(x.to(vae.dtype) / vae.config.scaling_factor, out, first, gw)
+            first += len(c)
+    save_png(path, out.cpu().numpy())
+    return path
 
 
 def write_reals(out_dir, dataset, size, resolution, device):

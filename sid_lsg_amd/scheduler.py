@@ -27,6 +27,43 @@ def prediction_mode(prediction_type):
     return 1 if prediction_type == 'epsilon' else 2
 
 
+# what SD 1.x / 2.x `scheduler/scheduler_config.json` files say; used for seeded `random:<arch>` networks, which have no such file
+SD_SAMPLING_CONFIG = dict(steps_offset=1, set_alpha_to_one=False, timestep_spacing='leading')
+
+
+def ddim_schedule(scheduler, config_dict, num_inference_steps):
+    """The timesteps and coefficients of an N-step deterministic DDIM sampler, by the index arithmetic of diffusers'
+    DDIMScheduler.set_timesteps / step with timestep_spacing 'leading':
+        ratio = T // N;  t_i = (N-1-i)*ratio + steps_offset;  prev_i = t_i - ratio;
+        abar_prev = alphas_cumprod[prev_i] when prev_i >= 0, else the final value: 1 if set_alpha_to_one else alphas_cumprod[0].
+    `config_dict`: the model's scheduler_config.json (keys steps_offset, default 0; set_alpha_to_one, default true;
+    timestep_spacing, default 'leading'); None = diffusers' defaults.
+    -> (timesteps LongTensor[N], s0, s1, s0p, s1p FloatTensor[N]) on the scheduler's device: sqrt(abar) and sqrt(1-abar) at t_i and
+    at prev_i, fp32, from the scheduler's own fp32 alphas_cumprod.  Raises ValueError naming the key it refuses."""
+    c = dict(config_dict or {})
+    spacing = c.get('timestep_spacing', 'leading')
+    if spacing != 'leading':
+        raise ValueError(f"timestep_spacing={spacing!r}: only 'leading' is reproduced")
+    T = int(scheduler.config.num_train_timesteps)
+    N = int(num_inference_steps)
+    if N < 1:
+        raise ValueError(f'num_inference_steps={N}: expected at least 1')
+    if N > T:
+        raise ValueError(f'num_inference_steps={N}: more than num_train_timesteps={T}')
+    offset = int(c.get('steps_offset', 0))
+    ratio = T // N
+    t0 = (N - 1) * ratio + offset
+    if t0 >= T or offset < 0:
+        raise ValueError(f'steps_offset={offset}: the first timestep {t0} is outside [0, {T}) for num_inference_steps={N}')
+    abar = scheduler.alphas_cumprod
+    t = torch.arange(N - 1, -1, -1, dtype=torch.long, device=abar.device) * ratio + offset
+    prev = t - ratio
+    final = torch.ones((), dtype=abar.dtype, device=abar.device) if c.get('set_alpha_to_one', True) else abar[0]
+    abar_prev = torch.where(prev >= 0, abar[prev.clamp(min=0)], final)
+    abar_t = abar[t]
+    return t, abar_t ** 0.5, (1 - abar_t) ** 0.5, abar_prev ** 0.5, (1 - abar_prev) ** 0.5
+
+
 class DDPMScheduler:
     def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, prediction_type='epsilon',
                  beta_schedule='scaled_linear'):

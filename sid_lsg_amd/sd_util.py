@@ -3,6 +3,8 @@
     sid_sd_sampler   :163-211  one-step (or few-step) generator  z -> x_hat (or decoded images); the N-step training
                                sampler is hip_generate_steps (one sidlsg_step_renoise launch per step boundary)
     sid_sd_denoise   :214-274  add_noise -> (CFG-batched) UNet -> guided eps or x0 prediction
+    teacher_sample   (no counterpart: the reference's tables take the teacher row from diffusers' pipeline)  guided N-step DDIM
+                               sampling of the teacher itself, one sidlsg_ddim_step launch per step boundary
 
 `unet` must be a HipUNet2DCondition (bare or wrapped in DistributedDataParallel, as the reference's loop passes it):
 the whole glue runs as fused HIP kernels (sidlsg_noisy_input / UNet / sidlsg_cfg_x0: no per-sample python loop, no
@@ -15,9 +17,13 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
-from .scheduler import DDPMScheduler
+from .scheduler import SD_SAMPLING_CONFIG, DDPMScheduler, ddim_schedule
 from .text import TEXT_CONFIGS, CLIPBPETokenizer, CLIPTextModel, HashTokenizer
 from .unet import CONFIGS, HipUNet2DCondition
+
+
+TEACHER = 'teacher'                    # value of --network / --network_pkl that stands for the teacher of the model itself
+TEACHER_STEPS, TEACHER_CFG = 50, 7.5   # its default DDIM step count and guidance scale (teacher_sample, both command lines)
 
 
 def _unwrap(net):
@@ -109,23 +115,32 @@ def resolve_scheduler(name):
       * with SIDLSG_ALLOW_RANDOM_INIT=1, the SD 2.x hub ids WITHOUT '-base' (stable-diffusion-2-1, stable-diffusion-2: the 768-v
         checkpoints) -> v-prediction;
       * otherwise today's default (scaled_linear 0.00085..0.012, 1000 steps, epsilon)."""
+    sched, sampling = _resolve_scheduler(str(name))
+    sched.sampling_config = sampling
+    return sched
+
+
+def _resolve_scheduler(name):
+    """-> (DDPMScheduler, sampling config).  The sampling config is what teacher_sample's DDIM schedule reads (steps_offset,
+    set_alpha_to_one, timestep_spacing): the keys of the model's scheduler_config.json when there is one (diffusers' defaults for
+    the absent ones), else the values of the SD 1.x / 2.x files."""
     import json
-    name = str(name)
     if os.path.isdir(name):
         sj = os.path.join(name, 'scheduler', 'scheduler_config.json')
         if os.path.isfile(sj):
             with open(sj) as f:
-                return DDPMScheduler.from_config(json.load(f))
-        return DDPMScheduler()
+                c = json.load(f)
+            return DDPMScheduler.from_config(c), {k: c[k] for k in SD_SAMPLING_CONFIG if k in c}
+        return DDPMScheduler(), dict(SD_SAMPLING_CONFIG)
     n = name.lower()
     if n.startswith('random:'):
         pt = _random_spec(n)[1]
-        return DDPMScheduler(prediction_type=pt or 'epsilon')
+        return DDPMScheduler(prediction_type=pt or 'epsilon'), dict(SD_SAMPLING_CONFIG)
     if os.environ.get('SIDLSG_ALLOW_RANDOM_INIT', '0') == '1':
         base = n.rstrip('/').rsplit('/', 1)[-1]
         if base in ('stable-diffusion-2-1', 'stable-diffusion-2'):
-            return DDPMScheduler(prediction_type='v_prediction')
-    return DDPMScheduler()
+            return DDPMScheduler(prediction_type='v_prediction'), dict(SD_SAMPLING_CONFIG)
+    return DDPMScheduler(), dict(SD_SAMPLING_CONFIG)
 
 
 def check_prediction_type(unet, noise_scheduler):
@@ -336,3 +351,57 @@ def sid_sd_denoise(unet, images, noise, contexts, timesteps, noise_scheduler, te
                                timesteps.contiguous(), cond.to(bf).contiguous(),
                                uncond.to(bf).contiguous() if guided else None, noise_scheduler, guided, act_dtype=bf)
     return hip_denoise(unet, prep, float(guidance_scale), predict_x0)
+
+
+def sampling_config_of(noise_scheduler, schedule_config=None):
+    """The DDIM sampling keys teacher_sample uses: `schedule_config` when given, else what resolve_scheduler attached to the scheduler
+    (an EMPTY dict there means a scheduler_config.json without these keys, i.e. diffusers' defaults), else the SD values."""
+    if schedule_config is not None:
+        return schedule_config
+    found = getattr(noise_scheduler, 'sampling_config', None)
+    return SD_SAMPLING_CONFIG if found is None else found
+
+
+def teacher_sample(unet, latents, contexts, noise_scheduler, text_encoder, tokenizer, resolution, guidance_scale=TEACHER_CFG,
+                   num_inference_steps=TEACHER_STEPS, return_images=False, vae=None, schedule_config=None):
+    """The teacher itself, sampled the way every SiD-LSG table samples it: classifier-free guidance and an N-step deterministic DDIM
+    sampler (Song et al. 2021, eta = 0; diffusers' DDIMScheduler with 'leading' spacing).  x_T = latents (DDIM's init_noise_sigma is
+    1); per step one UNet pass on the stacked [uncond ; cond] batch (unconditional prompt '', as sid_sd_denoise) and one
+    sidlsg_ddim_step launch; guidance_scale == 1 makes no unconditional pass.  Timesteps and coefficients are device tensors indexed
+    by the step number: the loop issues device work only.  `schedule_config`: the sampling keys of the model's scheduler_config.json
+    (scheduler.ddim_schedule); None = what resolve_scheduler found for the model, else the SD values (sampling_config_of).
+    `resolution` is accepted for the signature of the other samplers and not used: the size is the latents'.  The scheduler is not
+    moved: the N-entry tables are built where it lives and copied to the latents' device before the loop.
+    -> the final latent x_0 fp32 NCHW, or (return_images) the decoded images as sid_sd_sampler returns them."""
+    _require_hip(unet)
+    check_prediction_type(unet, noise_scheduler)
+    net = _unwrap(unet)
+    dt, pt = net.compute_dtype, noise_scheduler.config.prediction_type
+    schedule_config = sampling_config_of(noise_scheduler, schedule_config)
+    with torch.no_grad():
+        z = latents.to(torch.float32).contiguous()
+        b, dev = z.shape[0], z.device
+        ts, s0, s1, s0p, s1p = (v.to(dev) for v in ddim_schedule(noise_scheduler, schedule_config, num_inference_steps))
+        n = ts.numel()
+        guided = guidance_scale != 1
+        dup = 2 if guided else 1
+        ctx = encode_contexts(contexts, text_encoder, tokenizer, dev).to(dt)
+        if guided:
+            ctx = torch.cat([encode_contexts([''] * b, text_encoder, tokenizer, dev).to(dt), ctx])
+        ctx = ctx.contiguous()
+        tt = ts[:, None].expand(n, dup * b).contiguous()
+        s0, s1, s0p, s1p = (v.to(torch.float32)[:, None].expand(n, b).contiguous() for v in (s0, s1, s0p, s1p))
+        ones = torch.ones(b, device=dev, dtype=torch.float32)
+        xin, xt = ops.noisy_input(None, z, ones, ones, dup, dt)          # x_T = z, as the [uncond ; cond] NHWC batch
+        for i in range(n):
+            eps = net.forward_nhwc(xin, tt[i], ctx)
+            xin, xt, _ = ops.ddim_step(eps, xt, s0[i], s1[i], s0p[i], s1p[i], guidance_scale, dt, prediction_type=pt, last=i == n - 1)
+        if not return_images:
+            return xt
+        upcast = vae.dtype == torch.float16 and getattr(vae.config, 'force_upcast', False)
+        if upcast:
+            vae.to(dtype=torch.float32)
+        images = vae.decode(xt.to(vae.dtype) / vae.config.scaling_factor, return_dict=False)[0]
+        if upcast:
+            vae.to(dtype=torch.float16)
+        return images.to(torch.float32)

@@ -38,7 +38,7 @@ from . import ops
 from .data import InfiniteSampler, prompt_batches
 from .dnnlib_util import EasyDict, construct_class_by_name, format_time
 from .distributed import FlatGradReducer
-from .sd_util import check_prediction_type, load_sd15, resolve_compute_dtype
+from .sd_util import TEACHER, TEACHER_CFG, TEACHER_STEPS, check_prediction_type, load_sd15, resolve_compute_dtype
 from .sid_step import SiDStep
 from .text import TextConditioner
 
@@ -125,7 +125,16 @@ def training_loop(
     dataset_prompt_text_kwargs={}, cfg_train_fake=1, cfg_eval_fake=1, cfg_eval_real=1, num_steps=1, train_mode=True,
     network_pkl=None, enable_xformers=True, gradient_checkpointing=False, resolution=512, on_iteration=None,
     rng_device=None, metric_real_stats=None, metric_num_test=None, deterministic=False, snapshot_images=False,
+    teacher_steps=None, teacher_cfg=None,
 ):
+    if not train_mode and network_pkl == TEACHER:
+        return evaluate_teacher(run_dir=run_dir, dataset_kwargs=dataset_kwargs, network_kwargs=network_kwargs, device=device, metrics=metrics,
+                                init_timestep=init_timestep, metric_pt_path=metric_pt_path, metric_open_clip_path=metric_open_clip_path,
+                                pretrained_model_name_or_path=pretrained_model_name_or_path, resolution=resolution,
+                                teacher_steps=TEACHER_STEPS if teacher_steps is None else teacher_steps,
+                                teacher_cfg=TEACHER_CFG if teacher_cfg is None else teacher_cfg, metric_real_stats=metric_real_stats,
+                                metric_num_test=metric_num_test, dataset_prompt_text_kwargs=dataset_prompt_text_kwargs,
+                                snapshot_images=snapshot_images, batch_size=batch_size, batch_gpu=batch_gpu)
     if not train_mode:
         return evaluate_network(run_dir=run_dir, dataset_kwargs=dataset_kwargs, network_kwargs=network_kwargs, device=device, metrics=metrics,
                                 init_timestep=init_timestep, metric_pt_path=metric_pt_path, metric_open_clip_path=metric_open_clip_path,
@@ -388,6 +397,30 @@ def training_loop(
     return dict(G=G, fake_score=fake_score, G_ema=G_ema)
 
 
+def _evaluation_prompts(dataset_kwargs, dataset_prompt_text_kwargs, who):
+    """The prompt source of an evaluation run as calc_metric takes it: the caption set of --data, else the training prompts."""
+    if dataset_kwargs:
+        return dict(dataset_kwargs=dict(dataset_kwargs))
+    if not dataset_prompt_text_kwargs:
+        raise ValueError(f'{who}: neither dataset_kwargs (--data: the evaluation caption set) nor dataset_prompt_text_kwargs '
+                         '(--data_prompt_text) was given -- there are no prompts to evaluate on')
+    dist.print0('WARNING: no dataset_kwargs (--data): evaluating on the training prompts; not comparable with the reference\'s COCO numbers')
+    return dict(dataset_kwargs=dict(dataset_prompt_text_kwargs))
+
+
+def _evaluation_grid(msrc, vae, resolution, batch_size, batch_gpu, run_dir, device):
+    """The preview grid of an evaluation run (rank 0, snapshot_images): its prompts and latents; creates run_dir and writes reals.png
+    when the set has pixels."""
+    from . import preview
+    lat = resolution // (2 ** (len(vae.config.block_out_channels) - 1))
+    grid_set = construct_class_by_name(**msrc['dataset_kwargs'])
+    grid = preview.setup_snapshot_grid(grid_set, resolution, batch_gpu or max(batch_size // dist.get_world_size(), 1), (4, lat, lat), device)
+    os.makedirs(run_dir, exist_ok=True)
+    if getattr(grid_set, 'has_images', False):
+        preview.write_reals(run_dir, grid_set, grid.size, resolution, device)
+    return grid
+
+
 def evaluate_network(run_dir, dataset_kwargs, network_kwargs, device, metrics, init_timestep, metric_pt_path, metric_open_clip_path,
                      pretrained_model_name_or_path, network_pkl, resolution, num_steps=1, metric_real_stats=None, metric_num_test=None,
                      dataset_prompt_text_kwargs=None, snapshot_images=False, batch_size=512, batch_gpu=None):
@@ -416,25 +449,13 @@ def evaluate_network(run_dir, dataset_kwargs, network_kwargs, device, metrics, i
     G_ema.eval().requires_grad_(False)
     m = re.search(r'-(\d+)\.pkl$', network_pkl)
     number_part = m.group(1) if m else '_final'
-    if dataset_kwargs:
-        msrc = dict(dataset_kwargs=dict(dataset_kwargs))
-    else:
-        if not dataset_prompt_text_kwargs:
-            raise ValueError('evaluate_network: neither dataset_kwargs (--data: the evaluation caption set) nor dataset_prompt_text_kwargs '
-                             '(--data_prompt_text) was given -- there are no prompts to evaluate on')
-        dist.print0('WARNING: no dataset_kwargs (--data): evaluating on the training prompts; not comparable with the reference\'s COCO numbers')
-        msrc = dict(dataset_kwargs=dict(dataset_prompt_text_kwargs))
+    msrc = _evaluation_prompts(dataset_kwargs, dataset_prompt_text_kwargs, 'evaluate_network')
     grid = None
     if snapshot_images and dist.get_rank() == 0 and run_dir:
         from . import preview
-        lat = resolution // (2 ** (len(vae.config.block_out_channels) - 1))
-        grid_set = construct_class_by_name(**msrc['dataset_kwargs'])
-        grid = preview.setup_snapshot_grid(grid_set, resolution, batch_gpu or max(batch_size // dist.get_world_size(), 1), (4, lat, lat), device)
+        grid = _evaluation_grid(msrc, vae, resolution, batch_size, batch_gpu, run_dir, device)
         for c in grid.c:
             dist.print0(c)
-        os.makedirs(run_dir, exist_ok=True)
-        if getattr(grid_set, 'has_images', False):
-            preview.write_reals(run_dir, grid_set, grid.size, resolution, device)
     out = {}
     for num_steps_eval in (1, 2, 4):
         for metric in metrics:
@@ -457,6 +478,55 @@ def evaluate_network(run_dir, dataset_kwargs, network_kwargs, device, metrics, i
                 with open(txt, 'w') as f:                          # save_metric (sid_training_loop.py:134-137)
                     for k, v in result.items():
                         f.write(f'{k}: {v}\n')
+    return out
+
+
+def evaluate_teacher(run_dir, dataset_kwargs, network_kwargs, device, metrics, init_timestep, metric_pt_path, metric_open_clip_path,
+                     pretrained_model_name_or_path, resolution, teacher_steps=TEACHER_STEPS, teacher_cfg=TEACHER_CFG, metric_real_stats=None,
+                     metric_num_test=None, dataset_prompt_text_kwargs=None, snapshot_images=False, batch_size=512, batch_gpu=None):
+    """`--train_mode 0 --network_pkl teacher`: the teacher row of the tables under this project's own protocol.  The UNet of the model
+    is sampled with classifier-free guidance `teacher_cfg` and a `teacher_steps`-step deterministic DDIM sampler
+    (sd_util.teacher_sample) as the `G` of every metric -- the same prompts, seeds, VAE, detector resize and metric code as a
+    distilled generator gets from evaluate_network.  Evaluated ONCE (there is no 1 / 2 / 4 loop: the step count is teacher_steps);
+    each result is reported through report_metric (`metric-<name>.jsonl` in run_dir) with snapshot_pkl
+    `teacher-ddim<steps>-cfg<scale>`.  snapshot_images=True also writes one preview grid `<run_dir>/<metric>_teacher.png` per metric."""
+    from functools import partial
+
+    from . import metrics as metric_main
+    from .sd_util import teacher_sample
+    if not metrics:
+        raise ValueError('--train_mode 0 evaluates metrics: pass --metrics')
+    dtype = resolve_compute_dtype(dict(network_kwargs).get('compute_dtype'))
+    unet, vae, noise_scheduler, text_encoder, tokenizer = load_sd15(
+        pretrained_model_name_or_path=pretrained_model_name_or_path, pretrained_vae_model_name_or_path=None, device=device,
+        weight_dtype=dtype, lora_config=None, compute_dtype=dtype)
+    unet.eval().requires_grad_(False)
+    dist.print0('Loading network completed')
+    tag = f'teacher-ddim{int(teacher_steps):d}-cfg{float(teacher_cfg):g}'
+    dist.print0(f'Evaluating the teacher "{pretrained_model_name_or_path}": DDIM {int(teacher_steps)} steps, guidance scale {float(teacher_cfg):g}')
+    msrc = _evaluation_prompts(dataset_kwargs, dataset_prompt_text_kwargs, 'evaluate_teacher')
+    sample = partial(teacher_sample, unet=unet, noise_scheduler=noise_scheduler, text_encoder=text_encoder, tokenizer=tokenizer,
+                     resolution=resolution, guidance_scale=float(teacher_cfg), num_inference_steps=int(teacher_steps), vae=vae)
+
+    def G_eval(latents, contexts, init_timesteps=None):      # (the metrics pass init_timesteps to every G; DDIM starts at its own t_0)
+        return sample(latents=latents, contexts=contexts, return_images=True)
+    if run_dir and dist.get_rank() == 0:
+        os.makedirs(run_dir, exist_ok=True)
+    grid = None
+    if snapshot_images and dist.get_rank() == 0 and run_dir:
+        from . import preview
+        grid = _evaluation_grid(msrc, vae, resolution, batch_size, batch_gpu, run_dir, device)
+    out = {}
+    for metric in metrics:
+        if grid is not None:
+            preview.write_sampled_grid(os.path.join(run_dir, f'{metric}_teacher.png'), grid, resolution, vae,
+                                       lambda z, c: sample(latents=z, contexts=c, return_images=False))
+        extra = dict(num_test=metric_num_test) if metric_num_test is not None else {}
+        result = metric_main.calc_metric(metric, G=G_eval, resolution=resolution, init_timestep=init_timestep, detector=metric_pt_path,
+                                         real_stats=metric_real_stats, open_clip_detector=metric_open_clip_path, device=device,
+                                         run_dir=run_dir, **msrc, **extra)
+        metric_main.report_metric(result, run_dir=run_dir, snapshot_pkl=os.path.join(run_dir, tag) if run_dir else tag)
+        out[metric] = result
     return out
 
 

@@ -20,6 +20,8 @@ Differences (documented, not silent):
     the real-set statistics come from --data_stat or, when --data is an image directory, from the images themselves (cached as
     <run_dir>/real_stats.npz); pr30k3_full / pr_test (precision / recall) always read the images;
     `--train_mode 0 --network_pkl <snapshot>` evaluates a snapshot (1 / 2 / 4 steps);
+    `--train_mode 0 --network_pkl teacher` (added value) evaluates the teacher of --sd_model itself, once, under classifier-free
+    guidance `--teacher_cfg` and a `--teacher_steps`-step deterministic DDIM sampler (sid_lsg_amd.sd_util.teacher_sample);
   * `--data` is optional (it is the COCO image set used only by the metrics and by reals.png).
 """
 import json
@@ -33,7 +35,7 @@ import torch  # noqa: E402
 
 from sid_lsg_amd import distributed as dist  # noqa: E402
 from sid_lsg_amd.dnnlib_util import EasyDict, construct_class_by_name  # noqa: E402
-from sid_lsg_amd.sd_util import resolve_scheduler  # noqa: E402
+from sid_lsg_amd.sd_util import TEACHER, TEACHER_CFG, TEACHER_STEPS, resolve_scheduler  # noqa: E402
 from sid_lsg_amd.training_loop import training_loop  # noqa: E402
 
 
@@ -83,7 +85,9 @@ OPTIONS = [
     (('--lr',), dict(type=click.FloatRange(min=0, min_open=True), default=1e-6, show_default=True, help='Fake-score learning rate')),
     (('--glr',), dict(type=click.FloatRange(min=0, min_open=True), default=1e-6, show_default=True, help='Generator learning rate')),
     (('--train_mode',), dict(type=bool, default=True, show_default=True, help='Distill (True) or evaluate the metrics of --network_pkl with 1 / 2 / 4 generation steps (False)')),
-    (('--network_pkl',), dict(type=str, default=None, help='network-snapshot-*.pkl to evaluate with --train_mode 0')),
+    (('--network_pkl',), dict(type=str, default=None, help='network-snapshot-*.pkl to evaluate with --train_mode 0, or "teacher": the teacher of --sd_model itself')),
+    (('--teacher_steps',), dict(type=int, default=None, metavar='INT', help=f'DDIM steps of --network_pkl teacher  [default: {TEACHER_STEPS}] (not a reference option)')),
+    (('--teacher_cfg',), dict(type=float, default=None, help=f'Guidance scale of --network_pkl teacher  [default: {TEACHER_CFG}] (not a reference option)')),
     (('--cfg_train_fake',), dict(type=float, default=1, show_default=True, help='kappa1: guidance scale when training the fake score')),
     (('--cfg_eval_fake',), dict(type=float, default=1, show_default=True, help='kappa2 = kappa3: guidance scale when evaluating the fake score')),
     (('--cfg_eval_real',), dict(type=float, default=1, show_default=True, help='kappa4: guidance scale when evaluating the teacher')),
@@ -131,8 +135,12 @@ def build_config(o):
     if not o.train_mode:
         if o.metrics is None:
             raise click.ClickException('--train_mode 0 evaluates a network snapshot: --metrics is required')
-        if not o.network_pkl or not os.path.isfile(o.network_pkl):
+        if o.network_pkl != TEACHER and (not o.network_pkl or not os.path.isfile(o.network_pkl)):
             raise click.ClickException(f'--train_mode 0 needs --network_pkl to be a local network-snapshot-*.pkl (got {o.network_pkl!r})')
+    teacher = not o.train_mode and o.network_pkl == TEACHER
+    given = [f'--{k}' for k in ('teacher_steps', 'teacher_cfg') if o.get(k) is not None]
+    if given and not teacher:
+        raise click.ClickException(f'{" / ".join(given)} apply to --train_mode 0 --network_pkl {TEACHER} only')
     c.metrics, c.resolution = o.metrics, o.resolution
     c.metric_real_stats = o.data_stat
     if o.metrics is not None and o.data:
@@ -169,6 +177,12 @@ def build_config(o):
              gradient_checkpointing=o.gradient_checkpointing, pretrained_model_name_or_path=o.sd_model,
              pretrained_vae_model_name_or_path=o.sd_model, metric_pt_path=o.metric_pt_path,
              metric_open_clip_path=o.metric_open_clip_path, metric_clip_path=o.metric_clip_path)
+    if teacher:      # (absent otherwise: the printed options of every other run stay as they were)
+        T = resolve_scheduler(o.sd_model).config.num_train_timesteps
+        c.teacher_steps = TEACHER_STEPS if o.get('teacher_steps') is None else int(o.teacher_steps)
+        c.teacher_cfg = TEACHER_CFG if o.get('teacher_cfg') is None else float(o.teacher_cfg)
+        if not 1 <= c.teacher_steps <= T:
+            raise click.ClickException(f'--teacher_steps {c.teacher_steps}: expected 1 .. {T} (num_train_timesteps of --sd_model)')
     if o.transfer is not None:
         c.resume_pkl = o.transfer
     if o.resume is not None:

@@ -1,0 +1,90 @@
+#!/usr/bin/env python
+"""Cost of sampling the teacher (sd_util.teacher_sample) and of its step-boundary kernel.
+    python tools/teacher_sampler_cost.py
+(a) sidlsg_ddim_step against the three launches it replaces (cfg_x0 mode 1, cfg_x0 mode 0, noisy_input) at B = 8, 64 x 64 latents,
+    [uncond ; cond] input, bf16 activations: device events around windows of 200 back-to-back calls after 20 warm-up calls, five
+    windows per variant, the two variants alternating; the median and the range.  Back-to-back launches of a ~4 MB kernel measure
+    launch throughput as much as the kernel, which is what the sampler loop sees.
+(b) images/s of teacher_sample at SD1.5 size with seeded weights (random:sd15), 50 steps, kappa = 7.5, batch 8, 512 x 512, with and
+    without the VAE decode: host clock around a call that ends in torch.cuda.synchronize, one warm-up call, three timed calls."""
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from sid_lsg_amd import ops  # noqa: E402
+from sid_lsg_amd.scheduler import DDPMScheduler  # noqa: E402
+from sid_lsg_amd.sd_util import load_sd15, teacher_sample  # noqa: E402
+
+dev = torch.device('cuda:0')
+BF16 = torch.bfloat16
+print(f'device: {torch.cuda.get_device_name(0)}', flush=True)
+
+# ---- (a) the step-boundary kernel ----
+B, lat, kappa = 8, 64, 7.5
+g = torch.Generator().manual_seed(0)
+eps = torch.randn(2 * B, lat * lat, 8, generator=g).to(dev)
+xt = torch.randn(B, 4, lat, lat, generator=g).to(dev)
+sched = DDPMScheduler().to(dev)
+t = torch.full((B,), 501, dtype=torch.long, device=dev)
+s0, s1 = sched.coefficients(t)
+s0p, s1p = sched.coefficients(t - 20)
+
+
+def fused():
+    return ops.ddim_step(eps, xt, s0, s1, s0p, s1p, kappa, BF16)
+
+
+def chain():
+    x0 = ops.cfg_x0(eps, xt, s0, s1, kappa, True, BF16)
+    e = ops.cfg_x0(eps, xt, s0, s1, kappa, False, BF16)
+    return ops.noisy_input(x0, e, s0p, s1p, 2, BF16)
+
+
+def window_us(fn, calls=200):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(calls):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1000.0 / calls
+
+
+moved = eps.numel() * 4 + 2 * xt.numel() * 4 + 2 * B * lat * lat * 8 * 2
+variants = (('ddim_step (1 launch)', fused), ('cfg_x0 x0 + cfg_x0 raw + noisy_input (3 launches)', chain))
+with torch.no_grad():
+    for _, fn in variants:
+        for _ in range(20):
+            fn()
+    torch.cuda.synchronize()
+    samples = {name: [] for name, _ in variants}
+    for _ in range(5):                      # the two variants alternate inside one process
+        for name, fn in variants:
+            samples[name].append(window_us(fn))
+for name, v in samples.items():
+    print(f'(a) {name}: {statistics.median(v):.1f} us per step boundary (median of 5 windows of 200 back-to-back calls, alternating with the '
+          f'other variant; range {min(v):.1f} .. {max(v):.1f}); B = {B}, {lat} x {lat} latents, dup 2, bf16', flush=True)
+print(f'    the fused kernel reads and writes {moved / 1e6:.2f} MB per launch', flush=True)
+
+# ---- (b) the sampler ----
+res, steps = 512, 50
+unet, vae, sched, te, tok = load_sd15('random:sd15', None, dev, BF16)
+unet.eval().requires_grad_(False)
+prompts = [f'a photo of object number {i} on a table, studio light' for i in range(B)]
+z = torch.randn(B, 4, res // 8, res // 8, generator=g).to(dev)
+for decode in (False, True):
+    times = []
+    for rep in range(4):
+        torch.cuda.synchronize()
+        t0 = time.time()
+        teacher_sample(unet, z, prompts, sched, te, tok, res, guidance_scale=kappa, num_inference_steps=steps, return_images=decode, vae=vae)
+        torch.cuda.synchronize()
+        if rep:
+            times.append(time.time() - t0)
+    med = statistics.median(times)
+    print(f'(b) teacher_sample, random:sd15, {res} x {res}, batch {B}, {steps} steps, kappa {kappa}, {"with" if decode else "without"} VAE decode: '
+          f'{B / med:.2f} images/s ({med:.2f} s per batch, median of 3 after one warm-up call; {min(times):.2f} .. {max(times):.2f} s)', flush=True)
