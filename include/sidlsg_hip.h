@@ -340,6 +340,28 @@ int sidlsg_pr_member(const void* probes, int P, const void* manifold, int N, int
 int sidlsg_image_grid_u8(const float* src, void* grid, int B, int H, int W, int layout, int first, int gw, int gh, float lo, float hi,
                          void* stream);
 
+/* ---- CLIP image tower (networks/clip.py; the ViT itself runs on the GEMM / LayerNorm / attention entry points above) ----------
+ * sidlsg_clip_patches_u8(_f32): the wrapper's preprocessing (networks/clip.py:33-37) in one launch.  images: uint8 [B][3][H][W]
+ *   (H and W may differ).  In fp32, exactly: v = x / 255; bicubic resampling to R x R with F.interpolate(mode='bicubic',
+ *   align_corners=False) semantics (A = -0.75, source coordinate (dst + 0.5) * in / out - 0.5, tap indices clamped to the border, no
+ *   antialiasing, overshoot not clamped); (v - mean_c) / std_c.  out: bf16 (_f32: fp32) [B * (1 + (R/P)^2)][Kp], the A operand of
+ *   the patch-embedding GEMM: one row per token slot, column (c * P + py) * P + px (the flattened patch_embedding.weight); columns
+ *   3*P*P .. Kp - 1 and the whole class-token row (row 0 of every image) are written as zeros, so ONE GEMM whose res operand holds
+ *   the position embeddings (class embedding added into row 0) yields the token tensor.  R % P == 0, Kp % 8 == 0, Kp >= 3*P*P, out
+ *   16-byte aligned, std != 0, fewer than 2^31 input bytes and output elements; SIDLSG_EINVAL and no launch otherwise.
+ * sidlsg_gelu(_f32): y = act(x) on n bf16 (fp32) elements, evaluated in fp32.  mode 0: quick_gelu x * sigmoid(1.702 x) (OpenAI
+ *   checkpoints); mode 1: the exact GELU x * Phi(x) (open_clip ViT-H / ViT-g), as 0.5 x erfc(-x / sqrt 2).  x, y 16-byte aligned; any n.
+ * sidlsg_clip_score: img, txt [B][F] bf16 (f32_in != 0: fp32) -> feats [B][2F] fp32 = F.normalize(img) | F.normalize(txt) (x /
+ *   max(|x|_2, 1e-12): the wrapper's return value, :39-53) and cosine [B] fp32, the dot product of the two halves.  One wave per
+ *   row, fp32 accumulation. */
+int sidlsg_clip_patches_u8(const void* images, void* out, int B, int H, int W, int R, int P, int Kp, float mean0, float mean1, float mean2,
+                           float std0, float std1, float std2, void* stream);
+int sidlsg_clip_patches_u8_f32(const void* images, void* out, int B, int H, int W, int R, int P, int Kp, float mean0, float mean1,
+                               float mean2, float std0, float std1, float std2, void* stream);
+int sidlsg_gelu(const void* x, void* y, long long n, int mode, void* stream);
+int sidlsg_gelu_f32(const void* x, void* y, long long n, int mode, void* stream);
+int sidlsg_clip_score(const void* img, const void* txt, int f32_in, float* feats, float* cosine, int B, int F, void* stream);
+
 /* ---- reference plugin op: torch_utils/ops/bias_act.cpp:32 `bias_act(x,b,xref,yref,dy,grad,dim,act,alpha,gain,clamp)`
  * act: 1 linear 2 relu 3 lrelu 4 tanh 5 sigmoid 6 elu 7 selu 8 softplus 9 swish (bias_act.py:23-33).
  * grad 0: out = clamp(act(x + b[(i/stepB)%sizeB]) * gain); grad 1: out = dL/dx from dy (x, b = saved inputs).

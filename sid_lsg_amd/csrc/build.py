@@ -6,14 +6,16 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
-SOURCES = ['gemm.hip', 'norm.hip', 'attention.hip', 'elementwise.hip', 'optim.hip', 'fp32.hip', 'trace.hip', 'image_grid.hip', 'pr_dist.hip']
+SOURCES = ['gemm.hip', 'norm.hip', 'attention.hip', 'elementwise.hip', 'optim.hip', 'fp32.hip', 'trace.hip', 'image_grid.hip', 'pr_dist.hip', 'clip.hip']
 LIB = os.path.join(PKG, 'libsidlsg_hip.so')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-munsafe-fp-atomics', '-Wno-unused-result']
 # Per-file extras.  attention.hip: the softmax works on MFMA results with VALU ops; with the default heuristics the
 # accumulators live in AGPRs and every tile pays ~110 v_accvgpr_read/write moves in a VALU-bound loop.
 # -fno-honor-nans: no canonicalising v_max x,x in front of every fmaxf on an MFMA result (infinities stay honoured).
 # image_grid.hip: the preview grid's uint8 conversion is specified rounding by rounding (subtract, multiply, round to even).
-EXTRA = {'attention.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form', '-fno-honor-nans'], 'image_grid.hip': ['-ffp-contract=off']}
+# clip.hip: likewise the CLIP preprocessing (divide, bicubic taps, normalise): its result must not depend on compiler fusion.
+EXTRA = {'attention.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form', '-fno-honor-nans'], 'image_grid.hip': ['-ffp-contract=off'],
+         'clip.hip': ['-ffp-contract=off']}
 
 
 def digest():

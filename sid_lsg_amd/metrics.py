@@ -4,7 +4,8 @@ Reference: metrics/sid_metric_main.py:25-123 (registry, `calc_metric`, `report_m
 `fid_clip_30k_full` / `fid_test` / `fid_clip_test` entries), metrics/sid_fid_and_clip.py:32-74 (the Frechet distance between
 the Inception feature statistics of generated images and of the real set), metrics/sid_metric_utils.py:112-188
 (`FeatureStats`) and :412-510 (the generation loop: prompts through the InfiniteSampler, z ~ N(0, I) at resolution / 8,
-uint8 images, 256 x 256 PIL-LANCZOS resize for the detector (reproduced bit for bit on the GPU); the CLIP score is the mean cosine of the detector's image | text halves).
+uint8 images, 256 x 256 PIL-LANCZOS resize for the detector (reproduced bit for bit on the GPU); the CLIP score is the mean cosine of the detector's image | text halves;
+a CLIP directory in the Hugging Face layout is scored by sid_lsg_amd.clip: the ViT image tower on the HIP kernels).
 
 What is different here (not a translation):
   * the feature statistics live ON THE GPU in fp64 (`FeatureStats.raw_mean / raw_cov` are device tensors; x^T x is one
@@ -145,12 +146,22 @@ def clip_score_from_features(features):
 
 
 # ------------------------------------------------------------------------------------------------
+def is_clip_spec(path):
+    """A CLIP model this package builds itself: a local directory in the Hugging Face layout (config.json, model.safetensors,
+    vocab.json, merges.txt) or 'random:clip-<arch>' (sid_lsg_amd.clip)."""
+    return isinstance(path, (str, os.PathLike)) and (str(path).lower().startswith('random:clip-') or os.path.isfile(os.path.join(str(path), 'config.json')))
+
+
 def load_detector(path, device):
     """A feature detector file of the reference's kinds: TorchScript (`inception-2015-12-05.pt`, called as
     `detector(uint8 NCHW images, return_features=True)`) or a pickled module (open_clip / CLIP wrappers, called with
-    `texts=..., div255=True`).  Offline there are none: callers may pass any callable instead."""
+    `texts=..., div255=True`).  Offline there are none: callers may pass any callable instead.  A CLIP directory (is_clip_spec) gives
+    a `clip.HipCLIPDetector` with the wrappers' call contract: the image tower on the HIP kernels."""
     if callable(path):
         return path
+    if is_clip_spec(path):
+        from .clip import load_clip
+        return load_clip(path, device)
     if not path or not os.path.isfile(path):
         raise FileNotFoundError(f'feature detector {path!r} not found: FID / CLIP metrics need the Inception / CLIP files the reference '
                                 'downloads (metrics/sid_fid_and_clip.py:36, sid_metric_utils.py:456); pass a local file or a callable')
@@ -236,7 +247,7 @@ class MetricOptions:
 
     def __init__(self, G, prompts=None, resolution=512, init_timestep=625, detector=None, real_stats=None, open_clip_detector=None,
                  clip_score_fn=None, device=None, seed=0, batch_gen=4, detector_size=256, progress=None, dataset_kwargs=None,
-                 dataset=None, run_dir=None):
+                 dataset=None, run_dir=None, metric_clip_path=None):
         from .dnnlib_util import construct_class_by_name
         self.run_dir = run_dir
         if dataset is None and dataset_kwargs:
@@ -248,9 +259,22 @@ class MetricOptions:
         self.dataset = dataset
         self.G, self.resolution, self.init_timestep = G, resolution, init_timestep
         self.detector, self.real_stats, self.open_clip_detector, self.clip_score_fn = detector, real_stats, open_clip_detector, clip_score_fn
+        self.metric_clip_path = metric_clip_path        # --metric_clip_path: the detector behind `clipscore30k` when clip_score_fn is None
         self.device = torch.device(device if device is not None else 'cuda')
         self.seed, self.batch_gen, self.detector_size, self.progress = seed, batch_gen, detector_size, progress
         self.rank, self.num_gpus = dist.get_rank(), dist.get_world_size()
+
+
+def row_cosines(detector):
+    """`clip_score_fn(images_u8, texts) -> [B]` of a CLIP detector: its own `scores` (HipCLIPDetector), else the row dot product
+    of the image | text halves it returns."""
+    if hasattr(detector, 'scores'):
+        return detector.scores
+
+    def fn(images, texts):
+        img, txt = torch.as_tensor(detector(images, texts=texts, div255=True)).float().chunk(2, 1)
+        return (img * txt).sum(-1)
+    return fn
 
 
 def _caption(dataset, i):
@@ -302,6 +326,11 @@ def generator_feature_stats(opts, num_gen, compute_clip=False, capture_all=False
     order = iter(InfiniteSampler(opts.dataset, rank=opts.rank, num_replicas=opts.num_gpus, seed=0))
     detector = load_detector(opts.detector, opts.device)
     oc = load_detector(opts.open_clip_detector, opts.device) if (compute_clip and opts.open_clip_detector is not None) else None
+    clip_score_fn = opts.clip_score_fn if compute_clip else None
+    if compute_clip and clip_score_fn is None and opts.metric_clip_path is not None:
+        # each detector is loaded once per metric call; one model given under both names is loaded once
+        same = oc is not None and isinstance(opts.open_clip_detector, str) and opts.open_clip_detector == opts.metric_clip_path
+        clip_score_fn = row_cosines(oc if same else load_detector(opts.metric_clip_path, opts.device))
     stats = FeatureStats(capture_mean_cov=not capture_all, capture_all=capture_all, keep_on_device=capture_all, max_items=None, device=opts.device)
     gen = torch.Generator(device=opts.device).manual_seed(opts.seed * opts.num_gpus + opts.rank)
     lat = opts.resolution // 8
@@ -320,8 +349,8 @@ def generator_feature_stats(opts, num_gen, compute_clip=False, capture_all=False
         with torch.no_grad():
             stats.append(detector(img, return_features=True))
             if compute_clip:
-                if opts.clip_score_fn is not None:
-                    clip_scores.append(torch.as_tensor(opts.clip_score_fn(img, texts)).float().flatten().cpu())
+                if clip_score_fn is not None:
+                    clip_scores.append(torch.as_tensor(clip_score_fn(img, texts)).float().flatten().cpu())
                 if oc is not None:
                     oc_scores.append(torch.tensor([clip_score_from_features(oc(img, texts=texts, div255=True))] * len(idx)))
         if opts.progress is not None:

@@ -1888,6 +1888,59 @@ def image_grid_u8(images, grid, first, gw, drange=(-1, 1), layout='nchw'):
     return grid
 
 
+CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)      # the OpenAI constants the reference wrapper normalises with (networks/clip.py:26)
+CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
+
+
+def clip_patch_width(patch):
+    """Kp: 3 * patch^2 rounded up to the multiple of 8 the GEMMs take as K (588 -> 592 for patch 14)."""
+    return (3 * patch * patch + 7) // 8 * 8
+
+
+def clip_patches(images_u8, size, patch, dtype=BF16, mean=CLIP_MEAN, std=CLIP_STD):
+    """uint8 NCHW [B, 3, H, W] -> [B * (1 + (size / patch)^2), Kp] `dtype`: x / 255, bicubic resampling to size x size
+    (F.interpolate(mode='bicubic', align_corners=False)), (v - mean) / std, unfolded into patch rows in (c, py, px) column order
+    with a zero class-token row in front of every image and zero pad columns (sidlsg_clip_patches_u8): the A operand of the
+    patch-embedding GEMM (networks/clip.py:33-37 in one launch)."""
+    if images_u8.dim() != 4 or images_u8.shape[1] != 3:
+        raise RuntimeError(f'clip_patches: expected uint8 [B, 3, H, W] images, got {tuple(images_u8.shape)}')
+    if dtype not in (BF16, F32):
+        raise RuntimeError(f'clip_patches: output dtype {dtype}: expected bf16 or fp32')
+    if size % patch:
+        raise RuntimeError(f'clip_patches: image size {size} is not a multiple of the patch size {patch}')
+    B, _, H, W = images_u8.shape
+    kp = clip_patch_width(patch)
+    out = torch.empty((B * (1 + (size // patch) ** 2), kp), device=images_u8.device, dtype=dtype)
+    _fn('clip_patches_u8', dtype)(_p(_chk(images_u8, torch.uint8)), _p(out), B, H, W, int(size), int(patch), kp, *(float(m) for m in mean),
+                                  *(float(s) for s in std), _s())
+    return out
+
+
+def gelu(x, mode):
+    """MLP activation of a CLIP layer (sidlsg_gelu): mode 'quick_gelu' = x * sigmoid(1.702 x), 'gelu' = the exact erf GELU."""
+    if mode not in ('quick_gelu', 'gelu'):
+        raise ValueError(f"gelu: mode {mode!r}: expected 'quick_gelu' or 'gelu'")
+    _chk(x, ACT)
+    y = torch.empty_like(x)
+    if x.numel():
+        _fn('gelu', x.dtype)(_p(x), _p(y), x.numel(), 0 if mode == 'quick_gelu' else 1, _s())
+    return y
+
+
+def clip_score(image_embeds, text_embeds):
+    """[B, F] image and text embeddings (both bf16 or both fp32) -> ([B, 2F] fp32 = F.normalize(image) | F.normalize(text), the
+    reference wrapper's return value, and [B] fp32 cosines) (sidlsg_clip_score)."""
+    _chk(image_embeds, ACT)
+    _chk(text_embeds, image_embeds.dtype)
+    if image_embeds.dim() != 2 or image_embeds.shape != text_embeds.shape or 0 in image_embeds.shape:
+        raise RuntimeError(f'clip_score: image {tuple(image_embeds.shape)} and text {tuple(text_embeds.shape)}: expected two equal non-empty [B, F]')
+    B, F = image_embeds.shape
+    feats = torch.empty((B, 2 * F), device=image_embeds.device, dtype=F32)
+    cosine = torch.empty(B, device=image_embeds.device, dtype=F32)
+    lib.sidlsg_clip_score(_p(image_embeds), _p(text_embeds), 1 if image_embeds.dtype == F32 else 0, _p(feats), _p(cosine), B, F, _s())
+    return feats, cosine
+
+
 F16 = torch.float16
 
 

@@ -129,7 +129,7 @@ def training_loop(
 ):
     if not train_mode and network_pkl == TEACHER:
         return evaluate_teacher(run_dir=run_dir, dataset_kwargs=dataset_kwargs, network_kwargs=network_kwargs, device=device, metrics=metrics,
-                                init_timestep=init_timestep, metric_pt_path=metric_pt_path, metric_open_clip_path=metric_open_clip_path,
+                                init_timestep=init_timestep, metric_pt_path=metric_pt_path, metric_open_clip_path=metric_open_clip_path, metric_clip_path=metric_clip_path,
                                 pretrained_model_name_or_path=pretrained_model_name_or_path, resolution=resolution,
                                 teacher_steps=TEACHER_STEPS if teacher_steps is None else teacher_steps,
                                 teacher_cfg=TEACHER_CFG if teacher_cfg is None else teacher_cfg, metric_real_stats=metric_real_stats,
@@ -137,7 +137,7 @@ def training_loop(
                                 snapshot_images=snapshot_images, batch_size=batch_size, batch_gpu=batch_gpu)
     if not train_mode:
         return evaluate_network(run_dir=run_dir, dataset_kwargs=dataset_kwargs, network_kwargs=network_kwargs, device=device, metrics=metrics,
-                                init_timestep=init_timestep, metric_pt_path=metric_pt_path, metric_open_clip_path=metric_open_clip_path,
+                                init_timestep=init_timestep, metric_pt_path=metric_pt_path, metric_open_clip_path=metric_open_clip_path, metric_clip_path=metric_clip_path,
                                 pretrained_model_name_or_path=pretrained_model_name_or_path, network_pkl=network_pkl, resolution=resolution,
                                 num_steps=num_steps, metric_real_stats=metric_real_stats, metric_num_test=metric_num_test,
                                 dataset_prompt_text_kwargs=dataset_prompt_text_kwargs, snapshot_images=snapshot_images,
@@ -373,7 +373,7 @@ def training_loop(
             for metric in metrics:
                 extra = dict(num_test=metric_num_test) if metric_num_test is not None else {}
                 result = metric_main.calc_metric(metric, G=G_eval, resolution=resolution, init_timestep=init_timestep, detector=metric_pt_path,
-                                                 real_stats=metric_real_stats, open_clip_detector=metric_open_clip_path, device=device,
+                                                 real_stats=metric_real_stats, open_clip_detector=metric_open_clip_path, metric_clip_path=metric_clip_path, device=device,
                                                  run_dir=run_dir, **msrc, **extra)
                 metric_main.report_metric(result, run_dir=run_dir, alpha=alpha,
                                           snapshot_pkl=os.path.join(run_dir, f'network-snapshot-{alpha:03f}-{cur_nimg // 1000:06d}.pkl') if run_dir else None)
@@ -423,7 +423,7 @@ def _evaluation_grid(msrc, vae, resolution, batch_size, batch_gpu, run_dir, devi
 
 def evaluate_network(run_dir, dataset_kwargs, network_kwargs, device, metrics, init_timestep, metric_pt_path, metric_open_clip_path,
                      pretrained_model_name_or_path, network_pkl, resolution, num_steps=1, metric_real_stats=None, metric_num_test=None,
-                     dataset_prompt_text_kwargs=None, snapshot_images=False, batch_size=512, batch_gpu=None):
+                     dataset_prompt_text_kwargs=None, snapshot_images=False, batch_size=512, batch_gpu=None, metric_clip_path=None):
     """`--train_mode 0` (sid_training_loop.py:680-745): load the text encoder / VAE / scheduler, un-pickle the distilled generator
     from `network_pkl` (`pickle.load(f)['ema']`, the file the training loop writes at the snapshot ticks) and evaluate every metric
     with 1, 2 and 4 generation steps; each result goes to `<dirname(run_dir)>/<metric><number>_<steps>.txt` in the reference's
@@ -468,7 +468,7 @@ def evaluate_network(run_dir, dataset_kwargs, network_kwargs, device, metrics, i
                                     init_timestep=init_timestep, resolution=resolution, num_steps=num_steps)
             extra = dict(num_test=metric_num_test) if metric_num_test is not None else {}
             result = metric_main.calc_metric(metric, G=G_eval, resolution=resolution, init_timestep=init_timestep, detector=metric_pt_path,
-                                             real_stats=metric_real_stats, open_clip_detector=metric_open_clip_path, device=device,
+                                             real_stats=metric_real_stats, open_clip_detector=metric_open_clip_path, metric_clip_path=metric_clip_path, device=device,
                                              run_dir=run_dir, **msrc, **extra)
             out[(metric, num_steps_eval)] = result
             if dist.get_rank() == 0:
@@ -483,7 +483,8 @@ def evaluate_network(run_dir, dataset_kwargs, network_kwargs, device, metrics, i
 
 def evaluate_teacher(run_dir, dataset_kwargs, network_kwargs, device, metrics, init_timestep, metric_pt_path, metric_open_clip_path,
                      pretrained_model_name_or_path, resolution, teacher_steps=TEACHER_STEPS, teacher_cfg=TEACHER_CFG, metric_real_stats=None,
-                     metric_num_test=None, dataset_prompt_text_kwargs=None, snapshot_images=False, batch_size=512, batch_gpu=None):
+                     metric_num_test=None, dataset_prompt_text_kwargs=None, snapshot_images=False, batch_size=512, batch_gpu=None,
+                     metric_clip_path=None):
     """`--train_mode 0 --network_pkl teacher`: the teacher row of the tables under this project's own protocol.  The UNet of the model
     is sampled with classifier-free guidance `teacher_cfg` and a `teacher_steps`-step deterministic DDIM sampler
     (sd_util.teacher_sample) as the `G` of every metric -- the same prompts, seeds, VAE, detector resize and metric code as a
@@ -523,7 +524,7 @@ def evaluate_teacher(run_dir, dataset_kwargs, network_kwargs, device, metrics, i
                                        lambda z, c: sample(latents=z, contexts=c, return_images=False))
         extra = dict(num_test=metric_num_test) if metric_num_test is not None else {}
         result = metric_main.calc_metric(metric, G=G_eval, resolution=resolution, init_timestep=init_timestep, detector=metric_pt_path,
-                                         real_stats=metric_real_stats, open_clip_detector=metric_open_clip_path, device=device,
+                                         real_stats=metric_real_stats, open_clip_detector=metric_open_clip_path, metric_clip_path=metric_clip_path, device=device,
                                          run_dir=run_dir, **msrc, **extra)
         metric_main.report_metric(result, run_dir=run_dir, snapshot_pkl=os.path.join(run_dir, tag) if run_dir else tag)
         out[metric] = result

@@ -92,8 +92,8 @@ OPTIONS = [
     (('--cfg_eval_fake',), dict(type=float, default=1, show_default=True, help='kappa2 = kappa3: guidance scale when evaluating the fake score')),
     (('--cfg_eval_real',), dict(type=float, default=1, show_default=True, help='kappa4: guidance scale when evaluating the teacher')),
     (('--metric_pt_path',), dict(type=str, default=None, help='Accepted for compatibility')),
-    (('--metric_clip_path',), dict(type=str, default=None, help='Accepted for compatibility')),
-    (('--metric_open_clip_path',), dict(type=str, default=None, help='Accepted for compatibility')),
+    (('--metric_clip_path',), dict(type=str, default=None, help='CLIP model behind clipscore30k: a local directory in the Hugging Face layout (config.json, model.safetensors, vocab.json, merges.txt)')),
+    (('--metric_open_clip_path',), dict(type=str, default=None, help='CLIP model behind open_clipscore_30k: such a directory, or a pickled open_clip wrapper of the reference')),
     (('--enable_xformers',), dict(type=bool, default=True, show_default=True, help='Accepted for compatibility (attention is the fused HIP kernel)')),
     (('--gradient_checkpointing',), dict(type=bool, default=False, show_default=True, help='Accepted for compatibility')),
     (('--optimizer',), dict(type=click.Choice(['adam', 'adamw']), default='adam', show_default=True, help='Optimizer')),

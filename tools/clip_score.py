@@ -1,0 +1,55 @@
+#!/usr/bin/env python
+"""CLIP score of a directory of generated images against their prompts, with a local CLIP directory (sid_lsg_amd.clip).
+    python tools/clip_score.py --images out --text_prompts prompts.txt --clip /models/clip-vit-large-patch14 [--batch 64]
+`<seed:06d>.png` pairs with prompt line `seed % len(prompts)`: generate_onestep.py's own pairing.  The images go through
+metrics.resize_for_detector (256 x 256, Pillow LANCZOS arithmetic) first, so the number is the one `fid_clip_30k_full` reports for them."""
+import argparse
+import os
+import re
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from generate_onestep import read_prompts  # noqa: E402
+from sid_lsg_amd import metrics  # noqa: E402
+
+
+def paired_files(image_dir, prompts):
+    """[(path, prompt)] of every <seed:06d>.png below image_dir (--subdirs layouts included), in seed order."""
+    out = []
+    for root, _, files in os.walk(image_dir):
+        for f in files:
+            m = re.fullmatch(r'(\d{6,})\.png', f)
+            if m:
+                out.append((int(m.group(1)), os.path.join(root, f)))
+    return [(p, prompts[seed % len(prompts)]) for seed, p in sorted(out)]
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('--images', required=True)
+    ap.add_argument('--text_prompts', required=True)
+    ap.add_argument('--clip', required=True, help="a CLIP directory in the Hugging Face layout, or 'random:clip-<arch>'")
+    ap.add_argument('--batch', type=int, default=64)
+    a = ap.parse_args(argv)
+    import PIL.Image
+    pairs = paired_files(a.images, read_prompts(a.text_prompts))
+    if not pairs:
+        raise SystemExit(f'{a.images}: no <seed:06d>.png files')
+    dev = torch.device('cuda:0')
+    det = metrics.load_detector(a.clip, dev)
+    scores = []
+    for i in range(0, len(pairs), a.batch):
+        chunk = pairs[i:i + a.batch]
+        imgs = torch.stack([torch.from_numpy(np.asarray(PIL.Image.open(p).convert('RGB'))).permute(2, 0, 1) for p, _ in chunk]).to(dev)
+        with torch.no_grad():
+            scores.append(metrics.row_cosines(det)(metrics.resize_for_detector(imgs, 256), [t for _, t in chunk]).double().cpu())
+    s = torch.cat(scores)
+    print(f'clip_score {float(s.mean()):.6f}  ({len(s)} images, {a.clip})')
+    return float(s.mean())
+
+
+if __name__ == '__main__':
+    main()
