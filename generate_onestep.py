@@ -11,10 +11,17 @@ over ranks.  `--repo_id` must be a local diffusers-layout directory (text encode
 (`random:<arch>:v` for a v-prediction model); its parameterisation must be the snapshot's.  `--resolution` is the image size
 (latent = resolution / 8; 768 for an SD 2.x 768-v generator).
 
+`--init_images DIR` turns it into image-to-image generation: sample `idx` (the index that picks its prompt) starts from file
+`idx % len(files)` of DIR (PNG / JPEG, sorted by name; centre-cropped to a square and resized to `--resolution`), encoded by the VAE
+encoder on the HIP kernels (sid_lsg_amd.vae.HipAutoencoderKLEncoder) and re-noised with the sample's own z.  A generator trained with
+`--num_steps N` is entered at step k of its chain, chosen by `--strength` (strength_to_step); for a one-step generator the knob is
+`--init_timestep`.  Without `--init_images` nothing changes.
+
 `--network teacher` samples the teacher itself instead of a snapshot: the UNet of `--repo_id` under classifier-free guidance
 (`--guidance_scale`, default 7.5) and a deterministic DDIM sampler of `--teacher_steps` steps (default 50;
 sid_lsg_amd.sd_util.teacher_sample), with the same seeds, prompts and file names -- the teacher row of the SiD-LSG tables.
 """
+import math
 import os
 import pickle
 import re
@@ -25,7 +32,8 @@ import torch
 
 from sid_lsg_amd import distributed as dist
 from sid_lsg_amd.preview import save_png
-from sid_lsg_amd.sd_util import TEACHER, TEACHER_CFG, TEACHER_STEPS, check_prediction_type, load_sd15, sid_sd_sampler, teacher_sample
+from sid_lsg_amd.sd_util import (TEACHER, TEACHER_CFG, TEACHER_STEPS, check_prediction_type, load_sd15, load_vae_encoder, sid_sd_sampler,
+                                 teacher_sample)
 
 
 class StackedRandomGenerator:
@@ -66,6 +74,65 @@ def teacher_options(network_pkl, teacher_steps, guidance_scale):
     return (TEACHER_STEPS if teacher_steps is None else teacher_steps), (TEACHER_CFG if guidance_scale is None else guidance_scale)
 
 
+IMAGE_EXTENSIONS = ('.png', '.jpg', '.jpeg')
+
+
+def strength_to_step(strength, num_steps):
+    """--strength S in (0, 1] -> the step k at which an N-step generator's chain is entered: k = clamp(N - ceil(S N), 0, N - 1).
+    S = 1 runs all N steps from the image re-noised at t_init (the most noise, the least of the image kept), a small S only the last
+    step.  N = 4: 1 -> 0, 0.75 -> 1, 0.6 -> 1, 0.5 -> 2, 0.25 -> 3, 0.01 -> 3; N = 1: always 0."""
+    if not 0 < strength <= 1:
+        raise ValueError(f'strength {strength}: expected a value in (0, 1]')
+    if num_steps < 1:
+        raise ValueError(f'num_steps {num_steps}: expected at least one step')
+    run = math.ceil(strength * num_steps - 1e-9)          # S N is formed in floating point: 0.3 * 10 must count as 3 steps, not 4
+    return min(max(num_steps - run, 0), num_steps - 1)
+
+
+def list_init_images(path):
+    """The PNG / JPEG files of a directory, sorted by name."""
+    if not os.path.isdir(path):
+        raise click.UsageError(f'--init_images {path}: not a directory')
+    files = sorted(f for f in os.listdir(path) if f.lower().endswith(IMAGE_EXTENSIONS) and os.path.isfile(os.path.join(path, f)))
+    if not files:
+        raise click.UsageError(f'--init_images {path}: no PNG or JPEG files')
+    return [os.path.join(path, f) for f in files]
+
+
+def load_init_image(path, resolution):
+    """-> uint8 [resolution, resolution, 3]: RGB, centre-cropped to a square, resized with PIL's LANCZOS filter (on the host)."""
+    import PIL.Image
+    with PIL.Image.open(path) as im:
+        im = im.convert('RGB')
+        w, h = im.size
+        side = min(w, h)
+        left, top = (w - side) // 2, (h - side) // 2
+        im = im.crop((left, top, left + side, top + side))
+        if side != resolution:
+            im = im.resize((resolution, resolution), PIL.Image.LANCZOS)
+        return np.ascontiguousarray(np.asarray(im, dtype=np.uint8))
+
+
+def load_init_batch(files, indices, resolution):
+    """Sample idx takes file idx % len(files) -> uint8 [B, resolution, resolution, 3]."""
+    return np.stack([load_init_image(files[i % len(files)], resolution) for i in indices])
+
+
+def init_image_options(network_pkl, init_images, strength, sample_posterior, num_steps_eval):
+    """-> None without --init_images, else (files, entry step k, sample the posterior?); inconsistent options are refused."""
+    if init_images is None:
+        given = [f for f, v in (('--strength', strength), ('--sample_posterior', sample_posterior)) if v is not None]
+        if given:
+            raise click.UsageError(f'{" / ".join(given)} apply to --init_images only')
+        return None
+    if network_pkl == TEACHER:
+        raise click.UsageError(f'--init_images with --network {TEACHER}: image-to-image with the teacher sampler is not supported')
+    if num_steps_eval < 1:
+        raise click.UsageError('--init_images needs --num_steps_eval >= 1')
+    files = list_init_images(init_images)
+    return files, strength_to_step(1.0 if strength is None else strength, num_steps_eval), bool(sample_posterior)
+
+
 @click.command()
 @click.option('--network', 'network_pkl', type=str, required=True, metavar='PATH', help=f'Network snapshot pickle, or "{TEACHER}": sample the UNet of --repo_id itself')
 @click.option('--outdir', type=str, required=True, metavar='DIR', help='Where to save the output images')
@@ -83,11 +150,17 @@ def teacher_options(network_pkl, teacher_steps, guidance_scale):
 @click.option('--custom_seed', type=bool, default=False, show_default=True, help='Prompt i <-> i-th seed of the list instead of seed value')
 @click.option('--teacher_steps', type=click.IntRange(min=1), default=None, help=f'DDIM steps of --network {TEACHER}  [default: {TEACHER_STEPS}]')
 @click.option('--guidance_scale', type=float, default=None, help=f'Classifier-free guidance scale of --network {TEACHER}  [default: {TEACHER_CFG}]')
+@click.option('--init_images', type=str, default=None, metavar='DIR', help='Image-to-image: PNG/JPEG files (sorted by name); sample idx starts from file idx mod len(files)')
+@click.option('--strength', type=click.FloatRange(min=0, max=1, min_open=True), default=None,
+              help='With --init_images: share of the --num_steps_eval steps that run, k = N - ceil(S N) is the entry step; a one-step '
+                   'generator has no such choice, its knob is --init_timestep  [default: 1]')
+@click.option('--sample_posterior', type=bool, default=None, help='With --init_images: sample the VAE posterior (eps from the per-seed generator, after z) instead of its mean  [default: False]')
 def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, init_timestep, text_prompts, repo_id, resolution, use_fp16,
-         enable_compress_npz, num_steps_eval, custom_seed, teacher_steps, guidance_scale):
+         enable_compress_npz, num_steps_eval, custom_seed, teacher_steps, guidance_scale, init_images, strength, sample_posterior):
     if resolution % 8:
         raise click.BadParameter(f'{resolution}: must be a multiple of 8', param_hint='--resolution')
     teacher = teacher_options(network_pkl, teacher_steps, guidance_scale)
+    img2img = init_image_options(network_pkl, init_images, strength, sample_posterior, num_steps_eval)
     dist.init()
     device = torch.device('cuda')
     rank, world = dist.get_rank(), dist.get_world_size()
@@ -113,6 +186,9 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
         G_ema.eval().requires_grad_(False)
         if num_steps_eval != 1:
             dist.print0(f'Note: --num_steps_eval {num_steps_eval} is ignored with --network {TEACHER} (the step count is --teacher_steps)')
+    if img2img is not None:
+        vae_encoder = load_vae_encoder(repo_id, device)
+        dist.print0(f'Image-to-image: {len(img2img[0])} init images from "{init_images}", entering at step {img2img[1]} of {num_steps_eval}')
     if world > 1 and rank == 0:
         torch.distributed.barrier()
     if teacher is None and num_steps_eval > 1:
@@ -127,8 +203,15 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
             continue
         batch = [int(b) for b in batch]
         batch_seeds = [seeds[i] for i in batch] if custom_seed else batch
-        z = StackedRandomGenerator(device, batch_seeds).randn([len(batch), 4, lat, lat], device=device)
+        rnd = StackedRandomGenerator(device, batch_seeds)
+        z = rnd.randn([len(batch), 4, lat, lat], device=device)
         prompts = [captions[i % len(captions)] for i in batch]
+        i2i = {}
+        if img2img is not None:
+            files, start_step, sample = img2img
+            pixels = torch.from_numpy(load_init_batch(files, batch, resolution)).to(device)
+            eps = rnd.randn([len(batch), 4, lat, lat], device=device) if sample else None
+            i2i = dict(init_latents=vae_encoder.encode_latents(pixels, eps=eps), start_step=start_step)
         with torch.no_grad():
             if teacher is not None:
                 images = teacher_sample(unet=G_ema, latents=z, contexts=prompts, noise_scheduler=sched, text_encoder=text_encoder,
@@ -139,7 +222,7 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
                                         init_timesteps=init_timestep * torch.ones(len(batch), device=device, dtype=torch.long),
                                         noise_scheduler=sched, text_encoder=text_encoder, tokenizer=tokenizer, resolution=resolution,
                                         dtype=torch.bfloat16, return_images=True, vae=vae, num_steps=1, train_sampler=False,
-                                        num_steps_eval=num_steps_eval)
+                                        num_steps_eval=num_steps_eval, **i2i)
         arr = (images.float() * 127.5 + 128).clip(0, 255).to(torch.uint8).permute(0, 2, 3, 1).cpu().numpy()
         for key, img in zip(batch, arr):
             d = os.path.join(outdir, f'{key - key % 1000:06d}') if subdirs else outdir

@@ -362,6 +362,29 @@ int sidlsg_gelu(const void* x, void* y, long long n, int mode, void* stream);
 int sidlsg_gelu_f32(const void* x, void* y, long long n, int mode, void* stream);
 int sidlsg_clip_score(const void* img, const void* txt, int f32_in, float* feats, float* cosine, int B, int F, void* stream);
 
+/* ---- AutoencoderKL.encode (sid_lsg_amd/vae.py HipAutoencoderKLEncoder; the reference never encodes images: no counterpart there) ----
+ * sidlsg_conv3x3_br_bf16: diffusers Downsample2D(padding = 0): F.pad(x, (0, 1, 0, 1)) + conv2d(k = 3, stride 2, padding 0), i.e.
+ *   Y(i, j) = sum_{u, v} W(u, v) X(2 i + u, 2 j + v) with X = 0 at row H and column Wd.  X: [B][H][Wd][ldx] bf16, W: [Cout][3][3][Cin],
+ *   Y: [B][H/2][Wd/2][ldc] bf16 (fp32 with SIDLSG_OUT_F32); epilogue: bias (may be NULL), SIDLSG_SILU.  Forward only.  H and Wd even,
+ *   Cin and ldx multiples of 8; SIDLSG_EINVAL otherwise.  sidlsg_conv3x3_bf16 and its dispatch are untouched by it.
+ * sidlsg_attn_fwd_wide: O = softmax(Q K^T D^-1/2) V for ONE head of width D = 512 (any other D: SIDLSG_EINVAL), forward only: bf16 in and
+ *   out, fp32 accumulation, online softmax over 32-key tiles, no N x N matrix in memory.  Q/K/V/O: [B][N][ld*] views (token stride ld*,
+ *   batch stride bs*, in elements, multiples of 8; Q/K/V 16-byte aligned), N a multiple of 16 (queries = keys).
+ * sidlsg_image_to_nhwc8(_f32): images -> the [B][H][W][8] bf16 activation conv_in takes (channels 3..7 zero).  uint8 [B][H][W][3]:
+ *   x / 127.5 - 1 in fp32 (IEEE division, then subtraction), rounded to nearest even; _f32: fp32 [B][3][H][W] already in [-1, 1], rounded.
+ * sidlsg_vae_posterior: the tail of encode in one launch.  moments [B][HW][8] fp32 (conv_out, NHWC) -> quant_conv (qw [8][8], qb [8]
+ *   fp32: out = qw moments + qb per pixel) -> mean | logvar = channels 0..3 | 4..7, logvar clamped to [-30, 20], std = exp(logvar / 2),
+ *   z = (mean + std * eps) * scaling, or mean * scaling when eps = NULL (the mode).  eps, z, and (when not NULL) mean, logvar
+ *   (clamped): fp32 NCHW [B][4][HW]. */
+int sidlsg_conv3x3_br_bf16(const void* X, int ldx, const void* W, void* Y, int ldc, const float* bias, int B, int H, int Wd, int Cin, int Cout,
+                           int flags, void* stream);
+int sidlsg_attn_fwd_wide(const void* Q, const void* K, const void* V, void* O, int B, int N, int D, int ldq, int ldk, int ldv, int ldo,
+                         long long bsq, long long bsk, long long bsv, long long bso, void* stream);
+int sidlsg_image_to_nhwc8(const void* images_u8, void* out, int B, int H, int W, void* stream);
+int sidlsg_image_to_nhwc8_f32(const float* images_nchw, void* out, int B, int H, int W, void* stream);
+int sidlsg_vae_posterior(const float* moments, const float* qw, const float* qb, const float* eps, float* z, float* mean, float* logvar, int B,
+                         int HW, float scaling, void* stream);
+
 /* ---- reference plugin op: torch_utils/ops/bias_act.cpp:32 `bias_act(x,b,xref,yref,dy,grad,dim,act,alpha,gain,clamp)`
  * act: 1 linear 2 relu 3 lrelu 4 tanh 5 sigmoid 6 elu 7 selu 8 softplus 9 swish (bias_act.py:23-33).
  * grad 0: out = clamp(act(x + b[(i/stepB)%sizeB]) * gain); grad 1: out = dL/dx from dy (x, b = saved inputs).

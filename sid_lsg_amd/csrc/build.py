@@ -6,7 +6,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
-SOURCES = ['gemm.hip', 'norm.hip', 'attention.hip', 'elementwise.hip', 'optim.hip', 'fp32.hip', 'trace.hip', 'image_grid.hip', 'pr_dist.hip', 'clip.hip']
+SOURCES = ['gemm.hip', 'norm.hip', 'attention.hip', 'elementwise.hip', 'optim.hip', 'fp32.hip', 'trace.hip', 'image_grid.hip', 'pr_dist.hip', 'clip.hip', 'attn_wide.hip', 'vae_io.hip']
 LIB = os.path.join(PKG, 'libsidlsg_hip.so')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-munsafe-fp-atomics', '-Wno-unused-result']
 # Per-file extras.  attention.hip: the softmax works on MFMA results with VALU ops; with the default heuristics the
@@ -14,8 +14,9 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-munsafe-fp-ato
 # -fno-honor-nans: no canonicalising v_max x,x in front of every fmaxf on an MFMA result (infinities stay honoured).
 # image_grid.hip: the preview grid's uint8 conversion is specified rounding by rounding (subtract, multiply, round to even).
 # clip.hip: likewise the CLIP preprocessing (divide, bicubic taps, normalise): its result must not depend on compiler fusion.
+# vae_io.hip: likewise the VAE encoder's image conversion (divide, subtract) and its posterior tail (mean + std * eps).
 EXTRA = {'attention.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form', '-fno-honor-nans'], 'image_grid.hip': ['-ffp-contract=off'],
-         'clip.hip': ['-ffp-contract=off']}
+         'clip.hip': ['-ffp-contract=off'], 'vae_io.hip': ['-ffp-contract=off']}
 
 
 def digest():

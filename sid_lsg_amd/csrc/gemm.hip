@@ -313,7 +313,9 @@ DEVFN void gemm_store_rows(const GemmParams& p, const bf16* stage, int m0, int n
     }
 }
 
-template <int BM, int BN, int MODE>
+// PAD (conv modes): rows / columns of zero padding in front of the image, 1 = torch's padding=1; 0 = the window of output (i, j) starts at
+// input (stride i, stride j) and only its far side can leave the image (sidlsg_conv3x3_br_bf16: padding on the bottom and right only).
+template <int BM, int BN, int MODE, int PAD = 1>
 __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_kernel(GemmParams p) {   // 2 blocks/CU: <= 256 registers
     constexpr int WMT = BM / 2, WNT = BN / 2;   // wave tile
     constexpr int MT = WMT / 16, NT = WNT / 16;
@@ -359,8 +361,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_kernel(GemmParams p) { 
             const int b = mm / hw, rem = mm - b * hw;
             const int ho = rem / p.Wo, wo = rem - ho * p.Wo;
             abase[i] = (unsigned)b * (unsigned)(Hs * Ws) * (unsigned)p.lda * 2u + kc * 16u;
-            ahi[i] = ok ? ho * p.stride - 1 : -100000;       // pushes every tap out of range
-            awi[i] = wo * p.stride - 1;
+            ahi[i] = ok ? ho * p.stride - PAD : -100000;     // pushes every tap out of range
+            awi[i] = wo * p.stride - PAD;
         }
         arow[i] = OOB;
     }
@@ -1799,19 +1801,19 @@ static int launch_gemm_as(const GemmParams& p, hipStream_t s) {
 // alone (tools/ab/small_gemm.py under rocprofv3) they are not: 1232 x 640 x 768 7.4 us with either kernel, 1024 x 1280 x 1280 12.9 ->
 // 11.2, 2048 x 1280 x 1280 17.2 -> 18.7, step 209.98 vs 209.87 ms -- their time in the step is chip sharing, not their own latency.
 // Correct (the shapes are in tests/test_gpu_ops.py::test_gemm), neutral, not in the build: commit "gemm_s64_kernel" of round 5.)
-template <int BM, int BN, int MODE>
+template <int BM, int BN, int MODE, int PAD = 1>
 static int launch_gemm(const GemmParams& p, hipStream_t s) {
     const int tiles = m_tiles_rt(p, BM) * ((p.N + BN - 1) / BN);
     const size_t lds = (size_t)2 * (BM + BN) * BK * sizeof(bf16);
     static bool attr_done = false;
     if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_kernel<BM, BN, MODE>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_kernel<BM, BN, MODE, PAD>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr_done = true;
     }
     const int nk = (p.K + BK - 1) / BK;
     const int splits = p.kt_per_split ? (nk + p.kt_per_split - 1) / p.kt_per_split : 1;
-    SIDLSG_LAUNCH((gemm_bf16_kernel<BM, BN, MODE>), dim3(tiles, splits), dim3(NTHREADS), lds, s, p);
+    SIDLSG_LAUNCH((gemm_bf16_kernel<BM, BN, MODE, PAD>), dim3(tiles, splits), dim3(NTHREADS), lds, s, p);
     if (p.kt_per_split) {
         const size_t n4 = ((size_t)p.M * p.N + 3) / 4;
         SIDLSG_LAUNCH(gemm_finish_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, p, splits);
@@ -2974,6 +2976,35 @@ int sidlsg_conv3x3_bf16(const void* X, int ldx, const void* W, void* Y, int ldc,
     p.a_bytes = (unsigned)ab; p.w_bytes = (unsigned)wb;
     if (Cin % 64 == 0) return dispatch_gemm<1>(p, (hipStream_t)stream);
     return dispatch_gemm<2>(p, (hipStream_t)stream);
+}
+
+// diffusers Downsample2D(padding = 0) of the AutoencoderKL encoder: F.pad(x, (0, 1, 0, 1)) then conv2d(k = 3, stride 2, no padding), i.e.
+//   Y(i, j) = sum_{u, v} W(u, v) X(2 i + u, 2 j + v),   X = 0 at row H and column Wd          (H, Wd even; Y: [B][H/2][Wd/2][ldc])
+// Forward only, bias epilogue (flags: SIDLSG_OUT_F32 | SIDLSG_SILU).  Its own entry point and its own kernel instantiations (PAD = 0 of
+// gemm_bf16_kernel): the dispatch of sidlsg_conv3x3_bf16 is not involved.
+int sidlsg_conv3x3_br_bf16(const void* X, int ldx, const void* W, void* Y, int ldc, const float* bias, int B, int H, int Wd, int Cin, int Cout,
+                           int flags, void* stream) {
+    if (B <= 0 || H <= 0 || Wd <= 0 || ((H | Wd) & 1) || (Cin & 7) || (flags & ~(F_OUT_F32 | F_SILU))) return SIDLSG_EINVAL;
+    GemmParams p{};
+    p.A = (const bf16*)X; p.W = (const bf16*)W; p.C = Y; p.bias = bias;
+    p.ldrv = Cout;
+    p.H = H; p.Wd = Wd; p.Cin = Cin; p.stride = 2; p.ups = 0;
+    p.Ho = H / 2; p.Wo = Wd / 2;
+    p.M = B * p.Ho * p.Wo; p.N = Cout; p.K = 9 * Cin; p.lda = ldx; p.ldc = ldc;
+    p.Mtot = p.M;
+    p.rows_per_batch = p.Ho * p.Wo; p.alpha = 1.0f; p.flags = flags;
+    if (int e = check_common(p)) return e;
+    if (ldx < Cin || ldc < Cout) return SIDLSG_EINVAL;
+    const unsigned long long ab = (((unsigned long long)B * H * Wd - 1) * ldx + Cin) * 2ull, wb = (unsigned long long)Cout * 9 * Cin * 2ull;
+    if (!fits31(ab) || !fits31(wb)) return SIDLSG_EINVAL;
+    p.a_bytes = (unsigned)ab; p.w_bytes = (unsigned)wb;
+    SidlsgTraceScope ts(SIDLSG_FAM_CONV, 2.0 * p.M * (double)p.N * p.K,
+                        2.0 * ((double)B * H * Wd * Cin + (double)p.N * p.K + (double)p.M * p.N * ((flags & F_OUT_F32) ? 2 : 1)));
+    // 128 x 128 tiles once they cover the chip (>= 384: the rule of dispatch_gemm), 64 x 64 below
+    const bool big = (long long)((p.M + 127) / 128) * ((p.N + 127) / 128) >= 384;
+    hipStream_t s = (hipStream_t)stream;
+    if (Cin % 64 == 0) return big ? launch_gemm<128, 128, 1, 0>(p, s) : launch_gemm<64, 64, 1, 0>(p, s);
+    return big ? launch_gemm<128, 128, 2, 0>(p, s) : launch_gemm<64, 64, 2, 0>(p, s);
 }
 
 // dW[N][K] += dY[M][N]^T A[M][K]   (dense: Linear / 1x1 conv weight gradient; fp32 accumulate)

@@ -565,9 +565,22 @@ def gemm(a, w16, out=None, bias=None, res=None, rowvec=None, rows_per_batch=1, a
     return out
 
 
-def conv3x3(x, w16, bias=None, res=None, rowvec=None, stride=1, ups=0, out_f32=False):
-    """x: [B,Hs,Ws,Cin] bf16 NHWC; w16: [Cout, 9*Cin]; -> [B,Ho,Wo,Cout]"""
+def conv3x3(x, w16, bias=None, res=None, rowvec=None, stride=1, ups=0, out_f32=False, pad=1):
+    """x: [B,Hs,Ws,Cin] bf16 NHWC; w16: [Cout, 9*Cin]; -> [B,Ho,Wo,Cout].  pad=1: torch's padding=1 on all four sides.
+    pad='br' (stride 2 only, forward only): zero padding on the bottom and right only -- diffusers Downsample2D(padding=0),
+    F.pad(x, (0, 1, 0, 1)) + conv2d(stride=2) (sidlsg_conv3x3_br_bf16); bias is its only epilogue operand."""
     B, Hs, Ws, Cin = x.shape
+    if pad == 'br':
+        if stride != 2 or ups or res is not None or rowvec is not None or x.dtype != BF16 or isinstance(w16, (Pair, Fp8Weight)) or w16.dtype != BF16:
+            raise RuntimeError("conv3x3(pad='br'): stride 2, bf16 activations and weights, no upsampling, residual or row vector")
+        if Hs % 2 or Ws % 2:
+            raise RuntimeError(f"conv3x3(pad='br'): H and W must be even, got {Hs} x {Ws}")
+        Cout = w16.shape[0]
+        out = torch.empty((B, Hs // 2, Ws // 2, Cout), device=x.device, dtype=F32 if out_f32 else BF16)
+        lib.sidlsg_conv3x3_br_bf16(_p(_chk(x, BF16)), Cin, _p(_chk(w16, BF16)), _p(out), Cout, _p(bias), B, Hs, Ws, Cin, Cout, 1 if out_f32 else 0, _s())
+        return out
+    if pad != 1:
+        raise ValueError(f"conv3x3: pad {pad!r}: expected 1 or 'br'")
     H, W = (2 * Hs, 2 * Ws) if ups else (Hs, Ws)
     Cout = w16.shape[0]
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
@@ -1231,6 +1244,25 @@ class _Attention(torch.autograd.Function):
         return dq, (None if same else dkv), None, None, None, None, None, None
 
 
+WIDE_HEAD = 512      # the one head width of sidlsg_attn_fwd_wide
+
+
+def wide_attention(q, k, v):
+    """softmax(q k^T / sqrt(D)) v for ONE head of width D = 512 (the VAE mid-block attention; sidlsg_attn_fwd_wide): q, k, v
+    [B, N, 512] bf16, contiguous or column slices of a wider [B, N, ld] buffer (a fused q|k|v projection); N a multiple of 16.
+    Forward only; -> [B, N, 512] bf16."""
+    for t in (q, k, v):
+        if not t.is_cuda:
+            raise RuntimeError('sid_lsg_amd ops need CUDA(HIP) tensors: there is no CPU fallback')
+        if t.dtype != BF16 or t.dim() != 3 or t.shape != q.shape or t.stride(2) != 1:
+            raise RuntimeError(f'wide_attention: expected three bf16 [B, N, D] tensors of one shape with unit channel stride, got {tuple(t.shape)} {t.dtype}')
+    B, N, D = q.shape
+    o = torch.empty((B, N, D), device=q.device, dtype=BF16)
+    lib.sidlsg_attn_fwd_wide(_p(q), _p(k), _p(v), _p(o), B, N, D, q.stride(1), k.stride(1), v.stride(1), D, q.stride(0), k.stride(0), v.stride(0),
+                             N * D, _s())
+    return o
+
+
 def self_attention(qkv, heads, prescaled=False):
     """qkv: [B,N,3C] (fused projection output) -> [B,N,C]"""
     C = qkv.shape[2] // 3
@@ -1886,6 +1918,38 @@ def image_grid_u8(images, grid, first, gw, drange=(-1, 1), layout='nchw'):
     lib.sidlsg_image_grid_u8(_p(_chk(images, F32)), _p(_chk(grid, torch.uint8)), B, H, W, 1 if layout == 'nchw' else 0, int(first), int(gw),
                              grid.shape[0] // H, float(lo), float(hi), _s())
     return grid
+
+
+def image_to_nhwc8(images):
+    """Images -> the [B, H, W, 8] bf16 NHWC activation the VAE encoder's conv_in takes, channels 3..7 zero (sidlsg_image_to_nhwc8).
+    uint8 [B, H, W, 3]: x / 127.5 - 1 in fp32 (IEEE division, subtraction), rounded to bf16; fp32 [B, 3, H, W] in [-1, 1]: rounded."""
+    if images.dtype == torch.uint8 and images.dim() == 4 and images.shape[3] == 3:
+        B, H, W, _ = images.shape
+        out = torch.empty((B, H, W, 8), device=images.device, dtype=BF16)
+        lib.sidlsg_image_to_nhwc8(_p(_chk(images, torch.uint8)), _p(out), B, H, W, _s())
+    elif images.dtype == F32 and images.dim() == 4 and images.shape[1] == 3:
+        B, _, H, W = images.shape
+        out = torch.empty((B, H, W, 8), device=images.device, dtype=BF16)
+        lib.sidlsg_image_to_nhwc8_f32(_p(_chk(images, F32)), _p(out), B, H, W, _s())
+    else:
+        raise RuntimeError(f'image_to_nhwc8: expected uint8 [B, H, W, 3] or fp32 [B, 3, H, W], got {images.dtype} {tuple(images.shape)}')
+    return out
+
+
+def vae_posterior(moments, qw, qb, scaling_factor, eps=None, want_moments=False):
+    """The tail of AutoencoderKL.encode in one launch (sidlsg_vae_posterior).  moments: [B, h, w, 8] fp32 (the encoder's conv_out, NHWC);
+    qw [8, 8] / qb [8] fp32: quant_conv; eps: [B, 4, h, w] fp32 or None (the mode).  -> z = (mean + std * eps) * scaling_factor fp32
+    [B, 4, h, w], or (z, mean, logvar) with want_moments (logvar clamped to [-30, 20])."""
+    if moments.dim() != 4 or moments.shape[3] != 8 or tuple(qw.shape) != (8, 8) or tuple(qb.shape) != (8,):
+        raise RuntimeError(f'vae_posterior: moments {tuple(moments.shape)}, quant_conv {tuple(qw.shape)} / {tuple(qb.shape)}: expected [B, h, w, 8], [8, 8], [8]')
+    B, h, w, _ = moments.shape
+    if eps is not None and tuple(eps.shape) != (B, 4, h, w):
+        raise RuntimeError(f'vae_posterior: eps {tuple(eps.shape)}: expected {(B, 4, h, w)}')
+    z = torch.empty((B, 4, h, w), device=moments.device, dtype=F32)
+    mean, logvar = (torch.empty_like(z), torch.empty_like(z)) if want_moments else (None, None)
+    lib.sidlsg_vae_posterior(_p(_chk(moments, F32)), _p(_chk(qw, F32)), _p(_chk(qb, F32)), _p(_chk(eps, F32)) if eps is not None else None, _p(z),
+                             _p(mean), _p(logvar), B, h * w, float(scaling_factor), _s())
+    return (z, mean, logvar) if want_moments else z
 
 
 CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)      # the OpenAI constants the reference wrapper normalises with (networks/clip.py:26)

@@ -229,6 +229,28 @@ def load_sd15(pretrained_model_name_or_path, pretrained_vae_model_name_or_path, 
     return unet, vae, noise_scheduler.to(device), text_encoder, tokenizer
 
 
+def load_vae_encoder(pretrained_model_name_or_path, device, seed=0):
+    """The encoder half of the model's AutoencoderKL (HipAutoencoderKLEncoder) for the same specs load_sd15 takes: a local
+    diffusers-layout directory -> its vae/diffusion_pytorch_model.safetensors (the file the decoder loads its half from), 'random:<arch>'
+    (or a directory without that file) -> seeded random weights.  Not part of load_sd15's tuple: only image-to-image needs it."""
+    name = str(pretrained_model_name_or_path)
+    arch = _arch_of(name)
+    local = os.path.isdir(name)
+    if not local and not name.lower().startswith('random:') and os.environ.get('SIDLSG_ALLOW_RANDOM_INIT', '0') != '1':
+        raise FileNotFoundError(f"{name}: not a local diffusers directory and there is no network; pass a directory or 'random:{arch}'")
+    from .vae import HipAutoencoderKLEncoder
+    enc = HipAutoencoderKLEncoder('sd' if arch in ('sd15', 'sd21-base') else 'tiny')
+    vae_file = os.path.join(name, 'vae', 'diffusion_pytorch_model.safetensors')
+    if local and os.path.isfile(vae_file):
+        from safetensors.torch import load_file
+        res = enc.load_state_dict(load_file(vae_file))
+        if res.missing_keys:
+            raise RuntimeError(f'{vae_file}: no encoder weights for {res.missing_keys[:8]}')
+    else:
+        enc.init_parameters(seed + 3)
+    return enc.to(torch.device(device))
+
+
 def encode_contexts(contexts, text_encoder, tokenizer, device):
     """list[str] -> [B, L, D] text states (no grad); a tensor is passed through (pre-computed states)."""
     if torch.is_tensor(contexts):
@@ -309,8 +331,20 @@ def hip_denoise(unet, prep, guidance_scale, predict_x0):
 # ------------------------------------------------------------------------------------------------
 def sid_sd_sampler(unet, latents, contexts, init_timesteps, noise_scheduler, text_encoder, tokenizer, resolution,
                    dtype=torch.float16, return_images=False, vae=None, guidance_scale=1, num_steps=1, train_sampler=True,
-                   num_steps_eval=1):
+                   num_steps_eval=1, init_latents=None, start_step=0):
+    """init_latents / start_step (eval mode only; image-to-image): the chain is entered at step `start_step` with D_x = init_latents
+    (scaled latents [B, 4, h, w], e.g. HipAutoencoderKLEncoder.encode_latents); the first executed step takes `latents` as its noise,
+    so its input is x_{t_k} = s0 init_latents + s1 latents -- what a generator trained with --num_steps N saw at step k."""
     steps = num_steps if train_sampler else num_steps_eval
+    if init_latents is None:
+        if start_step != 0:
+            raise ValueError('sid_sd_sampler: start_step without init_latents')
+    elif train_sampler:
+        raise ValueError('sid_sd_sampler: init_latents is for the evaluation sampler (train_sampler=False)')
+    elif not 0 <= start_step < steps:
+        raise ValueError(f'sid_sd_sampler: start_step {start_step} outside [0, {steps})')
+    elif init_latents.shape != latents.shape:
+        raise ValueError(f'sid_sd_sampler: init_latents {tuple(init_latents.shape)} vs latents {tuple(latents.shape)}')
     _require_hip(unet)
     check_prediction_type(unet, noise_scheduler)
     emb = encode_contexts(contexts, text_encoder, tokenizer, latents.device).to(_unwrap(unet).compute_dtype).contiguous()
@@ -323,8 +357,10 @@ def sid_sd_sampler(unet, latents, contexts, init_timesteps, noise_scheduler, tex
             D_x = hip_generate_steps(unet, latents.to(torch.float32).contiguous(), eps_next, emb, init_timesteps.contiguous(),
                                      noise_scheduler)
         else:
-            for i in range(steps):
-                noise = latents if i == 0 else torch.randn_like(latents)
+            if init_latents is not None:
+                D_x = init_latents.to(torch.float32).contiguous()
+            for i in range(start_step, steps):
+                noise = latents if i == start_step else torch.randn_like(latents)
                 t_i = (init_timesteps * (1 - i / steps)).to(torch.long)
                 D_x = hip_generate(unet, noise.to(torch.float32).contiguous(), emb, t_i.contiguous(), noise_scheduler, x0=D_x)
     if not return_images:
