@@ -155,8 +155,10 @@ def init_image_options(network_pkl, init_images, strength, sample_posterior, num
               help='With --init_images: share of the --num_steps_eval steps that run, k = N - ceil(S N) is the entry step; a one-step '
                    'generator has no such choice, its knob is --init_timestep  [default: 1]')
 @click.option('--sample_posterior', type=bool, default=None, help='With --init_images: sample the VAE posterior (eps from the per-seed generator, after z) instead of its mean  [default: False]')
+@click.option('--text_encoder', type=click.Choice(['torch', 'hip']), default=None, help='CLIP text encoder: the PyTorch module, or the same weights on the HIP kernels  [default: $SIDLSG_TEXT_ENCODER, else torch] (not a reference option)')
 def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, init_timestep, text_prompts, repo_id, resolution, use_fp16,
-         enable_compress_npz, num_steps_eval, custom_seed, teacher_steps, guidance_scale, init_images, strength, sample_posterior):
+         enable_compress_npz, num_steps_eval, custom_seed, teacher_steps, guidance_scale, init_images, strength, sample_posterior, text_encoder):
+    text_encoder_kind = text_encoder
     if resolution % 8:
         raise click.BadParameter(f'{resolution}: must be a multiple of 8', param_hint='--resolution')
     teacher = teacher_options(network_pkl, teacher_steps, guidance_scale)
@@ -177,12 +179,12 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
         with open(network_pkl, 'rb') as f:
             G_ema = pickle.load(f)['ema'].to(device)
         G_ema.eval().requires_grad_(False)
-        _, vae, sched, text_encoder, tokenizer = load_sd15(repo_id, repo_id, device, torch.bfloat16)
+        _, vae, sched, text_encoder, tokenizer = load_sd15(repo_id, repo_id, device, torch.bfloat16, text_encoder=text_encoder_kind)
         del _
         check_prediction_type(G_ema, sched)       # a v snapshot with an epsilon --repo_id (or the reverse) would sample garbage
     else:
         dist.print0(f'Sampling the teacher "{repo_id}": DDIM {teacher[0]} steps, guidance scale {teacher[1]:g}')
-        G_ema, vae, sched, text_encoder, tokenizer = load_sd15(repo_id, repo_id, device, torch.bfloat16)
+        G_ema, vae, sched, text_encoder, tokenizer = load_sd15(repo_id, repo_id, device, torch.bfloat16, text_encoder=text_encoder_kind)
         G_ema.eval().requires_grad_(False)
         if num_steps_eval != 1:
             dist.print0(f'Note: --num_steps_eval {num_steps_eval} is ignored with --network {TEACHER} (the step count is --teacher_steps)')

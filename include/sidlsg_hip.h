@@ -385,6 +385,24 @@ int sidlsg_image_to_nhwc8_f32(const float* images_nchw, void* out, int B, int H,
 int sidlsg_vae_posterior(const float* moments, const float* qw, const float* qb, const float* eps, float* z, float* mean, float* logvar, int B,
                          int HW, float scaling, void* stream);
 
+/* ---- CLIP text encoder (sid_lsg_amd/text.py HipCLIPTextModel; transformers' CLIPTextModel, which the reference calls) ------------
+ * sidlsg_attn_causal_fwd(_f32): O = softmax(mask(Q K^T D^-1/2)) V per head, key j visible to query i iff j <= i.  Forward only, no
+ *   LSE.  Q/K/V/O: [B][N][ld*] views of bf16 (_f32: fp32) holding H heads of width D side by side (token stride ld* >= H * D, batch
+ *   stride bs*, in elements), so a fused [B][N][3 H D] projection is consumed in place.  1 <= N <= 128 (queries = keys), D a multiple
+ *   of 8 up to 128; one workgroup per (batch, head) stages K and V in LDS once, wave w owns queries 16 w .. 16 w + 15 and visits key tiles
+ *   0 .. w only; single-pass softmax in fp32 (bf16: P rounded to bf16 once for the PV product; _f32: nothing rounded to bf16).
+ *   SIDLSG_EINVAL, and no launch, for any other N or D, null pointers, pointers not 16-byte aligned, ld* / bs* that are not
+ *   multiples of 16 bytes or ld* < H * D.
+ * sidlsg_text_embed(_f32): out[b L + l][:] = tok[ids[b][l]][:] + pos[l][:].  ids int64 [B][L]; tok fp32 [V][D], pos fp32 [P][D], L <= P;
+ *   out bf16 (_f32: fp32) [B L][D], the fp32 sum rounded once.  D % 8 == 0, tables and out 16-byte aligned; SIDLSG_EINVAL otherwise.  An
+ *   id outside [0, V) reads nothing: its row is written as NaN. */
+int sidlsg_attn_causal_fwd(const void* Q, const void* K, const void* V, void* O, int B, int H, int N, int D, int ldq, int ldk, int ldv,
+                           int ldo, long long bsq, long long bsk, long long bsv, long long bso, void* stream);
+int sidlsg_attn_causal_fwd_f32(const void* Q, const void* K, const void* V, void* O, int B, int H, int N, int D, int ldq, int ldk, int ldv,
+                               int ldo, long long bsq, long long bsk, long long bsv, long long bso, void* stream);
+int sidlsg_text_embed(const void* ids, const float* tok, const float* pos, void* out, int B, int L, int D, int V, int P, void* stream);
+int sidlsg_text_embed_f32(const void* ids, const float* tok, const float* pos, void* out, int B, int L, int D, int V, int P, void* stream);
+
 /* ---- reference plugin op: torch_utils/ops/bias_act.cpp:32 `bias_act(x,b,xref,yref,dy,grad,dim,act,alpha,gain,clamp)`
  * act: 1 linear 2 relu 3 lrelu 4 tanh 5 sigmoid 6 elu 7 selu 8 softplus 9 swish (bias_act.py:23-33).
  * grad 0: out = clamp(act(x + b[(i/stepB)%sizeB]) * gain); grad 1: out = dL/dx from dy (x, b = saved inputs).

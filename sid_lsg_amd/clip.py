@@ -1,4 +1,4 @@
-"""CLIP score from a local CLIP directory: the ViT image tower on the HIP kernels, the text tower in PyTorch.
+"""CLIP score from a local CLIP directory: the ViT image tower on the HIP kernels, the text tower in PyTorch or on them.
 
 Reference: networks/clip.py (the open_clip wrapper the metrics un-pickle: `forward(images, texts, div255)` -> the L2-normalised
 `image | text` features, :48-53; preprocessing :33-37) and metrics/sid_metric_utils.py:456-504 (the mean cosine of the two
@@ -13,7 +13,8 @@ Face layout instead (`openai/clip-vit-large-patch14`, `laion/CLIP-ViT-g-14-laion
     patch extraction in one launch (ops.clip_patches), ONE GEMM for patch embedding + class token + position embeddings (the
     latter two through its `res` operand), pre-LN layers on ops.layer_norm / ops.gemm / ops.self_attention / ops.gelu, the final
     LayerNorm and projection on the class token only.  Frozen, inference only.
-  * the text side is `text.CLIPTextModel` (PyTorch, as everywhere in this project), pooled at the first EOS token and projected.
+  * the text side is `text.CLIPTextModel` (PyTorch; the default) or, with load_clip(..., text_tower='hip'), the same weights as
+    `text.HipCLIPTextModel` on the HIP kernels; either way pooled at the first EOS token and projected.
   * `HipCLIPDetector`: the wrapper's call contract, finished by ops.clip_score (normalise both, concatenate, cosine).
   * `load_clip('random:clip-<arch>')`: seeded random networks with the hash tokenizer, for timing and tests (no weights offline).
 There is no fallback: the image tower runs on the GPU kernels or raises.
@@ -25,7 +26,7 @@ from types import SimpleNamespace
 import torch
 
 from . import ops
-from .text import CLIPBPETokenizer, CLIPTextModel, HashTokenizer
+from .text import TEXT_ENCODERS, CLIPBPETokenizer, CLIPTextModel, HashTokenizer, HipCLIPTextModel
 
 BF16, F32 = torch.bfloat16, torch.float32
 
@@ -263,9 +264,12 @@ def _random_state(v, t, device, seed):
     return sd
 
 
-def load_clip(path, device, compute_dtype=None, seed=0):
+def load_clip(path, device, compute_dtype=None, seed=0, text_tower='torch'):
     """A HipCLIPDetector from a local directory in the Hugging Face layout (module docstring), or from 'random:clip-<arch>'
-    (CLIP_ARCHS; seeded weights, hash tokenizer)."""
+    (CLIP_ARCHS; seeded weights, hash tokenizer).  text_tower: 'torch' (text.CLIPTextModel) or 'hip' (text.HipCLIPTextModel, the same
+    fp32 weights on the fp32 kernel family)."""
+    if text_tower not in TEXT_ENCODERS:
+        raise ValueError(f'text_tower {text_tower!r}: expected one of {TEXT_ENCODERS}')
     device = torch.device(device)
     name = str(path)
     if name.lower().startswith('random:'):
@@ -312,4 +316,6 @@ def load_clip(path, device, compute_dtype=None, seed=0):
             raise ValueError(f'{cj}: text_config.eos_token_id = {t.eos_token_id}, but {vj} has <|endoftext|> = {tokenizer.eos_token_id}')
     vision = HipCLIPVisionTower(v, state, device, compute_dtype)
     text = text.float().requires_grad_(False).eval().to(device)
+    if text_tower == 'hip':
+        text = HipCLIPTextModel.from_torch(text)
     return HipCLIPDetector(vision, text, state['text_projection.weight'].detach().to(device, F32), tokenizer, t.eos_token_id)

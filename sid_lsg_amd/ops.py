@@ -1991,6 +1991,70 @@ def gelu(x, mode):
     return y
 
 
+CAUSAL_MAX_TOKENS = 128            # sidlsg_attn_causal_fwd: the whole sequence of a head lives in one workgroup
+CAUSAL_MAX_HEAD_DIM = 128
+
+
+def causal_attention(q, k, v, heads):
+    """softmax(mask(q k^T / sqrt(D))) v per head, key j visible to query i iff j <= i (sidlsg_attn_causal_fwd): q, k, v [B, N, heads * D]
+    bf16 or fp32 of one shape with unit channel stride -- contiguous, or column slices of a wider buffer (a fused q|k|v projection,
+    consumed in place).  1 <= N <= 128, D a multiple of 8 up to 128.  Forward only; -> [B, N, heads * D]."""
+    for t in (q, k, v):
+        if not t.is_cuda:
+            raise RuntimeError('sid_lsg_amd ops need CUDA(HIP) tensors: there is no CPU fallback')
+        if t.requires_grad:
+            raise RuntimeError('causal_attention is forward only (the text encoder is frozen): got a tensor that requires grad')
+        if t.dtype not in (BF16, F32) or t.dtype != q.dtype or t.dim() != 3 or t.shape != q.shape or t.stride(2) != 1:
+            raise RuntimeError(f'causal_attention: expected three bf16 or fp32 [B, N, C] tensors of one shape and dtype with unit channel '
+                               f'stride, got {tuple(t.shape)} {t.dtype}')
+    B, N, C = q.shape
+    if heads <= 0 or C % heads or B == 0:
+        raise RuntimeError(f'causal_attention: {C} channels do not split into {heads} heads (batch {B})')
+    D = C // heads
+    if not 1 <= N <= CAUSAL_MAX_TOKENS or D % 8 or D > CAUSAL_MAX_HEAD_DIM:
+        raise RuntimeError(f'causal_attention: N = {N}, head dim {D}: the kernel takes 1 <= N <= {CAUSAL_MAX_TOKENS} and a head dim that '
+                           f'is a multiple of 8 up to {CAUSAL_MAX_HEAD_DIM}')
+    o = torch.empty((B, N, C), device=q.device, dtype=q.dtype)
+    _fn('attn_causal_fwd', q.dtype)(_p(q), _p(k), _p(v), _p(o), B, heads, N, D, q.stride(1), k.stride(1), v.stride(1), C, q.stride(0),
+                                    k.stride(0), v.stride(0), N * C, _s())
+    return o
+
+
+def causal_self_attention(qkv, heads):
+    """qkv: [B, N, 3C] (the fused q|k|v projection of a CLIP text layer, read in place) -> [B, N, C]; forward only."""
+    if qkv.dim() != 3 or qkv.shape[2] % 3:
+        raise RuntimeError(f'causal_self_attention: expected a [B, N, 3C] tensor, got {tuple(qkv.shape)}')
+    C = qkv.shape[2] // 3
+    return causal_attention(qkv[:, :, :C], qkv[:, :, C:2 * C], qkv[:, :, 2 * C:], heads)
+
+
+def text_embed(ids, tok, pos, dtype=BF16):
+    """int64 token ids [B, L] -> [B * L, D] `dtype`: tok[ids] + pos[:L], summed in fp32 and rounded once (sidlsg_text_embed).  tok [V, D]
+    and pos [P >= L, D] are fp32 on the GPU.  Host ids are checked here (ValueError naming the id) and copied; for device ids the
+    kernel writes the row of an id outside [0, V) as NaN and reads nothing for it."""
+    _chk(tok, F32)
+    _chk(pos, F32)
+    if dtype not in (BF16, F32):
+        raise RuntimeError(f'text_embed: output dtype {dtype}: expected bf16 or fp32')
+    if ids.dim() != 2 or ids.dtype != torch.int64 or 0 in ids.shape:
+        raise RuntimeError(f'text_embed: expected non-empty int64 [B, L] token ids, got {tuple(ids.shape)} {ids.dtype}')
+    if tok.dim() != 2 or pos.dim() != 2 or tok.shape[1] != pos.shape[1] or tok.shape[1] % 8:
+        raise RuntimeError(f'text_embed: tables {tuple(tok.shape)} and {tuple(pos.shape)}: expected [V, D] and [P, D], D a multiple of 8')
+    B, L = ids.shape
+    V, D = tok.shape
+    if L > pos.shape[0]:
+        raise RuntimeError(f'text_embed: {L} tokens per row, but only {pos.shape[0]} position embeddings')
+    if not ids.is_cuda:
+        bad = ids[(ids < 0) | (ids >= V)]
+        if bad.numel():
+            raise ValueError(f'text_embed: token id {int(bad[0])} is outside the vocabulary [0, {V})')
+        ids = ids.to(tok.device)
+    ids = ids.contiguous()
+    out = torch.empty((B * L, D), device=tok.device, dtype=dtype)
+    _fn('text_embed', dtype)(_p(ids), _p(tok), _p(pos), _p(out), B, L, D, V, pos.shape[0], _s())
+    return out
+
+
 def clip_score(image_embeds, text_embeds):
     """[B, F] image and text embeddings (both bf16 or both fp32) -> ([B, 2F] fp32 = F.normalize(image) | F.normalize(text), the
     reference wrapper's return value, and [B] fp32 cosines) (sidlsg_clip_score)."""

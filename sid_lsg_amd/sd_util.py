@@ -18,7 +18,7 @@ import torch.nn.functional as F
 
 from . import ops
 from .scheduler import SD_SAMPLING_CONFIG, DDPMScheduler, ddim_schedule
-from .text import TEXT_CONFIGS, CLIPBPETokenizer, CLIPTextModel, HashTokenizer
+from .text import TEXT_CONFIGS, CLIPBPETokenizer, CLIPTextModel, HashTokenizer, HipCLIPTextModel, resolve_text_encoder
 from .unet import CONFIGS, HipUNet2DCondition
 
 
@@ -165,7 +165,7 @@ def resolve_compute_dtype(compute_dtype=None):
 
 
 def load_sd15(pretrained_model_name_or_path, pretrained_vae_model_name_or_path, device, weight_dtype, revision=None,
-              variant=None, lora_config=None, enable_xformers=False, gradient_checkpointing=False, seed=0, compute_dtype=None):
+              variant=None, lora_config=None, enable_xformers=False, gradient_checkpointing=False, seed=0, compute_dtype=None, text_encoder=None):
     """Same contract as the reference factory.  Sources, in order:
       * a local diffusers-layout directory (unet/diffusion_pytorch_model.safetensors, text_encoder/model.safetensors,
         tokenizer/{vocab.json,merges.txt}) -> real weights through `load_state_dict` (key names are diffusers');
@@ -177,7 +177,10 @@ def load_sd15(pretrained_model_name_or_path, pretrained_vae_model_name_or_path, 
     always fp32.  The COMPUTE dtype is `compute_dtype` (torch.bfloat16 = production MFMA path, torch.float32 = the
     fp32-accurate mode of csrc/fp32.hip), default from $SIDLSG_COMPUTE_DTYPE ('bf16' | 'fp32'), else bf16.
     `enable_xformers` / `gradient_checkpointing` are accepted and ignored (attention is always the fused HIP kernel;
-    the reference itself never forwards gradient_checkpointing, sid_training_loop.py:224-228)."""
+    the reference itself never forwards gradient_checkpointing, sid_training_loop.py:224-228).
+    `text_encoder` (not a reference option): 'torch' = text.CLIPTextModel, the PyTorch module; 'hip' = text.HipCLIPTextModel, the same
+    seeded or loaded weights on the HIP kernels; default from $SIDLSG_TEXT_ENCODER, else 'torch'."""
+    text_encoder_kind = resolve_text_encoder(text_encoder)
     name = str(pretrained_model_name_or_path)
     arch = _arch_of(name)
     device = torch.device(device)
@@ -215,6 +218,8 @@ def load_sd15(pretrained_model_name_or_path, pretrained_vae_model_name_or_path, 
         if os.path.isfile(vj) and os.path.isfile(mt):
             tokenizer = CLIPBPETokenizer.from_files(vj, mt, model_max_length=cfg.text_len, pad_token_id=tokenizer.pad_token_id)
     text_encoder.requires_grad_(False).eval().to(device)
+    if text_encoder_kind == 'hip':
+        text_encoder = HipCLIPTextModel.from_torch(text_encoder)
     # VAE (decode only; cold path): real weights when the directory has them, seeded random ones otherwise
     vae_dir = pretrained_vae_model_name_or_path if (pretrained_vae_model_name_or_path and os.path.isdir(str(pretrained_vae_model_name_or_path))) else name
     vae_file = os.path.join(str(vae_dir), 'vae', 'diffusion_pytorch_model.safetensors')

@@ -1,4 +1,5 @@
-"""Text conditioning: tokenizer + CLIP text transformer ("stays PyTorch-ROCm" per BASELINE north_star).
+"""Text conditioning: tokenizer + CLIP text transformer ("stays PyTorch-ROCm" per BASELINE north_star; the same module on the HIP
+kernels is opt-in).
 
 Reference call sites: `tokenizer(prompts, padding='max_length', max_length=tokenizer.model_max_length,
 truncation=True, return_tensors='pt').input_ids` and `text_encoder(ids)[0]`
@@ -9,6 +10,8 @@ CLIPTextModel there (sid_sd_util.py:58-71).
     (`text_model.embeddings.token_embedding.weight`, `text_model.encoder.layers.N.self_attn.q_proj...`),
     so real SD text-encoder weights load with `load_state_dict`.  Checked against transformers'
     implementation by weight sharing in tests/test_text_encoder.py.
+  * `HipCLIPTextModel`: the same parameter tree with a forward on this package's kernels (ops.text_embed, ops.causal_self_attention,
+    ops.gemm / layer_norm / gelu); chosen by load_sd15(text_encoder='hip') / $SIDLSG_TEXT_ENCODER / load_clip(text_tower='hip').
   * `HashTokenizer`: no CLIP vocabulary exists offline, so prompts are mapped to ids by a deterministic
     word hash with CLIP's BOS/EOS/padding structure.  It is a stand-in for throughput and parity work,
     NOT the CLIP BPE; `CLIPBPETokenizer.from_files(vocab.json, merges.txt)` is used when files are given.
@@ -171,6 +174,102 @@ class CLIPTextModel(nn.Module):
         for lyr in tm.encoder.layers:
             x = lyr(x, mask)
         return (tm.final_layer_norm(x),)
+
+
+class HipCLIPTextModel(CLIPTextModel):
+    """CLIPTextModel on this package's HIP kernels: the same parameter tree and transformers key names (state_dict /
+    load_state_dict / .to() / deepcopy / pickling are the torch module's), another forward -- ops.text_embed, then per layer
+    layer_norm -> ONE fused q|k|v GEMM -> ops.causal_self_attention -> out-projection GEMM with the residual as its `res` operand ->
+    layer_norm -> fc1 GEMM -> ops.gelu -> fc2 GEMM with `res`, and the final layer_norm: 8 launches per layer.
+    The compute dtype follows the parameter dtype as the torch module's arithmetic does: fp32 parameters run the `_f32` kernel
+    family, bf16 parameters the bf16 one.  Compute copies (q|k|v weights concatenated to [3D, D], fp32 biases / norm parameters /
+    embedding tables) are built at the first forward and dropped by `_apply` (.to(), .float(), ...) and `load_state_dict`; the
+    encoder is frozen, so nothing else may change a parameter.  Forward only, GPU only: there is no CPU fallback."""
+
+    _hip_cache = None
+
+    @classmethod
+    def from_torch(cls, enc):
+        """The HIP module over the parameters of a CLIPTextModel (shared, not copied)."""
+        if isinstance(enc, cls):
+            return enc
+        if not isinstance(enc, CLIPTextModel):
+            raise TypeError(f'HipCLIPTextModel.from_torch: expected a CLIPTextModel, got {type(enc).__name__}')
+        new = cls.__new__(cls)
+        new.__dict__.update(enc.__dict__)
+        new._hip_cache = None
+        return new
+
+    def _apply(self, fn, *args, **kwargs):
+        self._hip_cache = None
+        return super()._apply(fn, *args, **kwargs)
+
+    def load_state_dict(self, *args, **kwargs):
+        self._hip_cache = None
+        return super().load_state_dict(*args, **kwargs)
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state['_hip_cache'] = None
+        return state
+
+    def _compute_copies(self):
+        tm = self.text_model
+        tok = tm.embeddings.token_embedding.weight
+        key = (tok.dtype, tok.device)
+        if self._hip_cache is not None and self._hip_cache.key == key:
+            return self._hip_cache
+        cd = tok.dtype
+        if cd not in (torch.bfloat16, torch.float32):
+            raise RuntimeError(f'HipCLIPTextModel: parameter dtype {cd}: the kernels compute in bfloat16 or float32')
+        f32 = lambda p: p.detach().float().contiguous()       # noqa: E731
+        w = lambda p: p.detach().to(cd).contiguous()          # noqa: E731
+        layers = []
+        for lyr in tm.encoder.layers:
+            a, m = lyr.self_attn, lyr.mlp
+            qkv = (a.q_proj, a.k_proj, a.v_proj)
+            layers.append(SimpleNamespace(
+                heads=a.heads, act=m.act, eps1=lyr.layer_norm1.eps, eps2=lyr.layer_norm2.eps,
+                ln1=(f32(lyr.layer_norm1.weight), f32(lyr.layer_norm1.bias)), ln2=(f32(lyr.layer_norm2.weight), f32(lyr.layer_norm2.bias)),
+                w_qkv=w(torch.cat([p.weight.detach() for p in qkv])), b_qkv=f32(torch.cat([p.bias.detach() for p in qkv])),
+                w_o=w(a.out_proj.weight), b_o=f32(a.out_proj.bias), w_1=w(m.fc1.weight), b_1=f32(m.fc1.bias),
+                w_2=w(m.fc2.weight), b_2=f32(m.fc2.bias)))
+        self._hip_cache = SimpleNamespace(
+            key=key, dtype=cd, tok=f32(tok), pos=f32(tm.embeddings.position_embedding.weight), layers=layers,
+            ln_f=(f32(tm.final_layer_norm.weight), f32(tm.final_layer_norm.bias)), eps_f=tm.final_layer_norm.eps)
+        return self._hip_cache
+
+    @torch.no_grad()
+    def forward(self, input_ids, attention_mask=None):
+        if attention_mask is not None:
+            raise ValueError('HipCLIPTextModel takes no attention_mask: the mask is causal, as in every Stable Diffusion and CLIP-score call')
+        if self.device.type != 'cuda':
+            raise RuntimeError('HipCLIPTextModel runs on the MI355X only (no CPU fallback): move it to the GPU, or use CLIPTextModel')
+        if input_ids.dim() != 2:
+            raise ValueError(f'HipCLIPTextModel: expected [B, L] token ids, got {tuple(input_ids.shape)}')
+        from . import ops
+        c = self._compute_copies()
+        B, L = input_ids.shape
+        D = c.tok.shape[1]
+        x = ops.text_embed(input_ids, c.tok, c.pos, c.dtype)                       # [B * L, D]
+        for lyr in c.layers:
+            qkv = ops.gemm(ops.layer_norm(x, *lyr.ln1, lyr.eps1), lyr.w_qkv, bias=lyr.b_qkv)
+            o = ops.causal_self_attention(qkv.view(B, L, 3 * D), lyr.heads)
+            x = ops.gemm(o.view(B * L, D), lyr.w_o, bias=lyr.b_o, res=x)
+            h = ops.gelu(ops.gemm(ops.layer_norm(x, *lyr.ln2, lyr.eps2), lyr.w_1, bias=lyr.b_1), lyr.act)
+            x = ops.gemm(h, lyr.w_2, bias=lyr.b_2, res=x)
+        return (ops.layer_norm(x, *c.ln_f, c.eps_f).view(B, L, D),)
+
+
+TEXT_ENCODERS = ('torch', 'hip')
+
+
+def resolve_text_encoder(kind=None):
+    """'torch' | 'hip': the argument when given, else $SIDLSG_TEXT_ENCODER, else 'torch'."""
+    kind = os.environ.get('SIDLSG_TEXT_ENCODER') or 'torch' if kind is None else kind
+    if kind not in TEXT_ENCODERS:
+        raise ValueError(f'text encoder {kind!r}: expected one of {TEXT_ENCODERS}')
+    return kind
 
 
 TEXT_CONFIGS = {

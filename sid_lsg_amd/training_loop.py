@@ -114,6 +114,12 @@ class PromptStream:
 SNAPSHOT_EXTRA_TICKS = (2, 4, 10, 20, 30, 40, 50, 60, 70, 80, 90, 100)
 
 
+def _text_encoder_opt(kind):
+    """load_sd15's `text_encoder` keyword ('torch' | 'hip'; not a reference option) when it was asked for: None leaves the choice
+    to load_sd15 ($SIDLSG_TEXT_ENCODER, else the torch module) and the call as the reference makes it."""
+    return {} if kind is None else dict(text_encoder=kind)
+
+
 def training_loop(
     run_dir='.', dataset_kwargs={}, data_loader_kwargs={}, network_kwargs={}, loss_kwargs={},
     fake_score_optimizer_kwargs={}, g_optimizer_kwargs={}, augment_kwargs=None, seed=0, batch_size=512, batch_gpu=None,
@@ -125,7 +131,7 @@ def training_loop(
     dataset_prompt_text_kwargs={}, cfg_train_fake=1, cfg_eval_fake=1, cfg_eval_real=1, num_steps=1, train_mode=True,
     network_pkl=None, enable_xformers=True, gradient_checkpointing=False, resolution=512, on_iteration=None,
     rng_device=None, metric_real_stats=None, metric_num_test=None, deterministic=False, snapshot_images=False,
-    teacher_steps=None, teacher_cfg=None,
+    teacher_steps=None, teacher_cfg=None, text_encoder=None,
 ):
     if not train_mode and network_pkl == TEACHER:
         return evaluate_teacher(run_dir=run_dir, dataset_kwargs=dataset_kwargs, network_kwargs=network_kwargs, device=device, metrics=metrics,
@@ -134,14 +140,14 @@ def training_loop(
                                 teacher_steps=TEACHER_STEPS if teacher_steps is None else teacher_steps,
                                 teacher_cfg=TEACHER_CFG if teacher_cfg is None else teacher_cfg, metric_real_stats=metric_real_stats,
                                 metric_num_test=metric_num_test, dataset_prompt_text_kwargs=dataset_prompt_text_kwargs,
-                                snapshot_images=snapshot_images, batch_size=batch_size, batch_gpu=batch_gpu)
+                                snapshot_images=snapshot_images, batch_size=batch_size, batch_gpu=batch_gpu, text_encoder=text_encoder)
     if not train_mode:
         return evaluate_network(run_dir=run_dir, dataset_kwargs=dataset_kwargs, network_kwargs=network_kwargs, device=device, metrics=metrics,
                                 init_timestep=init_timestep, metric_pt_path=metric_pt_path, metric_open_clip_path=metric_open_clip_path, metric_clip_path=metric_clip_path,
                                 pretrained_model_name_or_path=pretrained_model_name_or_path, network_pkl=network_pkl, resolution=resolution,
                                 num_steps=num_steps, metric_real_stats=metric_real_stats, metric_num_test=metric_num_test,
                                 dataset_prompt_text_kwargs=dataset_prompt_text_kwargs, snapshot_images=snapshot_images,
-                                batch_size=batch_size, batch_gpu=batch_gpu)
+                                batch_size=batch_size, batch_gpu=batch_gpu, text_encoder=text_encoder)
     num_steps = int(num_steps)
     if num_steps < 1:
         raise ValueError(f'num_steps={num_steps}: expected >= 1')
@@ -165,7 +171,7 @@ def training_loop(
         torch.distributed.barrier()
     unet, vae, noise_scheduler, text_encoder, tokenizer = load_sd15(
         pretrained_model_name_or_path=pretrained_model_name_or_path, pretrained_vae_model_name_or_path=None, device=device,
-        weight_dtype=dtype, enable_xformers=enable_xformers, lora_config=None, compute_dtype=dtype)
+        weight_dtype=dtype, enable_xformers=enable_xformers, lora_config=None, compute_dtype=dtype, **_text_encoder_opt(text_encoder))
     if world > 1 and rank == 0:
         torch.distributed.barrier()
     dist.print0('Loading network completed')
@@ -423,7 +429,8 @@ def _evaluation_grid(msrc, vae, resolution, batch_size, batch_gpu, run_dir, devi
 
 def evaluate_network(run_dir, dataset_kwargs, network_kwargs, device, metrics, init_timestep, metric_pt_path, metric_open_clip_path,
                      pretrained_model_name_or_path, network_pkl, resolution, num_steps=1, metric_real_stats=None, metric_num_test=None,
-                     dataset_prompt_text_kwargs=None, snapshot_images=False, batch_size=512, batch_gpu=None, metric_clip_path=None):
+                     dataset_prompt_text_kwargs=None, snapshot_images=False, batch_size=512, batch_gpu=None, metric_clip_path=None,
+                     text_encoder=None):
     """`--train_mode 0` (sid_training_loop.py:680-745): load the text encoder / VAE / scheduler, un-pickle the distilled generator
     from `network_pkl` (`pickle.load(f)['ema']`, the file the training loop writes at the snapshot ticks) and evaluate every metric
     with 1, 2 and 4 generation steps; each result goes to `<dirname(run_dir)>/<metric><number>_<steps>.txt` in the reference's
@@ -441,7 +448,7 @@ def evaluate_network(run_dir, dataset_kwargs, network_kwargs, device, metrics, i
     dtype = resolve_compute_dtype(dict(network_kwargs).get('compute_dtype'))
     _, vae, noise_scheduler, text_encoder, tokenizer = load_sd15(
         pretrained_model_name_or_path=pretrained_model_name_or_path, pretrained_vae_model_name_or_path=None, device=device,
-        weight_dtype=dtype, lora_config=None, compute_dtype=dtype)
+        weight_dtype=dtype, lora_config=None, compute_dtype=dtype, **_text_encoder_opt(text_encoder))
     dist.print0('Loading network completed')
     dist.print0(f'Loading network from "{network_pkl}"...')
     with open(network_pkl, 'rb') as f:
@@ -484,7 +491,7 @@ def evaluate_network(run_dir, dataset_kwargs, network_kwargs, device, metrics, i
 def evaluate_teacher(run_dir, dataset_kwargs, network_kwargs, device, metrics, init_timestep, metric_pt_path, metric_open_clip_path,
                      pretrained_model_name_or_path, resolution, teacher_steps=TEACHER_STEPS, teacher_cfg=TEACHER_CFG, metric_real_stats=None,
                      metric_num_test=None, dataset_prompt_text_kwargs=None, snapshot_images=False, batch_size=512, batch_gpu=None,
-                     metric_clip_path=None):
+                     metric_clip_path=None, text_encoder=None):
     """`--train_mode 0 --network_pkl teacher`: the teacher row of the tables under this project's own protocol.  The UNet of the model
     is sampled with classifier-free guidance `teacher_cfg` and a `teacher_steps`-step deterministic DDIM sampler
     (sd_util.teacher_sample) as the `G` of every metric -- the same prompts, seeds, VAE, detector resize and metric code as a
@@ -500,7 +507,7 @@ def evaluate_teacher(run_dir, dataset_kwargs, network_kwargs, device, metrics, i
     dtype = resolve_compute_dtype(dict(network_kwargs).get('compute_dtype'))
     unet, vae, noise_scheduler, text_encoder, tokenizer = load_sd15(
         pretrained_model_name_or_path=pretrained_model_name_or_path, pretrained_vae_model_name_or_path=None, device=device,
-        weight_dtype=dtype, lora_config=None, compute_dtype=dtype)
+        weight_dtype=dtype, lora_config=None, compute_dtype=dtype, **_text_encoder_opt(text_encoder))
     unet.eval().requires_grad_(False)
     dist.print0('Loading network completed')
     tag = f'teacher-ddim{int(teacher_steps):d}-cfg{float(teacher_cfg):g}'

@@ -88,6 +88,7 @@ OPTIONS = [
     (('--network_pkl',), dict(type=str, default=None, help='network-snapshot-*.pkl to evaluate with --train_mode 0, or "teacher": the teacher of --sd_model itself')),
     (('--teacher_steps',), dict(type=int, default=None, metavar='INT', help=f'DDIM steps of --network_pkl teacher  [default: {TEACHER_STEPS}] (not a reference option)')),
     (('--teacher_cfg',), dict(type=float, default=None, help=f'Guidance scale of --network_pkl teacher  [default: {TEACHER_CFG}] (not a reference option)')),
+    (('--text_encoder',), dict(type=click.Choice(['torch', 'hip']), default=None, help='CLIP text encoder: the PyTorch module, or the same weights on the HIP kernels  [default: $SIDLSG_TEXT_ENCODER, else torch] (not a reference option)')),
     (('--cfg_train_fake',), dict(type=float, default=1, show_default=True, help='kappa1: guidance scale when training the fake score')),
     (('--cfg_eval_fake',), dict(type=float, default=1, show_default=True, help='kappa2 = kappa3: guidance scale when evaluating the fake score')),
     (('--cfg_eval_real',), dict(type=float, default=1, show_default=True, help='kappa4: guidance scale when evaluating the teacher')),
@@ -177,6 +178,8 @@ def build_config(o):
              gradient_checkpointing=o.gradient_checkpointing, pretrained_model_name_or_path=o.sd_model,
              pretrained_vae_model_name_or_path=o.sd_model, metric_pt_path=o.metric_pt_path,
              metric_open_clip_path=o.metric_open_clip_path, metric_clip_path=o.metric_clip_path)
+    if o.get('text_encoder') is not None:      # (absent when not given: load_sd15 then decides, and the printed options stay as they were)
+        c.text_encoder = o.text_encoder
     if teacher:      # (absent otherwise: the printed options of every other run stay as they were)
         T = resolve_scheduler(o.sd_model).config.num_train_timesteps
         c.teacher_steps = TEACHER_STEPS if o.get('teacher_steps') is None else int(o.teacher_steps)

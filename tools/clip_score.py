@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """CLIP score of a directory of generated images against their prompts, with a local CLIP directory (sid_lsg_amd.clip).
-    python tools/clip_score.py --images out --text_prompts prompts.txt --clip /models/clip-vit-large-patch14 [--batch 64]
+    python tools/clip_score.py --images out --text_prompts prompts.txt --clip /models/clip-vit-large-patch14 [--batch 64] [--text_tower hip]
 `<seed:06d>.png` pairs with prompt line `seed % len(prompts)`: generate_onestep.py's own pairing.  The images go through
 metrics.resize_for_detector (256 x 256, Pillow LANCZOS arithmetic) first, so the number is the one `fid_clip_30k_full` reports for them."""
 import argparse
@@ -33,13 +33,18 @@ def main(argv=None):
     ap.add_argument('--text_prompts', required=True)
     ap.add_argument('--clip', required=True, help="a CLIP directory in the Hugging Face layout, or 'random:clip-<arch>'")
     ap.add_argument('--batch', type=int, default=64)
+    ap.add_argument('--text_tower', choices=('torch', 'hip'), default='torch', help='text tower of a CLIP directory: the PyTorch module, or the same weights on the HIP kernels')
     a = ap.parse_args(argv)
     import PIL.Image
     pairs = paired_files(a.images, read_prompts(a.text_prompts))
     if not pairs:
         raise SystemExit(f'{a.images}: no <seed:06d>.png files')
     dev = torch.device('cuda:0')
-    det = metrics.load_detector(a.clip, dev)
+    if metrics.is_clip_spec(a.clip):
+        from sid_lsg_amd.clip import load_clip
+        det = load_clip(a.clip, dev, text_tower=a.text_tower)
+    else:
+        det = metrics.load_detector(a.clip, dev)
     scores = []
     for i in range(0, len(pairs), a.batch):
         chunk = pairs[i:i + a.batch]
