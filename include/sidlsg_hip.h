@@ -403,6 +403,28 @@ int sidlsg_attn_causal_fwd_f32(const void* Q, const void* K, const void* V, void
 int sidlsg_text_embed(const void* ids, const float* tok, const float* pos, void* out, int B, int L, int D, int V, int P, void* stream);
 int sidlsg_text_embed_f32(const void* ids, const float* tok, const float* pos, void* out, int B, int L, int D, int V, int P, void* stream);
 
+/* ---- HPSv2 preprocessing (sid_lsg_amd/hps.py; open_clip's validation transform, which the hpsv2 package scores through) --------
+ * sidlsg_pil_patches_u8(_f32): Pillow's 8-bit BICUBIC resize of the shorter side to R, the R x R centre crop, ToTensor, Normalize and
+ *   the patch unfold in one launch.  images: uint8 [B][3][H][W].  The resampling is Pillow's ImagingResample in integers: per pass
+ *   clip8((2^21 + sum_k coeff[k] * in[first + k]) >> 22), horizontal pass first, the vertical pass on its 8-bit result; the
+ *   intermediate picture lives in LDS only.  The 22-bit coefficient banks are built on the host in double as Pillow builds them
+ *   (sid_lsg_amd.metrics.pil_crop_plan) and restricted to the crop: hbounds int32 [R][2] = (first source column, taps <= hk) of
+ *   cropped output column x, hcoef int32 [R][hk]; vbounds / vcoef / vk likewise for rows; band_rows: the largest number of source
+ *   rows the vertical windows of P consecutive output rows span.  A side that takes no pass has one tap of 1 << 22.  Then in fp32,
+ *   exactly: (p / 255 - mean_c) / std_c, an IEEE division, a subtraction and an IEEE division; bf16 rounds that once.  out: bf16 (_f32:
+ *   fp32) [B * (1 + (R/P)^2)][Kp], the layout sidlsg_clip_patches_u8 writes (column (c * P + py) * P + px; pad columns and the
+ *   class-token row zero).  One workgroup per (image, row of patches); its LDS tile is 3 * band_rows * roundup(R, 4) bytes of
+ *   intermediate picture behind a 3 KiB table and must fit 64 KiB: 3072 + 3 * band_rows * roundup(R, 4) <= 65536 (224 / 14 from
+ *   512^2: 38 rows, 28 KiB; from 1024^2: 78 rows, 54 KiB).  SIDLSG_EINVAL, and no launch, for a band beyond that limit, R % P != 0,
+ *   Kp % 8 != 0, Kp < 3*P*P, std == 0, null pointers, out not 16-byte or a table not 4-byte aligned, hk / vk / band_rows <= 0, 2^31 or
+ *   more input bytes or output elements.  Table entries are clamped to the image before use: a wrong bank cannot read outside it. */
+int sidlsg_pil_patches_u8(const void* images, void* out, int B, int H, int W, int R, int P, int Kp, const int* hbounds, const int* hcoef,
+                          int hk, const int* vbounds, const int* vcoef, int vk, int band_rows, float mean0, float mean1, float mean2,
+                          float std0, float std1, float std2, void* stream);
+int sidlsg_pil_patches_u8_f32(const void* images, void* out, int B, int H, int W, int R, int P, int Kp, const int* hbounds, const int* hcoef,
+                              int hk, const int* vbounds, const int* vcoef, int vk, int band_rows, float mean0, float mean1, float mean2,
+                              float std0, float std1, float std2, void* stream);
+
 /* ---- reference plugin op: torch_utils/ops/bias_act.cpp:32 `bias_act(x,b,xref,yref,dy,grad,dim,act,alpha,gain,clamp)`
  * act: 1 linear 2 relu 3 lrelu 4 tanh 5 sigmoid 6 elu 7 selu 8 softplus 9 swish (bias_act.py:23-33).
  * grad 0: out = clamp(act(x + b[(i/stepB)%sizeB]) * gain); grad 1: out = dL/dx from dy (x, b = saved inputs).

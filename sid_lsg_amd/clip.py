@@ -17,6 +17,9 @@ Face layout instead (`openai/clip-vit-large-patch14`, `laion/CLIP-ViT-g-14-laion
     `text.HipCLIPTextModel` on the HIP kernels; either way pooled at the first EOS token and projected.
   * `HipCLIPDetector`: the wrapper's call contract, finished by ops.clip_score (normalise both, concatenate, cosine).
   * `load_clip('random:clip-<arch>')`: seeded random networks with the hash tokenizer, for timing and tests (no weights offline).
+  * `load_open_clip(checkpoint, tokenizer_dir)`: the same towers from a checkpoint in open_clip's own layout (HPS_v2_compressed.pt,
+    open_clip_pytorch_model.bin), behind open_clip's validation transform: `HipCLIPVisionTower(..., preprocess='pil')` swaps the
+    float interpolation for Pillow's 8-bit BICUBIC resize + centre crop (ops.pil_patches, one launch, bit-equal to Pillow).
 There is no fallback: the image tower runs on the GPU kernels or raises.
 """
 import json
@@ -48,6 +51,17 @@ CLIP_ARCHS = {
     'vit-g-14': dict(projection_dim=1024,           # laion/CLIP-ViT-g-14-laion2B-s12B-b42K (what the reference's clip_score.py builds)
                      vision_config=dict(_V, hidden_size=1408, intermediate_size=6144, num_hidden_layers=40, num_attention_heads=16, hidden_act='gelu'),
                      text_config=dict(_T, hidden_size=1024, intermediate_size=4096, num_hidden_layers=24, num_attention_heads=16, hidden_act='gelu')),
+    'vit-h-14': dict(projection_dim=1024,           # laion/CLIP-ViT-H-14-laion2B-s32B-b79K, the model HPSv2 fine-tunes (head dim 80)
+                     vision_config=dict(_V, hidden_size=1280, intermediate_size=5120, num_hidden_layers=32, num_attention_heads=16, hidden_act='gelu'),
+                     text_config=dict(_T, hidden_size=1024, intermediate_size=4096, num_hidden_layers=24, num_attention_heads=16, hidden_act='gelu')),
+}
+PREPROCESS = ('interpolate', 'pil')      # ops.clip_patches (the reference's CLIP-score wrapper) / ops.pil_patches (open_clip's validation transform)
+# What a state dict in open_clip's layout does not say: head counts and the activation (widths are there to be checked against the shapes)
+OPEN_CLIP_ARCHS = {
+    'tiny': dict(vision_width=64, vision_heads=2, text_width=64, text_heads=2, act='gelu'),
+    'ViT-L-14': dict(vision_width=1024, vision_heads=16, text_width=768, text_heads=12, act='gelu'),
+    'ViT-H-14': dict(vision_width=1280, vision_heads=16, text_width=1024, text_heads=16, act='gelu'),
+    'ViT-g-14': dict(vision_width=1408, vision_heads=16, text_width=1024, text_heads=16, act='gelu'),
 }
 
 
@@ -105,12 +119,15 @@ class HipCLIPVisionTower:
     (not yet normalised).  `state`: fp32 masters under the transformers key names; the compute copies are bf16 (default) or, with
     compute_dtype=torch.float32, fp32 (the `_f32` kernel family, as HipUNet2DCondition).  Frozen: runs under no_grad only."""
 
-    def __init__(self, cfg, state, device, compute_dtype=None):
+    def __init__(self, cfg, state, device, compute_dtype=None, preprocess='interpolate'):
         self.cfg = cfg
         self.device = torch.device(device)
         self.compute_dtype = compute_dtype or BF16
         if self.compute_dtype not in (BF16, F32):
             raise ValueError(f'compute_dtype {compute_dtype}: expected torch.bfloat16 or torch.float32')
+        if preprocess not in PREPROCESS:
+            raise ValueError(f'preprocess {preprocess!r}: expected one of {PREPROCESS}')
+        self.preprocess = preprocess
         self.grid = cfg.image_size // cfg.patch_size
         self.tokens = 1 + self.grid ** 2
         self.masters = {}
@@ -163,12 +180,13 @@ class HipCLIPVisionTower:
 
     def embed(self, images_u8):
         """uint8 [B, 3, H, W] -> the token tensor [B * T, C] in front of pre_layrnorm: patch embeddings + position embeddings, the
-        class embedding in row 0 of every image -- one ops.clip_patches launch and one GEMM."""
+        class embedding in row 0 of every image -- one ops.clip_patches (preprocess='pil': ops.pil_patches) launch and one GEMM."""
         self._check(images_u8)
         B = images_u8.shape[0]
         if B not in self._res:
             self._res = {B: self.pos.repeat(B, 1)}                       # the cached res operand of the current batch size
-        a = ops.clip_patches(images_u8.contiguous(), self.cfg.image_size, self.cfg.patch_size, self.compute_dtype)
+        patches = ops.pil_patches if self.preprocess == 'pil' else ops.clip_patches
+        a = patches(images_u8.contiguous(), self.cfg.image_size, self.cfg.patch_size, self.compute_dtype)
         return ops.gemm(a, self.w_patch, res=self._res[B])
 
     def __call__(self, images_u8):
@@ -202,6 +220,11 @@ class HipCLIPDetector:
         self.vision, self.text_encoder, self.tokenizer, self.eos_token_id = vision, text_encoder, tokenizer, eos_token_id
         self.text_projection = text_projection                            # [F, hidden] fp32
         self.device = vision.device
+
+    @property
+    def preprocess(self):
+        """'interpolate' or 'pil': the image preprocessing of the tower (HipCLIPVisionTower)."""
+        return self.vision.preprocess
 
     @torch.no_grad()
     def text_embeds_from_ids(self, ids):
@@ -264,10 +287,11 @@ def _random_state(v, t, device, seed):
     return sd
 
 
-def load_clip(path, device, compute_dtype=None, seed=0, text_tower='torch'):
+def load_clip(path, device, compute_dtype=None, seed=0, text_tower='torch', preprocess='interpolate'):
     """A HipCLIPDetector from a local directory in the Hugging Face layout (module docstring), or from 'random:clip-<arch>'
     (CLIP_ARCHS; seeded weights, hash tokenizer).  text_tower: 'torch' (text.CLIPTextModel) or 'hip' (text.HipCLIPTextModel, the same
-    fp32 weights on the fp32 kernel family)."""
+    fp32 weights on the fp32 kernel family).  preprocess: 'interpolate' (the reference's CLIP-score wrapper) or 'pil' (open_clip's
+    validation transform, ops.pil_patches)."""
     if text_tower not in TEXT_ENCODERS:
         raise ValueError(f'text_tower {text_tower!r}: expected one of {TEXT_ENCODERS}')
     device = torch.device(device)
@@ -314,7 +338,143 @@ def load_clip(path, device, compute_dtype=None, seed=0, text_tower='torch'):
             setattr(tokenizer, attr, tokenizer.vocab[word])
         if tokenizer.eos_token_id != t.eos_token_id:
             raise ValueError(f'{cj}: text_config.eos_token_id = {t.eos_token_id}, but {vj} has <|endoftext|> = {tokenizer.eos_token_id}')
-    vision = HipCLIPVisionTower(v, state, device, compute_dtype)
+    vision = HipCLIPVisionTower(v, state, device, compute_dtype, preprocess)
+    text = text.float().requires_grad_(False).eval().to(device)
+    if text_tower == 'hip':
+        text = HipCLIPTextModel.from_torch(text)
+    return HipCLIPDetector(vision, text, state['text_projection.weight'].detach().to(device, F32), tokenizer, t.eos_token_id)
+
+
+# ---- checkpoints in open_clip's layout (HPS_v2_compressed.pt, open_clip_pytorch_model.bin, open_clip_model.safetensors) ---------------
+_OC_LAYER = (('ln_1', 'layer_norm1'), ('ln_2', 'layer_norm2'), ('attn.out_proj', 'self_attn.out_proj'), ('mlp.c_fc', 'mlp.fc1'),
+             ('mlp.c_proj', 'mlp.fc2'))
+
+
+def open_clip_state(obj):
+    """What torch.load / load_file returned -> the flat state dict: the `state_dict` entry when there is one, a leading `module.`
+    (DistributedDataParallel) stripped."""
+    if isinstance(obj, dict) and isinstance(obj.get('state_dict'), dict):
+        obj = obj['state_dict']
+    if not isinstance(obj, dict):
+        raise ValueError(f'open_clip checkpoint: expected a state dict, got {type(obj).__name__}')
+    return {(k[len('module.'):] if k.startswith('module.') else k): v for k, v in obj.items()}
+
+
+def open_clip_to_transformers(state, arch='ViT-H-14', where='open_clip checkpoint'):
+    """A state dict under open_clip's names -> (the same tensors under the transformers names the towers take, the config dict
+    parse_clip_config reads).  in_proj_{weight,bias} are split into q / k / v rows, visual.proj and text_projection transposed,
+    logit_scale and attn_mask dropped.  Widths, depth, patch and image size come from the shapes; head counts and the activation
+    from OPEN_CLIP_ARCHS[arch].  Raises, naming the key, on a missing key, and, naming the item, where shapes and table disagree."""
+    if arch not in OPEN_CLIP_ARCHS:
+        raise ValueError(f'arch {arch!r}: expected one of {sorted(OPEN_CLIP_ARCHS)}')
+    tab = OPEN_CLIP_ARCHS[arch]
+    state = open_clip_state(state)
+
+    def get(k, ndim=None):
+        if k not in state:
+            raise KeyError(f'{where}: {k} is missing')
+        t = state[k].detach().float()
+        if ndim is not None and t.dim() != ndim:
+            raise ValueError(f'{where}: {k} has shape {tuple(t.shape)}: expected {ndim} dimensions')
+        return t
+    out = {}
+    conv = get('visual.conv1.weight', 4)
+    C, P = conv.shape[0], conv.shape[2]
+    if C != tab['vision_width']:
+        raise ValueError(f'{where}: visual.conv1.weight has {C} output channels, arch {arch} has vision width {tab["vision_width"]}')
+    pos = get('visual.positional_embedding', 2)
+    grid = int(round((pos.shape[0] - 1) ** 0.5))
+    if grid * grid + 1 != pos.shape[0]:
+        raise ValueError(f'{where}: visual.positional_embedding has {pos.shape[0]} rows: not 1 + a square grid')
+    vproj, tproj = get('visual.proj', 2), get('text_projection', 2)
+    tok, tpos = get('token_embedding.weight', 2), get('positional_embedding', 2)
+    D = tok.shape[1]
+    if D != tab['text_width']:
+        raise ValueError(f'{where}: token_embedding.weight has width {D}, arch {arch} has text width {tab["text_width"]}')
+    if vproj.shape[1] != tproj.shape[1]:
+        raise ValueError(f'{where}: visual.proj projects to {vproj.shape[1]}, text_projection to {tproj.shape[1]}')
+    out['vision_model.embeddings.patch_embedding.weight'] = conv
+    out['vision_model.embeddings.class_embedding'] = get('visual.class_embedding', 1)
+    out['vision_model.embeddings.position_embedding.weight'] = pos
+    out['visual_projection.weight'] = vproj.t().contiguous()
+    out['text_projection.weight'] = tproj.t().contiguous()
+    out['text_model.embeddings.token_embedding.weight'] = tok
+    out['text_model.embeddings.position_embedding.weight'] = tpos
+    for oc, hf in (('visual.ln_pre', 'vision_model.pre_layrnorm'), ('visual.ln_post', 'vision_model.post_layernorm'),
+                   ('ln_final', 'text_model.final_layer_norm')):
+        for p in ('weight', 'bias'):
+            out[f'{hf}.{p}'] = get(f'{oc}.{p}', 1)
+    depth, dff = {}, {}
+    for side, src, dst, width in (('vision', 'visual.transformer.resblocks.', 'vision_model.encoder.layers.', C),
+                                  ('text', 'transformer.resblocks.', 'text_model.encoder.layers.', D)):
+        n = 0
+        while f'{src}{n}.attn.in_proj_weight' in state:
+            w, b = get(f'{src}{n}.attn.in_proj_weight', 2), get(f'{src}{n}.attn.in_proj_bias', 1)
+            if tuple(w.shape) != (3 * width, width) or tuple(b.shape) != (3 * width,):
+                raise ValueError(f'{where}: {src}{n}.attn.in_proj_weight / bias have shapes {tuple(w.shape)} / {tuple(b.shape)}, the width '
+                                 f'{width} says {(3 * width, width)} / {(3 * width,)}')
+            for j, name in enumerate('qkv'):
+                out[f'{dst}{n}.self_attn.{name}_proj.weight'] = w[j * width:(j + 1) * width].contiguous()
+                out[f'{dst}{n}.self_attn.{name}_proj.bias'] = b[j * width:(j + 1) * width].contiguous()
+            for oc, hf in _OC_LAYER:
+                for p in ('weight', 'bias'):
+                    out[f'{dst}{n}.{hf}.{p}'] = get(f'{src}{n}.{oc}.{p}')
+            n += 1
+        if n == 0:
+            raise KeyError(f'{where}: {src}0.attn.in_proj_weight is missing')
+        depth[side], dff[side] = n, out[f'{dst}0.mlp.fc1.weight'].shape[0]
+    for side, width in (('vision', C), ('text', D)):
+        if width % tab[f'{side}_heads']:
+            raise ValueError(f'{where}: arch {arch} has {tab[f"{side}_heads"]} {side} heads, which do not divide the width {width}')
+    cfg = dict(projection_dim=int(vproj.shape[1]),
+               vision_config=dict(hidden_size=C, intermediate_size=dff['vision'], num_hidden_layers=depth['vision'],
+                                  num_attention_heads=tab['vision_heads'], image_size=grid * P, patch_size=P, hidden_act=tab['act'],
+                                  layer_norm_eps=1e-5),
+               text_config=dict(hidden_size=D, intermediate_size=dff['text'], num_hidden_layers=depth['text'],
+                                num_attention_heads=tab['text_heads'], hidden_act=tab['act'], layer_norm_eps=1e-5, vocab_size=int(tok.shape[0]),
+                                max_position_embeddings=int(tpos.shape[0]), eos_token_id=int(tok.shape[0]) - 1))
+    return out, cfg
+
+
+def load_open_clip(checkpoint, tokenizer_dir, device, arch='ViT-H-14', compute_dtype=None, text_tower='torch', preprocess='pil'):
+    """A HipCLIPDetector from a checkpoint in open_clip's layout: `.pt` / `.bin` (torch.load(weights_only=True)) or `.safetensors`,
+    flat or under a `state_dict` entry (HPS_v2_compressed.pt, open_clip_pytorch_model.bin of the LAION repositories), mapped by
+    open_clip_to_transformers.  The tokenizer is CLIPBPETokenizer on vocab.json / merges.txt of `tokenizer_dir` (the tokenizer/
+    directory of any Stable Diffusion model has the vocabulary).  The image preprocessing is open_clip's validation transform
+    (preprocess='pil') unless asked otherwise."""
+    if text_tower not in TEXT_ENCODERS:
+        raise ValueError(f'text_tower {text_tower!r}: expected one of {TEXT_ENCODERS}')
+    name = str(checkpoint)
+    if not os.path.isfile(name):
+        raise FileNotFoundError(f'{name}: the open_clip checkpoint is missing')
+    if name.endswith('.safetensors'):
+        from safetensors.torch import load_file
+        raw = load_file(name)
+    else:
+        raw = torch.load(name, map_location='cpu', weights_only=True)
+    state, cfg = open_clip_to_transformers(raw, arch, name)
+    v, t = parse_clip_config(cfg, f'{name} (arch {arch})')
+    text = _text_tower(t, device)
+    want = dict(text.state_dict())
+    for k, w in want.items():
+        if k not in state:
+            raise KeyError(f'{name}: no tensor maps to {k}')
+        if tuple(state[k].shape) != tuple(w.shape):
+            raise ValueError(f'{name}: {k} has shape {tuple(state[k].shape)}, the configuration says {tuple(w.shape)}')
+    text.load_state_dict({k: state[k].float() for k in want})
+    vj, mt = os.path.join(str(tokenizer_dir), 'vocab.json'), os.path.join(str(tokenizer_dir), 'merges.txt')
+    for p in (vj, mt):
+        if not os.path.isfile(p):
+            raise FileNotFoundError(f'{p}: the tokenizer files are missing')
+    tokenizer = CLIPBPETokenizer.from_files(vj, mt, model_max_length=min(MAX_TEXT_LEN, t.max_position_embeddings), pad_token_id=t.eos_token_id)
+    for attr, word in (('bos_token_id', '<|startoftext|>'), ('eos_token_id', '<|endoftext|>')):
+        if word not in tokenizer.vocab:
+            raise KeyError(f'{vj}: {word} is missing from the vocabulary')
+        setattr(tokenizer, attr, tokenizer.vocab[word])
+    if tokenizer.eos_token_id != t.eos_token_id or max(tokenizer.vocab.values()) >= t.vocab_size:
+        raise ValueError(f'{vj}: <|endoftext|> = {tokenizer.eos_token_id} and {max(tokenizer.vocab.values()) + 1} entries, but {name} embeds '
+                         f'{t.vocab_size} tokens (the last one is <|endoftext|>)')
+    vision = HipCLIPVisionTower(v, state, device, compute_dtype, preprocess)
     text = text.float().requires_grad_(False).eval().to(device)
     if text_tower == 'hip':
         text = HipCLIPTextModel.from_torch(text)

@@ -1,4 +1,4 @@
-"""Evaluation metrics of the distilled generator: FID, CLIP scores and precision / recall.
+"""Evaluation metrics of the distilled generator: FID, CLIP scores, precision / recall and HPSv2.
 
 Reference: metrics/sid_metric_main.py:25-123 (registry, `calc_metric`, `report_metric`, the `fid30k_full` /
 `fid_clip_30k_full` / `fid_test` / `fid_clip_test` entries), metrics/sid_fid_and_clip.py:32-74 (the Frechet distance between
@@ -203,6 +203,107 @@ def _lanczos_coefficients(in_size, out_size):
     return K
 
 
+_BICUBIC_CACHE = {}
+PIL_PRECISION_BITS = 22
+
+
+def _bicubic_coefficients(in_size, out_size):
+    """The integer filter bank of Pillow's 8-bit BICUBIC resampling (Resample.c `precompute_coeffs` with the a = -0.5 cubic, support
+    2 * max(scale, 1) around (x + 0.5) * scale, the window [int(centre - support + 0.5), int(centre + support + 0.5)) clipped to the
+    image, weights summed in window order and normalised to sum 1; then `normalize_coeffs_8bpc`: round-half-away to 22 fractional
+    bits) -> (bounds int32 [out_size, 2] = (first input pixel, taps), coefficients int32 [out_size, ksize], zero behind the taps).
+    in_size == out_size: Pillow takes no pass over that side; the bank is then the one tap 1 << 22, which the integer pass maps to
+    the pixel itself."""
+    key = (in_size, out_size)
+    if key in _BICUBIC_CACHE:
+        return _BICUBIC_CACHE[key]
+    if in_size == out_size:
+        bounds = np.stack([np.arange(out_size), np.ones(out_size, dtype=np.int64)], 1).astype(np.int32)
+        coeffs = np.full((out_size, 1), 1 << PIL_PRECISION_BITS, dtype=np.int32)
+        _BICUBIC_CACHE[key] = (bounds, coeffs)
+        return bounds, coeffs
+    import math
+    a = -0.5
+
+    def cubic(x):
+        x = -x if x < 0.0 else x
+        if x < 1.0:
+            return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+        if x < 2.0:
+            return (((x - 5) * x + 8) * x - 4) * a
+        return 0.0
+    scale = in_size / out_size
+    fscale = max(scale, 1.0)
+    support = 2.0 * fscale
+    ksize = int(math.ceil(support)) * 2 + 1
+    ss = 1.0 / fscale
+    bounds = np.zeros((out_size, 2), dtype=np.int32)
+    coeffs = np.zeros((out_size, ksize), dtype=np.int32)
+    one = float(1 << PIL_PRECISION_BITS)
+    for xx in range(out_size):
+        center = (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), in_size) - xmin
+        w = [cubic((x + xmin - center + 0.5) * ss) for x in range(xmax)]
+        ww = 0.0
+        for v in w:                          # Pillow's own order: a pairwise sum can differ in the last bit
+            ww += v
+        if ww != 0.0:
+            w = [v / ww for v in w]
+        bounds[xx] = (xmin, xmax)
+        coeffs[xx, :xmax] = [int(-0.5 + v * one) if v < 0 else int(0.5 + v * one) for v in w]
+    _BICUBIC_CACHE[key] = (bounds, coeffs)
+    return bounds, coeffs
+
+
+def pil_resized_size(H, W, size):
+    """(height, width) torchvision's `Resize(size)` gives a PIL image of H x W: the shorter side becomes `size`, the longer one
+    int(size * long / short)."""
+    return (size, int(size * W / H)) if H <= W else (int(size * H / W), size)
+
+
+def pil_crop_offset(side, size):
+    """Where torchvision's `CenterCrop(size)` starts on a side of length `side`: Python's round, half to even."""
+    return int(round((side - size) / 2.0))
+
+
+def pil_crop_plan(H, W, size, patch=None):
+    """open_clip's validation transform `Resize(size, BICUBIC)` + `CenterCrop(size)` of an H x W image as the two coefficient banks
+    restricted to the crop, what sidlsg_pil_patches_u8 takes: dict(hbounds [size, 2], hcoef [size, hk], vbounds, vcoef (int32),
+    resized=(h, w), crop=(top, left), band_rows = the most source rows the vertical windows of `patch` consecutive output rows span)."""
+    h, w = pil_resized_size(H, W, size)
+    top, left = pil_crop_offset(h, size), pil_crop_offset(w, size)
+    hb, hc = _bicubic_coefficients(W, w)
+    vb, vc = _bicubic_coefficients(H, h)
+    hb, hc, vb, vc = (np.ascontiguousarray(t) for t in (hb[left:left + size], hc[left:left + size], vb[top:top + size], vc[top:top + size]))
+    plan = dict(hbounds=hb, hcoef=hc, vbounds=vb, vcoef=vc, resized=(h, w), crop=(top, left))
+    if patch is not None:
+        first = vb[0::patch, 0]
+        last = vb[patch - 1::patch]
+        plan['band_rows'] = int((last[:, 0] + last[:, 1] - first).max())
+    return plan
+
+
+def pil_resize_crop_u8(image_u8, size):
+    """uint8 [C, H, W] (numpy) -> uint8 [C, size, size]: Pillow's `Image.resize(BICUBIC)` of the shorter side to `size` and the centre
+    crop, restated in integers on the host (the arithmetic sidlsg_pil_patches_u8 runs; pinned against Pillow in
+    tests/test_hps_host.py).  Horizontal pass, then vertical, each clip8((sum + 2^21) >> 22)."""
+    image_u8 = np.asarray(image_u8)
+    C, H, W = image_u8.shape
+    plan = pil_crop_plan(H, W, size)
+    half = 1 << (PIL_PRECISION_BITS - 1)
+
+    def one_pass(src, bounds, coeffs):          # along the last axis
+        out = np.empty(src.shape[:-1] + (len(bounds),), dtype=np.uint8)
+        s = src.astype(np.int64)
+        for x, (x0, n) in enumerate(bounds):
+            acc = (s[..., x0:x0 + n] * coeffs[x, :n].astype(np.int64)).sum(-1) + half
+            out[..., x] = np.clip(acc >> PIL_PRECISION_BITS, 0, 255)
+        return out
+    t = one_pass(image_u8, plan['hbounds'], plan['hcoef'])                                     # [C, H, size]
+    return one_pass(t.transpose(0, 2, 1), plan['vbounds'], plan['vcoef']).transpose(0, 2, 1)    # [C, size, size]
+
+
 def resize_for_detector(images_u8, size=256):
     """uint8 NCHW -> uint8 NCHW at size x size with the arithmetic of the reference's `resize_images_in_tensor`
     (sid_metric_utils.py:353-375: per image `PIL.Image.resize((256, 256), Image.LANCZOS)`, back to uint8) -- on the device, for the
@@ -247,16 +348,22 @@ class MetricOptions:
 
     def __init__(self, G, prompts=None, resolution=512, init_timestep=625, detector=None, real_stats=None, open_clip_detector=None,
                  clip_score_fn=None, device=None, seed=0, batch_gen=4, detector_size=256, progress=None, dataset_kwargs=None,
-                 dataset=None, run_dir=None, metric_clip_path=None):
+                 dataset=None, run_dir=None, metric_clip_path=None, metric_hps_path=None, hps_prompts=None, hps_arch=None, hps_tokenizer=None,
+                 hps_detector=None):
         from .dnnlib_util import construct_class_by_name
         self.run_dir = run_dir
         if dataset is None and dataset_kwargs:
             dataset = construct_class_by_name(**dataset_kwargs)
         if dataset is None:
+            if prompts is None and hps_prompts is not None:
+                prompts = []                         # hpsv2 brings its own prompts
             if prompts is None:
                 raise ValueError('metrics need a prompt source: dataset_kwargs, dataset or prompts')
             dataset = _PromptList(prompts)
         self.dataset = dataset
+        # --metric_hps_path / --hps_prompts / --hps_arch / --hps_tokenizer: the scorer and the benchmark prompts of `hpsv2`
+        self.metric_hps_path, self.hps_prompts, self.hps_arch, self.hps_tokenizer = metric_hps_path, hps_prompts, hps_arch, hps_tokenizer
+        self.hps_detector = hps_detector            # a ready clip.HipCLIPDetector instead of the checkpoint (callers that hold one)
         self.G, self.resolution, self.init_timestep = G, resolution, init_timestep
         self.detector, self.real_stats, self.open_clip_detector, self.clip_score_fn = detector, real_stats, open_clip_detector, clip_score_fn
         self.metric_clip_path = metric_clip_path        # --metric_clip_path: the detector behind `clipscore30k` when clip_score_fn is None
@@ -482,7 +589,57 @@ def pr_test(opts):
     return dict(pr30k3_full_precision=precision, pr30k3_full_recall=recall)
 
 
+def compute_hps(opts, per_style):
+    """HPSv2 benchmark score (the reference's generate_hpsv2.py + hpsv2.evaluate, sid_lsg_amd.hps): for each of the four styles,
+    image i < per_style from prompt i of the style and the latent of torch.Generator(i) -- the same latents for every style --
+    through G, uint8, PIL's JPEG encoder and decoder in memory (the scorer of the reference reads the .jpg files), scored by the
+    open_clip checkpoint of --metric_hps_path on the HIP towers.  Rank-strided; every rank returns the same numbers."""
+    from . import hps
+    if not opts.hps_prompts or (opts.hps_detector is None and not opts.metric_hps_path):
+        raise ValueError('hpsv2 needs --metric_hps_path (HPS_v2_compressed.pt, or any checkpoint in open_clip\'s layout) and --hps_prompts '
+                         '(a directory with anime.json, concept-art.json, paintings.json, photo.json)')
+    prompts = hps.benchmark_prompts(opts.hps_prompts)
+    for style, p in prompts.items():
+        if len(p) < per_style:
+            raise ValueError(f'hpsv2: {style}.json of {opts.hps_prompts} has {len(p)} prompts, {per_style} are needed')
+    det = opts.hps_detector
+    if det is None:
+        from .clip import load_open_clip
+        det = load_open_clip(opts.metric_hps_path, opts.hps_tokenizer, opts.device, arch=opts.hps_arch or 'ViT-H-14')
+    lat = opts.resolution // 8
+    mine = list(range(opts.rank, per_style, opts.num_gpus))
+    scores = {}
+    for style in hps.STYLES:
+        vals = []
+        for i in range(0, len(mine), opts.batch_gen):
+            idx = mine[i:i + opts.batch_gen]
+            z = torch.stack([torch.randn([4, lat, lat], device=opts.device, generator=torch.Generator(opts.device).manual_seed(s)) for s in idx])
+            texts = [prompts[style][s] for s in idx]
+            with torch.no_grad():
+                img = opts.G(latents=z, contexts=texts, init_timesteps=opts.init_timestep * torch.ones(len(idx), device=opts.device, dtype=torch.long))
+            img = (img * 127.5 + 128).clamp(0, 255).to(torch.uint8)
+            vals += hps.score(det, hps.jpeg_round_trip(img), texts).cpu().tolist()
+            if opts.progress is not None:
+                opts.progress(len(vals) * opts.num_gpus, per_style)
+        scores[style] = vals
+    res = hps.aggregate(hps.gather_scores(scores, list(range(per_style)), opts.rank, opts.num_gpus, opts.device))
+    out = {f'hpsv2_{style}': res[style] for style in hps.STYLES}
+    out['hpsv2'] = res['Average']
+    return out
+
+
+@register_metric
+def hpsv2(opts):
+    return compute_hps(opts, 800)
+
+
+@register_metric
+def hpsv2_test(opts):
+    return compute_hps(opts, 16)
+
+
 NEEDS_IMAGES = ('pr30k3_full', 'pr_test')      # metrics that read the real images themselves: --data_stat cannot stand in
+HPS_METRICS = ('hpsv2', 'hpsv2_test')          # metrics that need neither the Inception detector nor real-set statistics
 
 
 def calc_metric(metric, **kwargs):

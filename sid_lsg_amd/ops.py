@@ -1980,6 +1980,44 @@ def clip_patches(images_u8, size, patch, dtype=BF16, mean=CLIP_MEAN, std=CLIP_ST
     return out
 
 
+_PIL_PLANS = {}
+PIL_LDS_LIMIT = 64 * 1024          # sidlsg_pil_patches_u8: 3072 + 3 * band_rows * roundup(size, 4) bytes of LDS per workgroup
+
+
+def _pil_plan(H, W, size, patch, device):
+    """The coefficient banks of metrics.pil_crop_plan on `device`, built once per (source size, target, patch, device)."""
+    key = (H, W, size, patch, str(device))
+    if key not in _PIL_PLANS:
+        from .metrics import pil_crop_plan
+        plan = pil_crop_plan(H, W, size, patch)
+        t = {k: torch.from_numpy(plan[k]).to(device) for k in ('hbounds', 'hcoef', 'vbounds', 'vcoef')}
+        _PIL_PLANS[key] = (t, plan['hcoef'].shape[1], plan['vcoef'].shape[1], plan['band_rows'])
+    return _PIL_PLANS[key]
+
+
+def pil_patches(images_u8, size, patch, dtype=BF16, mean=CLIP_MEAN, std=CLIP_STD):
+    """uint8 NCHW [B, 3, H, W] -> [B * (1 + (size / patch)^2), Kp] `dtype`, the layout of clip_patches, through open_clip's
+    validation transform instead of the float interpolation: Pillow's 8-bit BICUBIC resize of the shorter side to `size` (antialiased,
+    22-bit fixed point, two passes each rounded to 8 bits), centre crop, x / 255, (v - mean) / std (sidlsg_pil_patches_u8: one launch;
+    bit-equal to PIL + torchvision's ToTensor / Normalize).  What HPSv2's `preprocess_val` feeds its ViT-H/14."""
+    if images_u8.dim() != 4 or images_u8.shape[1] != 3:
+        raise RuntimeError(f'pil_patches: expected uint8 [B, 3, H, W] images, got {tuple(images_u8.shape)}')
+    if dtype not in (BF16, F32):
+        raise RuntimeError(f'pil_patches: output dtype {dtype}: expected bf16 or fp32')
+    if size % patch:
+        raise RuntimeError(f'pil_patches: image size {size} is not a multiple of the patch size {patch}')
+    B, _, H, W = images_u8.shape
+    t, hk, vk, band_rows = _pil_plan(H, W, int(size), int(patch), images_u8.device)
+    if 3072 + 3 * band_rows * ((size + 3) // 4 * 4) > PIL_LDS_LIMIT:
+        raise RuntimeError(f'pil_patches: {H} x {W} -> {size}: a band of {patch} output rows reads {band_rows} source rows, more than the '
+                           f'{PIL_LDS_LIMIT} bytes of LDS a workgroup stages them in')
+    kp = clip_patch_width(patch)
+    out = torch.empty((B * (1 + (size // patch) ** 2), kp), device=images_u8.device, dtype=dtype)
+    _fn('pil_patches_u8', dtype)(_p(_chk(images_u8, torch.uint8)), _p(out), B, H, W, int(size), int(patch), kp, _p(t['hbounds']), _p(t['hcoef']),
+                                 hk, _p(t['vbounds']), _p(t['vcoef']), vk, band_rows, *(float(m) for m in mean), *(float(s) for s in std), _s())
+    return out
+
+
 def gelu(x, mode):
     """MLP activation of a CLIP layer (sidlsg_gelu): mode 'quick_gelu' = x * sigmoid(1.702 x), 'gelu' = the exact erf GELU."""
     if mode not in ('quick_gelu', 'gelu'):

@@ -120,6 +120,15 @@ def _text_encoder_opt(kind):
     return {} if kind is None else dict(text_encoder=kind)
 
 
+def _hps_opt(metric_hps_path, hps_prompts, hps_arch, hps_tokenizer, sd_model):
+    """The HPSv2 options as calc_metric (and the evaluate_* functions) take them; nothing when no checkpoint was given.  The
+    tokenizer defaults to the tokenizer/ directory of the Stable Diffusion model: the same CLIP vocabulary."""
+    if metric_hps_path is None and hps_prompts is None:
+        return {}
+    return dict(metric_hps_path=metric_hps_path, hps_prompts=hps_prompts, hps_arch=hps_arch,
+                hps_tokenizer=hps_tokenizer if hps_tokenizer is not None else os.path.join(str(sd_model), 'tokenizer'))
+
+
 def training_loop(
     run_dir='.', dataset_kwargs={}, data_loader_kwargs={}, network_kwargs={}, loss_kwargs={},
     fake_score_optimizer_kwargs={}, g_optimizer_kwargs={}, augment_kwargs=None, seed=0, batch_size=512, batch_gpu=None,
@@ -131,8 +140,9 @@ def training_loop(
     dataset_prompt_text_kwargs={}, cfg_train_fake=1, cfg_eval_fake=1, cfg_eval_real=1, num_steps=1, train_mode=True,
     network_pkl=None, enable_xformers=True, gradient_checkpointing=False, resolution=512, on_iteration=None,
     rng_device=None, metric_real_stats=None, metric_num_test=None, deterministic=False, snapshot_images=False,
-    teacher_steps=None, teacher_cfg=None, text_encoder=None,
+    teacher_steps=None, teacher_cfg=None, text_encoder=None, metric_hps_path=None, hps_prompts=None, hps_arch=None, hps_tokenizer=None,
 ):
+    hps_kwargs = _hps_opt(metric_hps_path, hps_prompts, hps_arch, hps_tokenizer, pretrained_model_name_or_path)
     if not train_mode and network_pkl == TEACHER:
         return evaluate_teacher(run_dir=run_dir, dataset_kwargs=dataset_kwargs, network_kwargs=network_kwargs, device=device, metrics=metrics,
                                 init_timestep=init_timestep, metric_pt_path=metric_pt_path, metric_open_clip_path=metric_open_clip_path, metric_clip_path=metric_clip_path,
@@ -140,14 +150,14 @@ def training_loop(
                                 teacher_steps=TEACHER_STEPS if teacher_steps is None else teacher_steps,
                                 teacher_cfg=TEACHER_CFG if teacher_cfg is None else teacher_cfg, metric_real_stats=metric_real_stats,
                                 metric_num_test=metric_num_test, dataset_prompt_text_kwargs=dataset_prompt_text_kwargs,
-                                snapshot_images=snapshot_images, batch_size=batch_size, batch_gpu=batch_gpu, text_encoder=text_encoder)
+                                snapshot_images=snapshot_images, batch_size=batch_size, batch_gpu=batch_gpu, text_encoder=text_encoder, **hps_kwargs)
     if not train_mode:
         return evaluate_network(run_dir=run_dir, dataset_kwargs=dataset_kwargs, network_kwargs=network_kwargs, device=device, metrics=metrics,
                                 init_timestep=init_timestep, metric_pt_path=metric_pt_path, metric_open_clip_path=metric_open_clip_path, metric_clip_path=metric_clip_path,
                                 pretrained_model_name_or_path=pretrained_model_name_or_path, network_pkl=network_pkl, resolution=resolution,
                                 num_steps=num_steps, metric_real_stats=metric_real_stats, metric_num_test=metric_num_test,
                                 dataset_prompt_text_kwargs=dataset_prompt_text_kwargs, snapshot_images=snapshot_images,
-                                batch_size=batch_size, batch_gpu=batch_gpu, text_encoder=text_encoder)
+                                batch_size=batch_size, batch_gpu=batch_gpu, text_encoder=text_encoder, **hps_kwargs)
     num_steps = int(num_steps)
     if num_steps < 1:
         raise ValueError(f'num_steps={num_steps}: expected >= 1')
@@ -380,7 +390,7 @@ def training_loop(
                 extra = dict(num_test=metric_num_test) if metric_num_test is not None else {}
                 result = metric_main.calc_metric(metric, G=G_eval, resolution=resolution, init_timestep=init_timestep, detector=metric_pt_path,
                                                  real_stats=metric_real_stats, open_clip_detector=metric_open_clip_path, metric_clip_path=metric_clip_path, device=device,
-                                                 run_dir=run_dir, **msrc, **extra)
+                                                 run_dir=run_dir, **msrc, **extra, **hps_kwargs)
                 metric_main.report_metric(result, run_dir=run_dir, alpha=alpha,
                                           snapshot_pkl=os.path.join(run_dir, f'network-snapshot-{alpha:03f}-{cur_nimg // 1000:06d}.pkl') if run_dir else None)
                 for k, v in result.results.items():
@@ -430,7 +440,7 @@ def _evaluation_grid(msrc, vae, resolution, batch_size, batch_gpu, run_dir, devi
 def evaluate_network(run_dir, dataset_kwargs, network_kwargs, device, metrics, init_timestep, metric_pt_path, metric_open_clip_path,
                      pretrained_model_name_or_path, network_pkl, resolution, num_steps=1, metric_real_stats=None, metric_num_test=None,
                      dataset_prompt_text_kwargs=None, snapshot_images=False, batch_size=512, batch_gpu=None, metric_clip_path=None,
-                     text_encoder=None):
+                     text_encoder=None, metric_hps_path=None, hps_prompts=None, hps_arch=None, hps_tokenizer=None):
     """`--train_mode 0` (sid_training_loop.py:680-745): load the text encoder / VAE / scheduler, un-pickle the distilled generator
     from `network_pkl` (`pickle.load(f)['ema']`, the file the training loop writes at the snapshot ticks) and evaluate every metric
     with 1, 2 and 4 generation steps; each result goes to `<dirname(run_dir)>/<metric><number>_<steps>.txt` in the reference's
@@ -443,6 +453,7 @@ def evaluate_network(run_dir, dataset_kwargs, network_kwargs, device, metrics, i
     from .sd_util import sid_sd_sampler
     if not metrics:
         raise ValueError('--train_mode 0 evaluates metrics: pass --metrics')
+    hps_kwargs = _hps_opt(metric_hps_path, hps_prompts, hps_arch, hps_tokenizer, pretrained_model_name_or_path)
     if not network_pkl or not os.path.isfile(network_pkl):
         raise FileNotFoundError(f'--network_pkl {network_pkl!r}: a local network-snapshot-*.pkl is needed (there is no network to fetch one)')
     dtype = resolve_compute_dtype(dict(network_kwargs).get('compute_dtype'))
@@ -476,7 +487,7 @@ def evaluate_network(run_dir, dataset_kwargs, network_kwargs, device, metrics, i
             extra = dict(num_test=metric_num_test) if metric_num_test is not None else {}
             result = metric_main.calc_metric(metric, G=G_eval, resolution=resolution, init_timestep=init_timestep, detector=metric_pt_path,
                                              real_stats=metric_real_stats, open_clip_detector=metric_open_clip_path, metric_clip_path=metric_clip_path, device=device,
-                                             run_dir=run_dir, **msrc, **extra)
+                                             run_dir=run_dir, **msrc, **extra, **hps_kwargs)
             out[(metric, num_steps_eval)] = result
             if dist.get_rank() == 0:
                 print(result.results)
@@ -491,7 +502,7 @@ def evaluate_network(run_dir, dataset_kwargs, network_kwargs, device, metrics, i
 def evaluate_teacher(run_dir, dataset_kwargs, network_kwargs, device, metrics, init_timestep, metric_pt_path, metric_open_clip_path,
                      pretrained_model_name_or_path, resolution, teacher_steps=TEACHER_STEPS, teacher_cfg=TEACHER_CFG, metric_real_stats=None,
                      metric_num_test=None, dataset_prompt_text_kwargs=None, snapshot_images=False, batch_size=512, batch_gpu=None,
-                     metric_clip_path=None, text_encoder=None):
+                     metric_clip_path=None, text_encoder=None, metric_hps_path=None, hps_prompts=None, hps_arch=None, hps_tokenizer=None):
     """`--train_mode 0 --network_pkl teacher`: the teacher row of the tables under this project's own protocol.  The UNet of the model
     is sampled with classifier-free guidance `teacher_cfg` and a `teacher_steps`-step deterministic DDIM sampler
     (sd_util.teacher_sample) as the `G` of every metric -- the same prompts, seeds, VAE, detector resize and metric code as a
@@ -504,6 +515,7 @@ def evaluate_teacher(run_dir, dataset_kwargs, network_kwargs, device, metrics, i
     from .sd_util import teacher_sample
     if not metrics:
         raise ValueError('--train_mode 0 evaluates metrics: pass --metrics')
+    hps_kwargs = _hps_opt(metric_hps_path, hps_prompts, hps_arch, hps_tokenizer, pretrained_model_name_or_path)
     dtype = resolve_compute_dtype(dict(network_kwargs).get('compute_dtype'))
     unet, vae, noise_scheduler, text_encoder, tokenizer = load_sd15(
         pretrained_model_name_or_path=pretrained_model_name_or_path, pretrained_vae_model_name_or_path=None, device=device,
@@ -532,7 +544,7 @@ def evaluate_teacher(run_dir, dataset_kwargs, network_kwargs, device, metrics, i
         extra = dict(num_test=metric_num_test) if metric_num_test is not None else {}
         result = metric_main.calc_metric(metric, G=G_eval, resolution=resolution, init_timestep=init_timestep, detector=metric_pt_path,
                                          real_stats=metric_real_stats, open_clip_detector=metric_open_clip_path, metric_clip_path=metric_clip_path, device=device,
-                                         run_dir=run_dir, **msrc, **extra)
+                                         run_dir=run_dir, **msrc, **extra, **hps_kwargs)
         metric_main.report_metric(result, run_dir=run_dir, snapshot_pkl=os.path.join(run_dir, tag) if run_dir else tag)
         out[metric] = result
     return out
