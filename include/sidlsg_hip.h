@@ -132,7 +132,10 @@ int sidlsg_set_deterministic(int on);
 
 /* ---- normalisation (HBM bound) ------------------------------------------------------------
  * torch.nn.GroupNorm(32, C, eps)+SiLU of ResnetBlock2D.norm1/norm2, Transformer2DModel.norm,
- * conv_norm_out; torch.nn.LayerNorm of BasicTransformerBlock.norm1-3. */
+ * conv_norm_out; torch.nn.LayerNorm of BasicTransformerBlock.norm1-3.
+ * Mean offsets: the operators are tested (tests/norm_cases.py, profiles/norm_offset_accuracy.txt) with a per-group / per-row
+ * |mean| / std of up to 30 at the operator tolerances in fp32 and in bf16, and of up to 100 at 4x those tolerances in fp32.
+ * How large the offsets of real SD UNet / VAE activations are has not been measured. */
 /* backward: dres (may be NULL, same shape as x) is the gradient reaching x through its other consumer (the residual /
  * shortcut branch of the block that owns the norm); dx = norm-backward + dres in the same pass. */
 int sidlsg_groupnorm_ws_floats(int B, int HW, int C, int G); /* host: workspace size in floats, <0 on bad shape */

@@ -7,7 +7,7 @@
 //
 // GroupNorm is split in two kernels so that the grid (B x pixel-chunks) fills all 256 CUs even
 // at batch 1-2, with a deterministic two-level reduction (no atomics):
-//   gn_stats : per (sample, pixel chunk) -> per-group partial (sum, sumsq)
+//   gn_stats : per (sample, pixel chunk) -> per-group partial (sum, sumsq); fp32 activations: a second, centred pass
 //   gn_apply : folds the partials, y = act((x-mean)*rstd*gamma+beta), writes (mean, rstd)
 // Backward:
 //   gn_bwd_stats : per (sample, chunk) per-CHANNEL partial (sum dy'*xhat, sum dy') -- these
@@ -33,15 +33,37 @@ struct GnGeom {
     int C, HW, G, cpg, C8, rows, nch, ppb;  // ppb: pixels per block (chunk)
 };
 
-template <typename T>
-__global__ void gn_stats_kernel(const T* __restrict__ x, float* __restrict__ part, GnGeom g) {
-    extern __shared__ float sm[];  // [rows][C][2]
+// Statistics of the two-kernel path.  bf16 activations: one pass of raw sums, var = sumsq / n - mean^2.  That loses
+// |mean / std|^2 * 2^-24 of the variance: 2e-4 at most at a group mean of 30 standard deviations, far inside the bf16 tolerances
+// (tests/test_gpu_ops.py test_groupnorm_distinct_groups), as in the one-pass bf16 kernels below.  In the fp32 mode the same formula
+// gave 1e-4 .. 4e-4 of y and dx at 30 standard deviations and 1e-3 .. 1e-2 at 100, against the mode's 2e-5 / 5e-5
+// (tests/test_gpu_fp32.py, profiles/norm_offset_accuracy.txt), so fp32 activations take a second, CENTRED pass: gn_stats_kernel
+// runs again with the pivot K = (raw sum) / n of the (sample, group) -- folded from the first pass's partials by every block, in the
+// same order as gn_apply_kernel folds them, hence the same bits -- and writes partial sums of x - K and (x - K)^2 behind the first
+// set (the forward uses 2 x B * nch * G * 2 of the workspace's B * nch * (C + G) * 2 floats).  gn_apply_kernel then forms
+// mean = K + a / n, var = c / n - (a / n)^2, where a / n is a rounding-sized correction.  (A cheaper pivot -- the group's first
+// element, in one pass -- met the operator tolerances too, but cost the bf16 forward +10% / +4% / +5% at 64x64 x 320 / x 640 /
+// 32x32 x 1920 (profiles/gn_stats_offset_ab.txt) and, in fp32, moved the loss curve of a whole training loop off its golden by more
+// than that test allows: an outlying first element costs accuracy that raw sums keep.)
+constexpr int GN_FOLD = 8;
+DEVFN void gn_fold_partials(const float* __restrict__ p, const GnGeom& g, float* sm);
+
+template <typename T, bool CENTRED = false>      // CENTRED: the second pass; `raw` = the first pass's partials of all samples
+__global__ void gn_stats_kernel(const T* __restrict__ x, const float* __restrict__ raw, float* __restrict__ part, GnGeom g) {
+    extern __shared__ float sm[];  // [rows][C][2]; CENTRED: the fold's 2 * G * (1 + GN_FOLD) floats behind them
     const int b = blockIdx.y, chunk = blockIdx.x;
     const int cc = threadIdx.x % g.C8, rl = threadIdx.x / g.C8;
     const int p0 = chunk * g.ppb, p1 = min(g.HW, p0 + g.ppb);
-    float s[8], q[8];
+    float s[8], q[8], k[8];        // k: the pivot of each channel's group (0: the subtraction folds away)
 #pragma unroll
-    for (int e = 0; e < 8; e++) s[e] = q[e] = 0.f;
+    for (int e = 0; e < 8; e++) s[e] = q[e] = k[e] = 0.f;
+    if constexpr (CENTRED) {
+        float* fs = sm + (size_t)g.rows * g.C * 2;
+        gn_fold_partials(raw + (size_t)b * g.nch * g.G * 2, g, fs);
+        const float n = (float)g.cpg * (float)g.HW;
+#pragma unroll
+        for (int e = 0; e < 8; e++) k[e] = fs[(cc * 8 + e) / g.cpg] / n;
+    }
     const T* xb = x + (size_t)b * g.HW * g.C + cc * 8;
     int p = p0 + rl;
     // GN_U independent 16-byte loads in flight per thread (8 measured slower than 4: 37 -> 44 us on 16 x 4096 x 320 -- the
@@ -53,13 +75,13 @@ __global__ void gn_stats_kernel(const T* __restrict__ x, float* __restrict__ par
 #pragma unroll
         for (int u = 0; u < GN_U; u++)
 #pragma unroll
-            for (int e = 0; e < 8; e++) { const float f = v[u][e]; s[e] += f; q[e] += f * f; }
+            for (int e = 0; e < 8; e++) { const float f = v[u][e] - k[e]; s[e] += f; q[e] += f * f; }
     }
     for (; p < p1; p += g.rows) {
         float v[8];
         ldv8<T>(xb + (size_t)p * g.C, v);
 #pragma unroll
-        for (int e = 0; e < 8; e++) { const float f = v[e]; s[e] += f; q[e] += f * f; }
+        for (int e = 0; e < 8; e++) { const float f = v[e] - k[e]; s[e] += f; q[e] += f * f; }
     }
     float* row = sm + (size_t)rl * g.C * 2;
 #pragma unroll
@@ -80,7 +102,6 @@ __global__ void gn_stats_kernel(const T* __restrict__ x, float* __restrict__ par
 // sm[0..G) / sm[G..2G) = sum over the nch chunks of one sample's per-group partial pairs p[k][grp][2].  All threads load
 // (a serial loop of nch dependent-latency loads in G threads cost several us per block); the order of the additions is
 // fixed by the block size, so the result is deterministic.  sm needs 2*G*GN_FOLD floats; ends with a barrier.
-constexpr int GN_FOLD = 8;
 DEVFN void gn_fold_partials(const float* __restrict__ p, const GnGeom& g, float* sm) {
     const int slices = min(GN_FOLD, max(1, (int)blockDim.x / g.G));
     float* tmp = sm + 2 * g.G;                                 // [slices][G][2]
@@ -107,17 +128,22 @@ __global__ void gn_apply_kernel(const T* __restrict__ x, const float* __restrict
                                 const float* __restrict__ gamma, const float* __restrict__ beta,
                                 T* __restrict__ y, float* __restrict__ stats, GnGeom g, float eps, int act,
                                 const float* __restrict__ gamma1, const float* __restrict__ beta1, int split) {
-    extern __shared__ float sm[];  // mean[G], rstd[G]
+    extern __shared__ float sm[];  // mean[G], rstd[G] (+ the fold's scratch; fp32: a second such area for the centred partials)
+    constexpr bool CENTRED = std::is_same<T, float>::value;          // fp32 activations: two sets of partials (see gn_stats_kernel)
     const int b = blockIdx.y, chunk = blockIdx.x;
     if (gamma1 && b >= split) { gamma = gamma1; beta = beta1; }      // grouped launch: samples [split, B) belong to the second network
     // fold the nch per-chunk partials of every group: all threads load (one (sum, sumsq) pair each, independent loads), LDS
     // float adds combine them -- a serial loop of nch dependent-latency loads in G threads cost several us per block
     gn_fold_partials(part + (size_t)b * g.nch * g.G * 2, g, sm);
+    float* sc2 = sm + 2 * g.G * (1 + GN_FOLD);
+    if constexpr (CENTRED) gn_fold_partials(part + ((size_t)gridDim.y * g.nch + (size_t)b * g.nch) * g.G * 2, g, sc2);
     for (int grp = threadIdx.x; grp < g.G; grp += blockDim.x) {      // each group is read and overwritten by one thread
-        const float a = sm[grp], c = sm[g.G + grp];
         const float n = (float)g.cpg * (float)g.HW;
-        const float mean = a / n;
-        const float var = fmaxf(c / n - mean * mean, 0.f);
+        const float K = CENTRED ? sm[grp] / n : 0.f;                 // the second pass's pivot: the same fold, the same bits
+        const float a = CENTRED ? sc2[grp] : sm[grp], c = CENTRED ? sc2[g.G + grp] : sm[g.G + grp];
+        const float m = a / n;
+        const float mean = K + m;
+        const float var = fmaxf(c / n - m * m, 0.f);
         const float rstd = rsqrtf(var + eps);
         sm[grp] = mean; sm[g.G + grp] = rstd;
         if (chunk == 0 && stats) { stats[((size_t)b * g.G + grp) * 2] = mean; stats[((size_t)b * g.G + grp) * 2 + 1] = rstd; }
@@ -1141,9 +1167,13 @@ static int groupnorm_fwd_t(const void* x, const float* gamma, const float* beta,
         }
     }
     const int threads = g.C8 * g.rows;
+    constexpr bool centred = std::is_same<T, float>::value;
     SIDLSG_LAUNCH(gn_stats_kernel<T>, dim3(g.nch, B), dim3(threads), (size_t)g.rows * C * 2 * sizeof(float), s,
-                       (const T*)x, ws, g);
-    SIDLSG_LAUNCH((gn_apply_kernel<T, F8>), dim3(g.nch, B), dim3(threads), (size_t)2 * G * (1 + GN_FOLD) * sizeof(float), s,
+                       (const T*)x, (const float*)nullptr, ws, g);
+    if constexpr (centred)
+        SIDLSG_LAUNCH((gn_stats_kernel<T, true>), dim3(g.nch, B), dim3(threads), ((size_t)g.rows * C * 2 + 2 * G * (1 + GN_FOLD)) * sizeof(float), s,
+                           (const T*)x, (const float*)ws, ws + (size_t)B * g.nch * G * 2, g);
+    SIDLSG_LAUNCH((gn_apply_kernel<T, F8>), dim3(g.nch, B), dim3(threads), (size_t)2 * G * (1 + GN_FOLD) * (centred ? 2 : 1) * sizeof(float), s,
                        (const T*)x, ws, gamma, beta, (T*)y, stats, g, eps, silu, gamma1, beta1, B / 2);
     return sidlsg_last_error();
 }

@@ -16,6 +16,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import norm_cases as nc
+
 pytestmark = pytest.mark.gpu
 F32, F64 = torch.float32, torch.float64
 TOL = 2e-5
@@ -160,6 +162,45 @@ def test_layernorm_f32(dev, rows, C):
     close(xd.grad, xr.grad, 5e-5, 'dx')
     close(gm.grad, gr.grad, 5e-5, 'dgamma')
     close(bm.grad, br.grad, 5e-5, 'dbeta')
+
+
+def _norm_f32_distinct(dev, run, c, rel, factor, what):
+    """Distinct statistics per (sample, group) / per row (tests/norm_cases.py) in the fp32 mode: y and dx judged per block with `rel`,
+    dgamma / dbeta globally, at `factor` times this file's operator tolerances.  Prints the figures (profiles/norm_offset_accuracy.txt)."""
+    gm = torch.nn.Parameter(c['gam'].to(dev)); gm.grad = torch.zeros_like(gm)
+    bm = torch.nn.Parameter(c['bet'].to(dev)); bm.grad = torch.zeros_like(bm)
+    xd = c['x'].to(dev).requires_grad_()
+    y = run(xd, gm, bm)
+    assert y.dtype == F32
+    y.backward(c['dy'].to(dev))
+    ref = c['ref']
+    errs = dict(y=rel(y, ref['y']), dx=rel(xd.grad, ref['dx']),
+                dgamma=nc.global_rel_err(gm.grad, ref['dgamma']), dbeta=nc.global_rel_err(bm.grad, ref['dbeta']))
+    print(f'NORM_ACCURACY hip_fp32 {what} ' + ' '.join(f'{k}={v:.3g}' for k, v in errs.items()))
+    for k, v in errs.items():
+        assert v <= factor * nc.TOL_F32[k], f'{what}: {k} rel err {v:.3g} > {factor * nc.TOL_F32[k]:.3g}'
+
+
+@pytest.mark.parametrize('name,offsets,factor', nc.OFFSET_SETS_F32, ids=[s[0] for s in nc.OFFSET_SETS_F32])
+@pytest.mark.parametrize('case', nc.GN_CASES_F32, ids=nc.gn_id)
+def test_groupnorm_f32_distinct_groups(dev, case, name, offsets, factor):
+    """Per-group |mean| / std up to 30 at the operator tolerances (2e-5 forward, 5e-5 backward) and up to 100 at 4x (an error relative
+    to |mean| grows linearly with the offset; torch's own fp32 result does, tests/test_norm_cases_host.py): the statistics must not be
+    formed as sumsq / n - mean^2 from raw fp32 sums, which loses |mean / std|^2 * 2^-24 of the variance."""
+    from sid_lsg_amd import ops
+    B, HW, C, G, silu, eps, fork = case
+    c = nc.gn_case(case, offsets, F32)
+    assert TOL == nc.TOL_F32['y']
+    _norm_f32_distinct(dev, lambda xd, gm, bm: ops.group_norm(xd, gm, bm, G, eps, silu), c, lambda got, ref: nc.group_rel_err(got, ref, G),
+                       factor, f'gn {nc.gn_id(case)} {name}')
+
+
+@pytest.mark.parametrize('name,offsets,factor', nc.OFFSET_SETS_F32, ids=[s[0] for s in nc.OFFSET_SETS_F32])
+@pytest.mark.parametrize('rows,C', nc.LN_CASES_F32)
+def test_layernorm_f32_distinct_rows(dev, rows, C, name, offsets, factor):
+    from sid_lsg_amd import ops
+    c = nc.ln_case((rows, C), offsets, F32)
+    _norm_f32_distinct(dev, lambda xd, gm, bm: ops.layer_norm(xd, gm, bm, 1e-5), c, nc.row_rel_err, factor, f'ln {rows}-{C} {name}')
 
 
 def attn_ref(q, k, v, heads):

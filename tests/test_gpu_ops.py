@@ -13,6 +13,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import norm_cases as nc
+
 pytestmark = pytest.mark.gpu
 
 BF16, F32 = torch.bfloat16, torch.float32
@@ -336,6 +338,66 @@ def test_groupnorm(dev, B, HW, C, G, silu):
     close(xd.grad, xr.grad, 1.5e-2, 'dx')
     close(gm.grad, gr.grad, 3e-3, 'dgamma')
     close(bm.grad, br.grad, 3e-3, 'dbeta')
+
+
+def _norm_distinct(dev, run, c, rel, what):
+    """Shared by the distinct-statistics tests (tests/norm_cases.py): `run(x, gm, bm)` -> (y, loss) on the device; y and dx are judged
+    per (sample, group) block / per row with `rel`, dgamma / dbeta globally, at the tolerances of test_groupnorm / test_layernorm."""
+    gm = torch.nn.Parameter(c['gam'].to(dev)); gm.grad = torch.zeros_like(gm)
+    bm = torch.nn.Parameter(c['bet'].to(dev)); bm.grad = torch.zeros_like(bm)
+    xd = c['x'].to(dev).requires_grad_()
+    y, loss = run(xd, gm, bm)
+    loss.backward()
+    ref = c['ref']
+    errs = dict(y=rel(y, ref['y']), dx=rel(xd.grad, ref['dx']),
+                dgamma=nc.global_rel_err(gm.grad, ref['dgamma']), dbeta=nc.global_rel_err(bm.grad, ref['dbeta']))
+    print(f'NORM_ACCURACY hip_bf16 {what} ' + ' '.join(f'{k}={v:.3g}' for k, v in errs.items()))
+    for k, v in errs.items():
+        assert v <= nc.TOL_BF16[k], f'{what}: {k} rel err {v:.3g} > {nc.TOL_BF16[k]}'
+
+
+def _groupnorm_distinct(dev, case):
+    from sid_lsg_amd import ops
+    B, HW, C, G, silu, eps, fork = case
+    c = nc.gn_case(case, nc.OFFSETS_BF16, BF16)
+
+    def run(xd, gm, bm):
+        dy = c['dy'].to(dev).float()
+        if fork:       # the residual-branch gradient is summed inside the backward kernel
+            y, xk = ops.group_norm(xd, gm, bm, G, eps, silu, fork=True)
+            return y, (y.float() * dy).sum() + (xk.float() * c['dk'].to(dev).float()).sum()
+        y = ops.group_norm(xd, gm, bm, G, eps, silu)
+        return y, (y.float() * dy).sum()
+    _norm_distinct(dev, run, c, lambda got, ref: nc.group_rel_err(got, ref, G), 'gn ' + nc.gn_id(case))
+
+
+@pytest.mark.parametrize('case', nc.GN_CASES_BF16, ids=nc.gn_id)
+def test_groupnorm_distinct_groups(dev, case):
+    """Every (sample, group) has its own scale (2^-2 .. 2^2) and its own mean (0, +-3, +-30 standard deviations), and dy makes both
+    projection terms of the backward O(1): a wrong group or sample index, or a lost s1 / s2 term, misses these bounds by more than
+    10x (tests/test_norm_cases_host.py).  fp64 reference; shapes: the smallest that reach each kernel family (norm_cases.py)."""
+    _groupnorm_distinct(dev, case)
+
+
+@pytest.mark.parametrize('case', nc.GN_CASES_DET, ids=nc.gn_id)
+def test_groupnorm_distinct_groups_deterministic(dev, case):
+    """Deterministic mode sends a trainable layer's backward to the two-kernel path at shapes that otherwise take the one-pass kernel
+    (a few pixel rows per chunk: a geometry nothing else reaches)."""
+    from sid_lsg_amd import ops
+    with ops.deterministic():
+        _groupnorm_distinct(dev, case)
+
+
+@pytest.mark.parametrize('rows,C', nc.LN_CASES_BF16)
+def test_layernorm_distinct_rows(dev, rows, C):
+    """test_groupnorm_distinct_groups for LayerNorm: one (scale, mean offset, dy projection) per row, judged per row."""
+    from sid_lsg_amd import ops
+    c = nc.ln_case((rows, C), nc.OFFSETS_BF16, BF16)
+
+    def run(xd, gm, bm):
+        y = ops.layer_norm(xd, gm, bm, 1e-5)
+        return y, (y.float() * c['dy'].to(dev).float()).sum()
+    _norm_distinct(dev, run, c, nc.row_rel_err, f'ln {rows}-{C}')
 
 
 def test_groupnorm_group_kernels_all_shapes(dev):
