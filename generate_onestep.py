@@ -20,6 +20,9 @@ encoder on the HIP kernels (sid_lsg_amd.vae.HipAutoencoderKLEncoder) and re-nois
 `--network teacher` samples the teacher itself instead of a snapshot: the UNet of `--repo_id` under classifier-free guidance
 (`--guidance_scale`, default 7.5) and a deterministic DDIM sampler of `--teacher_steps` steps (default 50;
 sid_lsg_amd.sd_util.teacher_sample), with the same seeds, prompts and file names -- the teacher row of the SiD-LSG tables.
+`--teacher_sampler {ddim,dpmpp2m}`, `--teacher_spacing {leading,trailing,linspace}`, `--teacher_eta`, `--guidance_rescale` and
+`--negative_prompt` choose the solver family of sd_util.teacher_sample_solver instead (DPM-Solver++ 2M, stochastic DDIM, 'trailing'
+spacing with guidance rescale as SD 2.1 768-v is usually run); with none of them given the DDIM path above runs unchanged.
 """
 import math
 import os
@@ -33,7 +36,7 @@ import torch
 from sid_lsg_amd import distributed as dist
 from sid_lsg_amd.preview import save_png
 from sid_lsg_amd.sd_util import (TEACHER, TEACHER_CFG, TEACHER_STEPS, check_prediction_type, load_sd15, load_vae_encoder, sid_sd_sampler,
-                                 teacher_sample)
+                                 teacher_sample, teacher_sample_solver)
 
 
 class StackedRandomGenerator:
@@ -72,6 +75,26 @@ def teacher_options(network_pkl, teacher_steps, guidance_scale):
                                    'in --num_steps_eval steps')
         return None
     return (TEACHER_STEPS if teacher_steps is None else teacher_steps), (TEACHER_CFG if guidance_scale is None else guidance_scale)
+
+
+def teacher_solver_options(network_pkl, teacher_sampler=None, teacher_spacing=None, teacher_eta=None, guidance_rescale=None,
+                           negative_prompt=None):
+    """-> None when none of the solver options of --network teacher is given (the deterministic DDIM path of teacher_sample runs, as
+    before they existed), else the keywords of sd_util.teacher_sample_solver except negative_contexts, plus the negative prompt; the
+    options with a snapshot, and combinations the schedule refuses, are usage errors."""
+    given = [f for f, v in (('--teacher_sampler', teacher_sampler), ('--teacher_spacing', teacher_spacing), ('--teacher_eta', teacher_eta),
+                            ('--guidance_rescale', guidance_rescale), ('--negative_prompt', negative_prompt)) if v is not None]
+    if not given:
+        return None
+    if network_pkl != TEACHER:
+        raise click.UsageError(f'{" / ".join(given)} apply to --network {TEACHER} only')
+    solver = 'ddim' if teacher_sampler is None else teacher_sampler
+    if solver == 'dpmpp2m' and teacher_eta:
+        raise click.UsageError(f'--teacher_eta {teacher_eta:g}: --teacher_sampler dpmpp2m is deterministic (eta applies to ddim)')
+    if solver == 'ddim' and teacher_spacing == 'linspace':
+        raise click.UsageError('--teacher_spacing linspace: not reproduced for --teacher_sampler ddim (use leading or trailing)')
+    return dict(solver=solver, spacing=teacher_spacing, eta=0.0 if teacher_eta is None else float(teacher_eta),
+                guidance_rescale=0.0 if guidance_rescale is None else float(guidance_rescale), negative_prompt=negative_prompt)
 
 
 IMAGE_EXTENSIONS = ('.png', '.jpg', '.jpeg')
@@ -150,6 +173,11 @@ def init_image_options(network_pkl, init_images, strength, sample_posterior, num
 @click.option('--custom_seed', type=bool, default=False, show_default=True, help='Prompt i <-> i-th seed of the list instead of seed value')
 @click.option('--teacher_steps', type=click.IntRange(min=1), default=None, help=f'DDIM steps of --network {TEACHER}  [default: {TEACHER_STEPS}]')
 @click.option('--guidance_scale', type=float, default=None, help=f'Classifier-free guidance scale of --network {TEACHER}  [default: {TEACHER_CFG}]')
+@click.option('--teacher_sampler', type=click.Choice(['ddim', 'dpmpp2m']), default=None, help=f'Solver of --network {TEACHER}: DDIM or DPM-Solver++ 2M  [default: ddim]')
+@click.option('--teacher_spacing', type=click.Choice(['leading', 'trailing', 'linspace']), default=None, help=f'Timestep spacing of --network {TEACHER}  [default: the timestep_spacing of --repo_id]')
+@click.option('--teacher_eta', type=click.FloatRange(min=0), default=None, help='DDIM eta: 0 deterministic, 1 ancestral; noise from the per-seed generator, after z  [default: 0]')
+@click.option('--guidance_rescale', type=click.FloatRange(min=0, max=1), default=None, help=f'Guidance rescale phi (Lin et al. 2024) of --network {TEACHER}  [default: 0]')
+@click.option('--negative_prompt', type=str, default=None, help=f"Prompt of the unconditional half of --network {TEACHER}  [default: '']")
 @click.option('--init_images', type=str, default=None, metavar='DIR', help='Image-to-image: PNG/JPEG files (sorted by name); sample idx starts from file idx mod len(files)')
 @click.option('--strength', type=click.FloatRange(min=0, max=1, min_open=True), default=None,
               help='With --init_images: share of the --num_steps_eval steps that run, k = N - ceil(S N) is the entry step; a one-step '
@@ -157,11 +185,13 @@ def init_image_options(network_pkl, init_images, strength, sample_posterior, num
 @click.option('--sample_posterior', type=bool, default=None, help='With --init_images: sample the VAE posterior (eps from the per-seed generator, after z) instead of its mean  [default: False]')
 @click.option('--text_encoder', type=click.Choice(['torch', 'hip']), default=None, help='CLIP text encoder: the PyTorch module, or the same weights on the HIP kernels  [default: $SIDLSG_TEXT_ENCODER, else torch] (not a reference option)')
 def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, init_timestep, text_prompts, repo_id, resolution, use_fp16,
-         enable_compress_npz, num_steps_eval, custom_seed, teacher_steps, guidance_scale, init_images, strength, sample_posterior, text_encoder):
+         enable_compress_npz, num_steps_eval, custom_seed, teacher_steps, guidance_scale, init_images, strength, sample_posterior, text_encoder,
+         teacher_sampler, teacher_spacing, teacher_eta, guidance_rescale, negative_prompt):
     text_encoder_kind = text_encoder
     if resolution % 8:
         raise click.BadParameter(f'{resolution}: must be a multiple of 8', param_hint='--resolution')
     teacher = teacher_options(network_pkl, teacher_steps, guidance_scale)
+    solver_kw = teacher_solver_options(network_pkl, teacher_sampler, teacher_spacing, teacher_eta, guidance_rescale, negative_prompt)
     img2img = init_image_options(network_pkl, init_images, strength, sample_posterior, num_steps_eval)
     dist.init()
     device = torch.device('cuda')
@@ -183,7 +213,11 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
         del _
         check_prediction_type(G_ema, sched)       # a v snapshot with an epsilon --repo_id (or the reverse) would sample garbage
     else:
-        dist.print0(f'Sampling the teacher "{repo_id}": DDIM {teacher[0]} steps, guidance scale {teacher[1]:g}')
+        if solver_kw is None:
+            dist.print0(f'Sampling the teacher "{repo_id}": DDIM {teacher[0]} steps, guidance scale {teacher[1]:g}')
+        else:
+            dist.print0(f'Sampling the teacher "{repo_id}": {solver_kw["solver"]} {teacher[0]} steps, spacing {solver_kw["spacing"] or "of the model"}, '
+                        f'eta {solver_kw["eta"]:g}, guidance scale {teacher[1]:g}, rescale {solver_kw["guidance_rescale"]:g}')
         G_ema, vae, sched, text_encoder, tokenizer = load_sd15(repo_id, repo_id, device, torch.bfloat16, text_encoder=text_encoder_kind)
         G_ema.eval().requires_grad_(False)
         if num_steps_eval != 1:
@@ -215,7 +249,14 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
             eps = rnd.randn([len(batch), 4, lat, lat], device=device) if sample else None
             i2i = dict(init_latents=vae_encoder.encode_latents(pixels, eps=eps), start_step=start_step)
         with torch.no_grad():
-            if teacher is not None:
+            if teacher is not None and solver_kw is not None:
+                kw = {k: v for k, v in solver_kw.items() if k != 'negative_prompt'}
+                neg = None if solver_kw['negative_prompt'] is None else [solver_kw['negative_prompt']] * len(batch)
+                images = teacher_sample_solver(unet=G_ema, latents=z, contexts=prompts, noise_scheduler=sched, text_encoder=text_encoder,
+                                               tokenizer=tokenizer, resolution=resolution, guidance_scale=teacher[1],
+                                               num_inference_steps=teacher[0], return_images=True, vae=vae, negative_contexts=neg,
+                                               randn=lambda shape: rnd.randn(list(shape), device=device), **kw)
+            elif teacher is not None:
                 images = teacher_sample(unet=G_ema, latents=z, contexts=prompts, noise_scheduler=sched, text_encoder=text_encoder,
                                         tokenizer=tokenizer, resolution=resolution, guidance_scale=teacher[1],
                                         num_inference_steps=teacher[0], return_images=True, vae=vae)

@@ -262,6 +262,25 @@ int sidlsg_step_renoise_bwd(const void* g, const float* gxtn, const float* s0, c
 int sidlsg_ddim_step(const float* eps, const float* xt, const float* s0, const float* s1, const float* s0p, const float* s1p,
                      void* out, float* xtn, float* x0, int B, int C, int HW, int Ce, int Cp, int dup, float kappa, int mode,
                      void* stream);
+/* solver_step (csrc/solver.hip): one step boundary of the teacher's solver family (DDIM with any eta, DPM-Solver++ 2M) as one launch,
+ * forward only.  eps / xt / s0 / s1 / dup / kappa / mode / Ce / Cp as ddim_step; coef [B][4] = (c_x, c_cur, c_prev, c_n) of
+ * scheduler.solver_schedule; x0p fp32 NCHW the x0 prediction of the step before (may be NULL); noise fp32 NCHW (may be NULL); scale
+ * [B] the guidance-rescale factors of cfg_rescale_stats (may be NULL).  All in fp32:
+ *   e = u + kappa*(c-u) when dup = 2, else eps;  e = e*scale[b] when scale is given;  x0 by `mode` as cfg_x0 (bit-equal to it when
+ *   scale is NULL);  x_t = c_x*x_s + c_cur*x0 + c_prev*x0p + c_n*noise: one rounded product, then one fma per term in this order; a
+ *   NULL x0p / noise term is not formed (the bits of a zero tensor with a zero coefficient)
+ *   -> out NHWC [dup*B][HW][Cp] activations (both halves equal, channels C.. zero; NULL on the last step), xtn fp32 NCHW, x0 fp32
+ *   NCHW (may be NULL; the next step's x0p).
+ * The coefficients live on the device, so the caller says whether this step's c_prev is non-zero: need_prev != 0 with a NULL x0p,
+ * dup other than 1 / 2, mode other than 1 / 2, a NULL eps / xt / s0 / s1 / coef / xtn -> SIDLSG_EINVAL, nothing launched. */
+int sidlsg_solver_step(const float* eps, const float* xt, const float* s0, const float* s1, const float* coef, const float* x0p,
+                       const float* noise, const float* scale, void* out, float* xtn, float* x0, int B, int C, int HW, int Ce, int Cp,
+                       int dup, float kappa, int mode, int need_prev, void* stream);
+/* cfg_rescale_stats: scale[b] = phi*std(c_b)/std(g_b) + 1 - phi, g = u + kappa*(c-u), for eps [2*B][HW][Ce>=C] fp32 ([uncond ; cond]):
+ * the guidance rescale of Lin et al. 2024 (diffusers' rescale_noise_cfg) as one factor per sample.  Unbiased standard deviations over
+ * the C*HW real channels, centred (two passes), summed in a fixed order without atomics; std(g_b) = 0 gives the factor 1 (diffusers
+ * yields NaN).  C*HW < 2 or a NULL pointer -> SIDLSG_EINVAL. */
+int sidlsg_cfg_rescale_stats(const float* eps, float* scale, int B, int C, int HW, int Ce, float kappa, float phi, void* stream);
 
 /* ---- losses with closed-form gradients (sid_training_loop.py:423-445, 508-530) -------------
  * Per-sample NaN filtering is done in-kernel (a sample containing NaN contributes 0 and gets zero
@@ -515,6 +534,9 @@ int sidlsg_step_renoise_bwd_f32(const void* g, const float* gxtn, const float* s
 int sidlsg_ddim_step_f32(const float* eps, const float* xt, const float* s0, const float* s1, const float* s0p, const float* s1p,
                          void* out, float* xtn, float* x0, int B, int C, int HW, int Ce, int Cp, int dup, float kappa, int mode,
                          void* stream);
+int sidlsg_solver_step_f32(const float* eps, const float* xt, const float* s0, const float* s1, const float* coef, const float* x0p,
+                           const float* noise, const float* scale, void* out, float* xtn, float* x0, int B, int C, int HW, int Ce,
+                           int Cp, int dup, float kappa, int mode, int need_prev, void* stream);
 int sidlsg_timestep_embed_f32(const long long* t, void* out, int B, int dim, void* stream);
 int sidlsg_silu_fwd_f32(const void* x, void* y, long long n, void* stream);
 int sidlsg_silu_bwd_f32(const void* x, const void* dy, void* dx, long long n, void* stream);

@@ -1701,6 +1701,60 @@ def ddim_step(eps, xt, s0, s1, s0p, s1p, kappa, act_dtype=BF16, prediction_type=
     return out, xtn, x0
 
 
+solver_launches = dict(solver_step=0, cfg_rescale_stats=0)   # launches issued through the two wrappers below (tests count them)
+
+
+def cfg_rescale_stats(eps, channels, kappa, phi):
+    """The per-sample guidance-rescale factors of Lin et al. 2024 (sidlsg_cfg_rescale_stats): eps [2*B,HW,Ce] fp32 ([uncond ; cond])
+    -> scale [B] fp32 = phi*std(c)/std(g) + 1 - phi, g = u + kappa*(c - u), the unbiased standard deviations over the `channels`
+    real channels of a sample (centred, fixed summation order; std(g) = 0 gives 1).  Forward only."""
+    if torch.is_grad_enabled() and eps.requires_grad:
+        raise RuntimeError('cfg_rescale_stats is forward only: call it under torch.no_grad() (the teacher sampler is not differentiated)')
+    if eps.dim() != 3 or eps.shape[0] % 2 or eps.shape[2] < channels:
+        raise RuntimeError(f'cfg_rescale_stats: eps {tuple(eps.shape)} is not a [2*B, HW, >={channels}] pair of halves')
+    B = eps.shape[0] // 2
+    scale = torch.empty(B, device=eps.device, dtype=F32)
+    lib.sidlsg_cfg_rescale_stats(_p(_chk(eps, F32)), _p(scale), B, int(channels), eps.shape[1], eps.shape[2], float(kappa), float(phi), _s())
+    solver_launches['cfg_rescale_stats'] += 1
+    return scale
+
+
+def solver_step(eps, xt, s0, s1, coef, kappa, act_dtype=BF16, prediction_type='epsilon', x0p=None, noise=None, scale=None, last=False,
+                x0_out=None, need_prev=None):
+    """One step boundary of the teacher's solver family (sidlsg_solver_step): the teacher's output eps [dup*B,HW,Ce] fp32 at s
+    ([uncond ; cond] when dup = 2) and x_s fp32 NCHW -> guided e (times `scale` [B] when given: ops.cfg_rescale_stats), x0 prediction,
+    x_t = c_x*x_s + c_cur*x0 + c_prev*x0p + c_n*noise with coef [B,4] = (c_x, c_cur, c_prev, c_n) of scheduler.solver_schedule, x0p
+    the x0 prediction of the step before and noise fresh N(0, 1) values (both fp32 NCHW, both optional: an absent term is not formed).
+    `need_prev`: whether this step's c_prev is non-zero (the coefficients are on the device and are not read back); default: whether
+    x0p was given.  True without x0p is refused by the kernel's host side.  `x0_out`: a buffer for the x0 prediction (the sampler
+    ping-pongs two), else a new tensor.
+    Returns (next network input NHWC [dup*B,H,W,8] of `act_dtype`, or None when `last`; x_t fp32 NCHW; the x0 prediction fp32 NCHW).
+    Forward only."""
+    tensors = (eps, xt, s0, s1, coef, x0p, noise, scale)
+    if torch.is_grad_enabled() and any(torch.is_tensor(v) and v.requires_grad for v in tensors):
+        raise RuntimeError('solver_step is forward only: call it under torch.no_grad() (the teacher sampler is not differentiated)')
+    B, C, H, W = xt.shape
+    if eps.dim() != 3 or eps.shape[1] != H * W or eps.shape[0] not in (B, 2 * B) or eps.shape[2] < C:
+        raise RuntimeError(f'solver_step: eps {tuple(eps.shape)} does not match x_t {tuple(xt.shape)}')
+    for name, v, n in (('s0', s0, B), ('s1', s1, B), ('coef', coef, 4 * B), ('scale', scale, B)):
+        if v is not None and v.numel() != n:
+            raise RuntimeError(f'solver_step: {name} has {v.numel()} elements, expected {n} for a batch of {B}')
+    for name, v in (('x0p', x0p), ('noise', noise), ('x0_out', x0_out)):
+        if v is not None and tuple(v.shape) != tuple(xt.shape):
+            raise RuntimeError(f'solver_step: {name} {tuple(v.shape)} does not match x_t {tuple(xt.shape)}')
+    dup = eps.shape[0] // B
+    out = None if last else torch.empty((dup * B, H, W, 8), device=xt.device, dtype=act_dtype)
+    xtn = torch.empty_like(xt)
+    x0 = torch.empty_like(xt) if x0_out is None else x0_out
+    opt = lambda v: None if v is None else _chk(v, F32)  # noqa: E731
+    _fn('solver_step', act_dtype)(_p(_chk(eps, F32)), _p(_chk(xt, F32)), _p(_chk(s0, F32)), _p(_chk(s1, F32)), _p(_chk(coef, F32)),
+                                  _p(opt(x0p)), _p(opt(noise)), _p(opt(scale)), _p(out), _p(xtn), _p(_chk(x0, F32)), B, C, H * W,
+                                  eps.shape[2], 8, dup, float(kappa), prediction_mode(prediction_type),
+                                  int(x0p is not None if need_prev is None else need_prev), _s())
+    solver_launches['solver_step'] += 1
+    return out, xtn, x0
+
+
 class _GLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, yr, yf, alpha, scale):

@@ -64,6 +64,111 @@ def ddim_schedule(scheduler, config_dict, num_inference_steps):
     return t, abar_t ** 0.5, (1 - abar_t) ** 0.5, abar_prev ** 0.5, (1 - abar_prev) ** 0.5
 
 
+SOLVERS = ('ddim', 'dpmpp2m')
+SPACINGS = ('leading', 'trailing', 'linspace')
+
+
+def solver_tables(scheduler, config_dict, num_inference_steps, solver='dpmpp2m', spacing=None, eta=0.0):
+    """The timesteps and update coefficients of an N-step teacher sampler for sidlsg_solver_step.  One step from s (now) to t
+    (target) is  x_t = c_x*x_s + c_cur*x0_s + c_prev*x0_r + c_n*xi  with x0_s the x0 prediction at s, x0_r that of the step before
+    and xi fresh N(0, 1) noise.  With abar the scheduler's alphas_cumprod, alpha = sqrt(abar), sigma = sqrt(1 - abar),
+    lambda = (ln abar - ln(1 - abar)) / 2, T = num_train_timesteps and numpy's half-to-even `round`:
+
+      solver 'ddim' (Song et al. 2021, any eta >= 0), spacing 'leading' (ddim_schedule's arithmetic) or 'trailing'
+      (t_i = round(T - i*T/N) - 1); the target of step i is t_i - T//N, below 0 the final abar (1 if set_alpha_to_one else abar[0]):
+        sigma_eta = eta*sqrt((1 - abar_t)/(1 - abar_s))*sqrt(1 - abar_s/abar_t)   (0 on a step onto abar = 1)
+        c_x = sqrt(sigma_t^2 - sigma_eta^2)/sigma_s;  c_cur = alpha_t - c_x*alpha_s;  c_prev = 0;  c_n = sigma_eta
+      solver 'dpmpp2m' (DPM-Solver++ 2M, Lu et al. 2022: data prediction, order 2, midpoint, final sigma = 0), spacing 'leading'
+      (t_i = (N - i)*(T//(N + 1)) + steps_offset), 'trailing' (as above) or 'linspace' (round(linspace(0, T - 1, N + 1)) reversed,
+      last entry dropped); the target of step i is t_{i+1}, that of the last step the clean state abar = 1:
+        h = lambda_t - lambda_s;  A = alpha_t*(1 - exp(-h));  c_x = sigma_t/sigma_s;  c_n = 0
+        step 0:          c_cur = A;  c_prev = 0
+        steps 1 .. N-2:  r0 = (lambda_s - lambda_r)/h with r the point before s;  c_cur = A*(1 + 0.5/r0);  c_prev = -A*0.5/r0
+      any step onto abar = 1 (dpmpp2m's last one): the row (0, 1, 0, 0) exactly -- x_t is the x0 prediction, no lambda = inf is formed.
+
+    These rules restate diffusers 0.27.2's DDIMScheduler and DPMSolverMultistepScheduler; agreement with the package is not pinned
+    by a test.  `config_dict` as ddim_schedule (steps_offset, set_alpha_to_one, timestep_spacing); `spacing` None takes its
+    timestep_spacing.  All arithmetic is fp64 from the scheduler's own fp32 alphas_cumprod.
+    -> numpy (timesteps int64[N], alpha f64[N], sigma f64[N] at t_i, coef f64[N, 4] = (c_x, c_cur, c_prev, c_n)); solver_schedule
+    rounds them to fp32 once.  Raises ValueError naming the argument it refuses."""
+    import numpy as np
+    c = dict(config_dict or {})
+    if solver not in SOLVERS:
+        raise ValueError(f'solver={solver!r}: expected one of {SOLVERS}')
+    if spacing is None:
+        spacing = c.get('timestep_spacing', 'leading')
+    if spacing not in SPACINGS:
+        raise ValueError(f'spacing={spacing!r}: expected one of {SPACINGS}')
+    if solver == 'ddim' and spacing == 'linspace':
+        raise ValueError("spacing='linspace': not reproduced for solver='ddim' (use 'leading' or 'trailing')")
+    eta = float(eta)
+    if not eta >= 0 or eta == float('inf'):
+        raise ValueError(f'eta={eta}: expected a finite value >= 0')
+    if solver == 'dpmpp2m' and eta != 0:
+        raise ValueError(f"eta={eta}: solver='dpmpp2m' is deterministic (eta applies to solver='ddim')")
+    T = int(scheduler.config.num_train_timesteps)
+    N = int(num_inference_steps)
+    if N < 1:
+        raise ValueError(f'num_inference_steps={N}: expected at least 1')
+    if N > T:
+        raise ValueError(f'num_inference_steps={N}: more than num_train_timesteps={T}')
+    offset = int(c.get('steps_offset', 0))
+    i = np.arange(N, dtype=np.int64)
+    if spacing == 'trailing':
+        t = np.round(T - i.astype(np.float64) * (T / N)).astype(np.int64) - 1
+    elif spacing == 'linspace':
+        t = np.round(np.linspace(0, T - 1, N + 1))[::-1][:-1].astype(np.int64)
+    elif solver == 'ddim':
+        t = (N - 1 - i) * (T // N) + offset
+    else:
+        t = (N - i) * (T // (N + 1)) + offset
+    if spacing == 'leading' and (offset < 0 or t[0] >= T):
+        raise ValueError(f'steps_offset={offset}: the first timestep {int(t[0])} is outside [0, {T}) for num_inference_steps={N}')
+    if t.min() < 0 or t.max() >= T or np.any(np.diff(t) >= 0):
+        raise ValueError(f'num_inference_steps={N}: the timesteps of solver={solver!r}, spacing={spacing!r} are not strictly decreasing '
+                         f'inside [0, {T})')
+    abar_dev = scheduler.alphas_cumprod
+    abar = abar_dev.detach().cpu().to(torch.float64).numpy()
+    a_s = abar[t]
+    if solver == 'ddim':
+        prev = t - T // N
+        final = 1.0 if c.get('set_alpha_to_one', True) else abar[0]
+        a_t = np.where(prev >= 0, abar[np.maximum(prev, 0)], final)
+    else:
+        a_t = np.append(abar[t[1:]], 1.0)
+    coef = np.zeros((N, 4), dtype=np.float64)
+    lam = lambda a: 0.5 * (np.log(a) - np.log1p(-a))  # noqa: E731
+    for k in range(N):
+        if a_t[k] == 1.0:
+            coef[k] = (0.0, 1.0, 0.0, 0.0)
+            continue
+        al_s, sg_s, al_t, sg_t = np.sqrt(a_s[k]), np.sqrt(1 - a_s[k]), np.sqrt(a_t[k]), np.sqrt(1 - a_t[k])
+        if solver == 'ddim':
+            sg_eta = eta * np.sqrt((1 - a_t[k]) / (1 - a_s[k])) * np.sqrt(max(1 - a_s[k] / a_t[k], 0.0))
+            if sg_eta > sg_t:
+                raise ValueError(f'eta={eta}: sigma_eta exceeds sigma_t at step {k} (t = {int(t[k])})')
+            cx = np.sqrt(sg_t ** 2 - sg_eta ** 2) / sg_s
+            coef[k] = (cx, al_t - cx * al_s, 0.0, sg_eta)
+        else:
+            h = lam(a_t[k]) - lam(a_s[k])
+            A = -al_t * np.expm1(-h)
+            if k == 0:
+                coef[k] = (sg_t / sg_s, A, 0.0, 0.0)
+            else:
+                r0 = (lam(a_s[k]) - lam(a_s[k - 1])) / h
+                coef[k] = (sg_t / sg_s, A * (1 + 0.5 / r0), -A * 0.5 / r0, 0.0)
+    return t.copy(), np.sqrt(a_s), np.sqrt(1 - a_s), coef
+
+
+def solver_schedule(scheduler, config_dict, num_inference_steps, solver='dpmpp2m', spacing=None, eta=0.0):
+    """solver_tables rounded to fp32 once, as the tensors sidlsg_solver_step takes:
+    -> (timesteps Long[N], s0 f32[N], s1 f32[N], coef f32[N, 4]) on the scheduler's device, s0 / s1 being alpha / sigma at t_i."""
+    t, al, sg, coef = solver_tables(scheduler, config_dict, num_inference_steps, solver=solver, spacing=spacing, eta=eta)
+    dev = scheduler.alphas_cumprod.device
+    f32 = lambda v: torch.from_numpy(v).to(torch.float32).to(dev)  # noqa: E731
+    return torch.from_numpy(t).to(dev), f32(al), f32(sg), f32(coef)
+
+
 class DDPMScheduler:
     def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, prediction_type='epsilon',
                  beta_schedule='scaled_linear'):

@@ -5,6 +5,8 @@
     sid_sd_denoise   :214-274  add_noise -> (CFG-batched) UNet -> guided eps or x0 prediction
     teacher_sample   (no counterpart: the reference's tables take the teacher row from diffusers' pipeline)  guided N-step DDIM
                                sampling of the teacher itself, one sidlsg_ddim_step launch per step boundary
+    teacher_sample_solver  (no counterpart)  the same under DPM-Solver++ 2M or DDIM with any eta, 'leading' / 'trailing' / 'linspace'
+                               spacing and guidance rescale, one sidlsg_solver_step launch per step boundary
 
 `unet` must be a HipUNet2DCondition (bare or wrapped in DistributedDataParallel, as the reference's loop passes it):
 the whole glue runs as fused HIP kernels (sidlsg_noisy_input / UNet / sidlsg_cfg_x0: no per-sample python loop, no
@@ -17,7 +19,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
-from .scheduler import SD_SAMPLING_CONFIG, DDPMScheduler, ddim_schedule
+from .scheduler import SD_SAMPLING_CONFIG, DDPMScheduler, ddim_schedule, solver_schedule
 from .text import TEXT_CONFIGS, CLIPBPETokenizer, CLIPTextModel, HashTokenizer, HipCLIPTextModel, resolve_text_encoder
 from .unet import CONFIGS, HipUNet2DCondition
 
@@ -437,6 +439,69 @@ def teacher_sample(unet, latents, contexts, noise_scheduler, text_encoder, token
         for i in range(n):
             eps = net.forward_nhwc(xin, tt[i], ctx)
             xin, xt, _ = ops.ddim_step(eps, xt, s0[i], s1[i], s0p[i], s1p[i], guidance_scale, dt, prediction_type=pt, last=i == n - 1)
+        if not return_images:
+            return xt
+        upcast = vae.dtype == torch.float16 and getattr(vae.config, 'force_upcast', False)
+        if upcast:
+            vae.to(dtype=torch.float32)
+        images = vae.decode(xt.to(vae.dtype) / vae.config.scaling_factor, return_dict=False)[0]
+        if upcast:
+            vae.to(dtype=torch.float16)
+        return images.to(torch.float32)
+
+
+def teacher_sample_solver(unet, latents, contexts, noise_scheduler, text_encoder, tokenizer, resolution, guidance_scale=TEACHER_CFG,
+                          num_inference_steps=TEACHER_STEPS, return_images=False, vae=None, schedule_config=None, solver='dpmpp2m',
+                          spacing=None, eta=0.0, guidance_rescale=0.0, negative_contexts=None, randn=None):
+    """The teacher under the solvers it is usually run with: `solver` 'dpmpp2m' (DPM-Solver++ 2M) or 'ddim' (any `eta` >= 0), timestep
+    `spacing` 'leading' / 'trailing' / 'linspace' (None: the model's timestep_spacing), guidance rescale `guidance_rescale` (phi of
+    Lin et al. 2024; 0 = plain classifier-free guidance) and `negative_contexts` in place of '' in the unconditional half.  The
+    timesteps and coefficients are scheduler.solver_schedule's.  Same loop shape as teacher_sample: contexts encoded once, x_T =
+    latents, per step one UNet pass on the [uncond ; cond] batch and one sidlsg_solver_step launch (with phi != 0 and guidance, one
+    sidlsg_cfg_rescale_stats launch before it), tables as device tensors indexed by the step number, the two x0 history buffers
+    swapped per step: nothing waits for the device between the first UNet pass and the result.  `randn(shape) -> fp32 tensor` supplies
+    xi once per step whose c_n is non-zero, in step order (default: torch.randn on the latents' device).
+    -> the final latent x_0 fp32 NCHW, or (return_images) the decoded images as sid_sd_sampler returns them."""
+    _require_hip(unet)
+    check_prediction_type(unet, noise_scheduler)
+    net = _unwrap(unet)
+    dt, pt = net.compute_dtype, noise_scheduler.config.prediction_type
+    schedule_config = sampling_config_of(noise_scheduler, schedule_config)
+    phi = float(guidance_rescale)
+    if not 0 <= phi <= 1:
+        raise ValueError(f'guidance_rescale={guidance_rescale}: expected a value in [0, 1]')
+    with torch.no_grad():
+        z = latents.to(torch.float32).contiguous()
+        b, dev = z.shape[0], z.device
+        ts, s0, s1, coef = solver_schedule(noise_scheduler, schedule_config, num_inference_steps, solver=solver, spacing=spacing, eta=eta)
+        flags = (coef.cpu() != 0).tolist()          # per step: which terms exist (read before the loop; the loop itself reads nothing back)
+        ts, s0, s1, coef = (v.to(dev) for v in (ts, s0, s1, coef))
+        n = ts.numel()
+        guided = guidance_scale != 1
+        dup = 2 if guided else 1
+        if negative_contexts is not None and not torch.is_tensor(negative_contexts) and len(negative_contexts) != b:
+            raise ValueError(f'negative_contexts: {len(negative_contexts)} prompts for a batch of {b}')
+        ctx = encode_contexts(contexts, text_encoder, tokenizer, dev).to(dt)
+        if guided:
+            neg = [''] * b if negative_contexts is None else negative_contexts
+            ctx = torch.cat([encode_contexts(neg, text_encoder, tokenizer, dev).to(dt), ctx])
+        ctx = ctx.contiguous()
+        if randn is None:
+            randn = lambda shape: torch.randn(shape, device=dev, dtype=torch.float32)  # noqa: E731
+        tt = ts[:, None].expand(n, dup * b).contiguous()
+        s0, s1 = (v[:, None].expand(n, b).contiguous() for v in (s0, s1))
+        coef = coef[:, None, :].expand(n, b, 4).contiguous()
+        ones = torch.ones(b, device=dev, dtype=torch.float32)
+        xin, xt = ops.noisy_input(None, z, ones, ones, dup, dt)          # x_T = z, as the [uncond ; cond] NHWC batch
+        history = [torch.empty_like(z), torch.empty_like(z)]
+        x0_prev = None
+        for i in range(n):
+            eps = net.forward_nhwc(xin, tt[i], ctx)
+            scale = ops.cfg_rescale_stats(eps, z.shape[1], guidance_scale, phi) if guided and phi != 0 else None
+            noise = randn(tuple(z.shape)).to(device=dev, dtype=torch.float32).contiguous() if flags[i][3] else None
+            xin, xt, x0_prev = ops.solver_step(eps, xt, s0[i], s1[i], coef[i], guidance_scale, dt, prediction_type=pt,
+                                               x0p=x0_prev if flags[i][2] else None, noise=noise, scale=scale, last=i == n - 1,
+                                               x0_out=history[i & 1], need_prev=flags[i][2])
         if not return_images:
             return xt
         upcast = vae.dtype == torch.float16 and getattr(vae.config, 'force_upcast', False)

@@ -141,6 +141,7 @@ def training_loop(
     network_pkl=None, enable_xformers=True, gradient_checkpointing=False, resolution=512, on_iteration=None,
     rng_device=None, metric_real_stats=None, metric_num_test=None, deterministic=False, snapshot_images=False,
     teacher_steps=None, teacher_cfg=None, text_encoder=None, metric_hps_path=None, hps_prompts=None, hps_arch=None, hps_tokenizer=None,
+    teacher_sampler=None, teacher_spacing=None, teacher_eta=None, teacher_rescale=None,
 ):
     hps_kwargs = _hps_opt(metric_hps_path, hps_prompts, hps_arch, hps_tokenizer, pretrained_model_name_or_path)
     if not train_mode and network_pkl == TEACHER:
@@ -150,7 +151,9 @@ def training_loop(
                                 teacher_steps=TEACHER_STEPS if teacher_steps is None else teacher_steps,
                                 teacher_cfg=TEACHER_CFG if teacher_cfg is None else teacher_cfg, metric_real_stats=metric_real_stats,
                                 metric_num_test=metric_num_test, dataset_prompt_text_kwargs=dataset_prompt_text_kwargs,
-                                snapshot_images=snapshot_images, batch_size=batch_size, batch_gpu=batch_gpu, text_encoder=text_encoder, **hps_kwargs)
+                                snapshot_images=snapshot_images, batch_size=batch_size, batch_gpu=batch_gpu, text_encoder=text_encoder,
+                                teacher_sampler=teacher_sampler, teacher_spacing=teacher_spacing, teacher_eta=teacher_eta,
+                                teacher_rescale=teacher_rescale, **hps_kwargs)
     if not train_mode:
         return evaluate_network(run_dir=run_dir, dataset_kwargs=dataset_kwargs, network_kwargs=network_kwargs, device=device, metrics=metrics,
                                 init_timestep=init_timestep, metric_pt_path=metric_pt_path, metric_open_clip_path=metric_open_clip_path, metric_clip_path=metric_clip_path,
@@ -499,20 +502,46 @@ def evaluate_network(run_dir, dataset_kwargs, network_kwargs, device, metrics, i
     return out
 
 
+def teacher_solver_kwargs(teacher_sampler=None, teacher_spacing=None, teacher_eta=None, teacher_rescale=None):
+    """-> None when none of the four is given (the deterministic DDIM path of sd_util.teacher_sample), else the solver keywords of
+    sd_util.teacher_sample_solver (an absent sampler is 'ddim', an absent spacing the model's own)."""
+    if all(v is None for v in (teacher_sampler, teacher_spacing, teacher_eta, teacher_rescale)):
+        return None
+    return dict(solver='ddim' if teacher_sampler is None else teacher_sampler, spacing=teacher_spacing,
+                eta=0.0 if teacher_eta is None else float(teacher_eta), guidance_rescale=0.0 if teacher_rescale is None else float(teacher_rescale))
+
+
+def teacher_report_name(teacher_steps, teacher_cfg, teacher_sampler=None, teacher_spacing=None, teacher_eta=None, teacher_rescale=None):
+    """`teacher-<sampler><N>[-<spacing>][-eta<eta>][-rs<phi>]-cfg<kappa>`: the bracketed parts appear when the option was given;
+    with none given this is the `teacher-ddim<N>-cfg<kappa>` of the deterministic DDIM path."""
+    name = f'teacher-{teacher_sampler or "ddim"}{int(teacher_steps):d}'
+    if teacher_spacing is not None:
+        name += f'-{teacher_spacing}'
+    if teacher_eta is not None:
+        name += f'-eta{float(teacher_eta):g}'
+    if teacher_rescale is not None:
+        name += f'-rs{float(teacher_rescale):g}'
+    return f'{name}-cfg{float(teacher_cfg):g}'
+
+
 def evaluate_teacher(run_dir, dataset_kwargs, network_kwargs, device, metrics, init_timestep, metric_pt_path, metric_open_clip_path,
                      pretrained_model_name_or_path, resolution, teacher_steps=TEACHER_STEPS, teacher_cfg=TEACHER_CFG, metric_real_stats=None,
                      metric_num_test=None, dataset_prompt_text_kwargs=None, snapshot_images=False, batch_size=512, batch_gpu=None,
-                     metric_clip_path=None, text_encoder=None, metric_hps_path=None, hps_prompts=None, hps_arch=None, hps_tokenizer=None):
+                     metric_clip_path=None, text_encoder=None, metric_hps_path=None, hps_prompts=None, hps_arch=None, hps_tokenizer=None,
+                     teacher_sampler=None, teacher_spacing=None, teacher_eta=None, teacher_rescale=None):
     """`--train_mode 0 --network_pkl teacher`: the teacher row of the tables under this project's own protocol.  The UNet of the model
     is sampled with classifier-free guidance `teacher_cfg` and a `teacher_steps`-step deterministic DDIM sampler
     (sd_util.teacher_sample) as the `G` of every metric -- the same prompts, seeds, VAE, detector resize and metric code as a
     distilled generator gets from evaluate_network.  Evaluated ONCE (there is no 1 / 2 / 4 loop: the step count is teacher_steps);
     each result is reported through report_metric (`metric-<name>.jsonl` in run_dir) with snapshot_pkl
-    `teacher-ddim<steps>-cfg<scale>`.  snapshot_images=True also writes one preview grid `<run_dir>/<metric>_teacher.png` per metric."""
+    `teacher-ddim<steps>-cfg<scale>`.  snapshot_images=True also writes one preview grid `<run_dir>/<metric>_teacher.png` per metric.
+    Any of teacher_sampler ('ddim' | 'dpmpp2m'), teacher_spacing, teacher_eta, teacher_rescale given (not None) samples through
+    sd_util.teacher_sample_solver instead and is reported as `teacher-<sampler><steps>[-<spacing>][-eta<eta>][-rs<phi>]-cfg<scale>`
+    (teacher_report_name)."""
     from functools import partial
 
     from . import metrics as metric_main
-    from .sd_util import teacher_sample
+    from .sd_util import teacher_sample, teacher_sample_solver
     if not metrics:
         raise ValueError('--train_mode 0 evaluates metrics: pass --metrics')
     hps_kwargs = _hps_opt(metric_hps_path, hps_prompts, hps_arch, hps_tokenizer, pretrained_model_name_or_path)
@@ -522,10 +551,14 @@ def evaluate_teacher(run_dir, dataset_kwargs, network_kwargs, device, metrics, i
         weight_dtype=dtype, lora_config=None, compute_dtype=dtype, **_text_encoder_opt(text_encoder))
     unet.eval().requires_grad_(False)
     dist.print0('Loading network completed')
-    tag = f'teacher-ddim{int(teacher_steps):d}-cfg{float(teacher_cfg):g}'
-    dist.print0(f'Evaluating the teacher "{pretrained_model_name_or_path}": DDIM {int(teacher_steps)} steps, guidance scale {float(teacher_cfg):g}')
+    tag = teacher_report_name(teacher_steps, teacher_cfg, teacher_sampler, teacher_spacing, teacher_eta, teacher_rescale)
+    solver_kw = teacher_solver_kwargs(teacher_sampler, teacher_spacing, teacher_eta, teacher_rescale)
+    if solver_kw is None:
+        dist.print0(f'Evaluating the teacher "{pretrained_model_name_or_path}": DDIM {int(teacher_steps)} steps, guidance scale {float(teacher_cfg):g}')
+    else:
+        dist.print0(f'Evaluating the teacher "{pretrained_model_name_or_path}": {tag}')
     msrc = _evaluation_prompts(dataset_kwargs, dataset_prompt_text_kwargs, 'evaluate_teacher')
-    sample = partial(teacher_sample, unet=unet, noise_scheduler=noise_scheduler, text_encoder=text_encoder, tokenizer=tokenizer,
+    sample = partial(teacher_sample if solver_kw is None else partial(teacher_sample_solver, **solver_kw), unet=unet, noise_scheduler=noise_scheduler, text_encoder=text_encoder, tokenizer=tokenizer,
                      resolution=resolution, guidance_scale=float(teacher_cfg), num_inference_steps=int(teacher_steps), vae=vae)
 
     def G_eval(latents, contexts, init_timesteps=None):      # (the metrics pass init_timesteps to every G; DDIM starts at its own t_0)

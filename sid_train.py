@@ -22,6 +22,8 @@ Differences (documented, not silent):
     `--train_mode 0 --network_pkl <snapshot>` evaluates a snapshot (1 / 2 / 4 steps);
     `--train_mode 0 --network_pkl teacher` (added value) evaluates the teacher of --sd_model itself, once, under classifier-free
     guidance `--teacher_cfg` and a `--teacher_steps`-step deterministic DDIM sampler (sid_lsg_amd.sd_util.teacher_sample);
+    `--teacher_sampler`, `--teacher_spacing`, `--teacher_eta`, `--teacher_rescale` choose DPM-Solver++ 2M, stochastic DDIM, another
+    timestep spacing or guidance rescale instead (sid_lsg_amd.sd_util.teacher_sample_solver);
   * `--data` is optional (it is the COCO image set used only by the metrics and by reals.png).
 """
 import json
@@ -89,6 +91,10 @@ OPTIONS = [
     (('--teacher_steps',), dict(type=int, default=None, metavar='INT', help=f'DDIM steps of --network_pkl teacher  [default: {TEACHER_STEPS}] (not a reference option)')),
     (('--teacher_cfg',), dict(type=float, default=None, help=f'Guidance scale of --network_pkl teacher  [default: {TEACHER_CFG}] (not a reference option)')),
     (('--text_encoder',), dict(type=click.Choice(['torch', 'hip']), default=None, help='CLIP text encoder: the PyTorch module, or the same weights on the HIP kernels  [default: $SIDLSG_TEXT_ENCODER, else torch] (not a reference option)')),
+    (('--teacher_sampler',), dict(type=click.Choice(['ddim', 'dpmpp2m']), default=None, help='Solver of --network_pkl teacher: DDIM or DPM-Solver++ 2M  [default: ddim] (not a reference option)')),
+    (('--teacher_spacing',), dict(type=click.Choice(['leading', 'trailing', 'linspace']), default=None, help='Timestep spacing of --network_pkl teacher  [default: the timestep_spacing of --sd_model] (not a reference option)')),
+    (('--teacher_eta',), dict(type=click.FloatRange(min=0), default=None, help='DDIM eta of --network_pkl teacher  [default: 0] (not a reference option)')),
+    (('--teacher_rescale',), dict(type=click.FloatRange(min=0, max=1), default=None, help='Guidance rescale phi (Lin et al. 2024) of --network_pkl teacher  [default: 0] (not a reference option)')),
     (('--cfg_train_fake',), dict(type=float, default=1, show_default=True, help='kappa1: guidance scale when training the fake score')),
     (('--cfg_eval_fake',), dict(type=float, default=1, show_default=True, help='kappa2 = kappa3: guidance scale when evaluating the fake score')),
     (('--cfg_eval_real',), dict(type=float, default=1, show_default=True, help='kappa4: guidance scale when evaluating the teacher')),
@@ -111,6 +117,9 @@ def _with_options(fn):
     for flags, kw in reversed(OPTIONS):
         fn = click.option(*flags, **kw)(fn)
     return fn
+
+
+TEACHER_SOLVER_OPTIONS = ('teacher_sampler', 'teacher_spacing', 'teacher_eta', 'teacher_rescale')      # sd_util.teacher_sample_solver
 
 
 def build_config(o):
@@ -150,7 +159,7 @@ def build_config(o):
         if o.network_pkl != TEACHER and (not o.network_pkl or not os.path.isfile(o.network_pkl)):
             raise click.ClickException(f'--train_mode 0 needs --network_pkl to be a local network-snapshot-*.pkl (got {o.network_pkl!r})')
     teacher = not o.train_mode and o.network_pkl == TEACHER
-    given = [f'--{k}' for k in ('teacher_steps', 'teacher_cfg') if o.get(k) is not None]
+    given = [f'--{k}' for k in ('teacher_steps', 'teacher_cfg') + TEACHER_SOLVER_OPTIONS if o.get(k) is not None]
     if given and not teacher:
         raise click.ClickException(f'{" / ".join(given)} apply to --train_mode 0 --network_pkl {TEACHER} only')
     c.metrics, c.resolution = o.metrics, o.resolution
@@ -200,6 +209,13 @@ def build_config(o):
         c.teacher_cfg = TEACHER_CFG if o.get('teacher_cfg') is None else float(o.teacher_cfg)
         if not 1 <= c.teacher_steps <= T:
             raise click.ClickException(f'--teacher_steps {c.teacher_steps}: expected 1 .. {T} (num_train_timesteps of --sd_model)')
+        for k in TEACHER_SOLVER_OPTIONS:      # (absent when not given: the deterministic DDIM path of teacher_sample, as before)
+            if o.get(k) is not None:
+                c[k] = o[k] if isinstance(o[k], str) else float(o[k])
+        if c.get('teacher_sampler') == 'dpmpp2m' and c.get('teacher_eta'):
+            raise click.ClickException(f'--teacher_eta {c.teacher_eta:g}: --teacher_sampler dpmpp2m is deterministic (eta applies to ddim)')
+        if c.get('teacher_sampler', 'ddim') == 'ddim' and c.get('teacher_spacing') == 'linspace':
+            raise click.ClickException('--teacher_spacing linspace: not reproduced for --teacher_sampler ddim (use leading or trailing)')
     if o.transfer is not None:
         c.resume_pkl = o.transfer
     if o.resume is not None:
