@@ -168,7 +168,7 @@ int sidlsg_layernorm_bwd(const void* x, const void* dy, const float* stats, cons
  * projections), and the frozen passes issue half the launches.  M (rows) resp. B (samples) must be even; the halves need not
  * be tile aligned.  Same epilogue contract as the ungrouped entry points; res / rowvec / outputs are stacked like the input.
  * The backward-data pass of a layer is the same entry point with (dY, transposed weight set 0, transposed weight set 1).
- * bf16 only; frozen networks only (there is no grouped weight gradient). */
+ * bf16 here (the e4m3 forms: "Grouped forms of the e4m3 entry points" below); frozen networks only (there is no grouped weight gradient). */
 int sidlsg_gemm_bf16_g2(const void* A, int lda, const void* W, const void* W1, void* C, int ldc, const float* bias, const float* bias1,
                         const void* res, int ldres, const float* rowvec, int ld_rowvec, int rows_per_batch, int M, int N, int K,
                         float alpha, int flags, void* stream);
@@ -484,6 +484,28 @@ int sidlsg_groupnorm_fwd_fp8(const void* x, const float* gamma, const float* bet
 int sidlsg_gemm_mx8(const void* A8, int lda, const void* W8, const float* wscale, void* C, int ldc, const float* bias, const void* res,
                     int ldres, const float* rowvec, int ld_rowvec, int rows_per_batch, int M, int N, int K, float alpha,
                     int flags, void* stream);
+/* Grouped forms of the e4m3 entry points ("grouped launches" above: two FROZEN networks that both hold e4m3 copies of the same
+ * layers, one stacked batch).  Rows (samples) of the first half use (W8, wscale, bias) resp. (gamma, beta), those of the second
+ * half (W8_1, wscale1, bias1) resp. (gamma1, beta1); res / rowvec / outputs are stacked like the input.  M (B, rows) even, bias
+ * and bias1 both given or both NULL, every set starts on a tile boundary of its own (the halves need not be tile aligned).
+ * Otherwise the arguments and restrictions of the ungrouped entry points; the layer's backward-data pass is the bf16 grouped
+ * entry point on the transposed bf16 copies. */
+int sidlsg_gemm_fp8w_g2(const void* A, int lda, const void* W8, const float* wscale, const void* W8_1, const float* wscale1, void* C, int ldc,
+                        const float* bias, const float* bias1, const void* res, int ldres, const float* rowvec, int ld_rowvec,
+                        int rows_per_batch, int M, int N, int K, float alpha, int flags, void* stream);
+int sidlsg_conv3x3_fp8w_g2(const void* X, int ldx, const void* W8, const float* wscale, const void* W8_1, const float* wscale1, void* Y, int ldc,
+                           const float* bias, const float* bias1, const void* res, int ldres, const float* rowvec, int ld_rowvec, int B, int H,
+                           int Wd, int Cin, int Cout, int stride, int ups, float alpha, int flags, void* stream);
+int sidlsg_gemm_mx8_g2(const void* A8, int lda, const void* W8, const float* wscale, const void* W8_1, const float* wscale1, void* C, int ldc,
+                       const float* bias, const float* bias1, const void* res, int ldres, const float* rowvec, int ld_rowvec,
+                       int rows_per_batch, int M, int N, int K, float alpha, int flags, void* stream);
+int sidlsg_conv3x3_mx8_g2(const void* X8, int ldx, const void* W8, const float* wscale, const void* W8_1, const float* wscale1, void* Y, int ldc,
+                          const float* bias, const float* bias1, const void* res, int ldres, const float* rowvec, int ld_rowvec, int B, int H,
+                          int Wd, int Cin, int Cout, float alpha, int flags, void* stream);
+int sidlsg_groupnorm_fwd_fp8_g2(const void* x, const float* gamma, const float* beta, const float* gamma1, const float* beta1, void* y8,
+                                float* stats, float* ws, int B, int HW, int C, int G, float eps, int silu, void* stream);
+int sidlsg_layernorm_fwd_fp8_g2(const void* x, const float* gamma, const float* beta, const float* gamma1, const float* beta1, void* y8,
+                                float* stats, int rows, int C, float eps, void* stream);
 
 /* ---- fp32-accurate compute mode ------------------------------------------------------------------------------
  * The reference's default precision is fp32 (training/sid_training_loop.py:205 `dtype = float16 if use_fp16 else float32`,

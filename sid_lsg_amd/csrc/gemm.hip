@@ -53,6 +53,7 @@ struct GemmParams {
     // (= M; kept separately because a block narrows its M to its own set's row range, see group_select)
     const bf16* W1;
     const float* bias1;
+    const float* wscale1;        // fp8-weight path: the second set's dequantisation scales (sidlsg_*_mx8_g2 / _fp8w_g2)
     int Mg, Mtot;
     // fused GEGLU (sidlsg_gemm_geglu_bf16: the transformer's FF-in projection): geglu = F = N / 2 > 0 -> an output tile holds 80
     // features of the "a" half (rows [80 t, +80) of W) and the SAME 80 features of the gate half (rows [F + 80 t, +80)), the
@@ -74,7 +75,7 @@ template <int BM>
 __device__ __forceinline__ int group_select(GemmParams& p, int mt) {
     if (!p.Mg) return mt * BM;
     const int tg = (p.Mg + BM - 1) / BM;
-    if (mt >= tg) { p.W = p.W1; p.bias = p.bias1; return p.Mg + (mt - tg) * BM; }
+    if (mt >= tg) { p.W = p.W1; p.bias = p.bias1; p.wscale = p.wscale1; return p.Mg + (mt - tg) * BM; }
     p.M = p.Mg;
     return mt * BM;
 }
@@ -546,13 +547,13 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_fp8w_kernel(GemmParams p) {
     __shared__ __attribute__((aligned(16))) unsigned char As[2][F8_T * F8_LD];
     __shared__ __attribute__((aligned(16))) unsigned char Ws[2][F8_T * F8_LD];
     const int tiles_n = (p.N + F8_T - 1) / F8_T;
-    const int nblk = tiles_n * ((p.M + F8_T - 1) / F8_T);
+    const int nblk = tiles_n * m_tiles_rt(p, F8_T);
     int bid = blockIdx.x;
     {
         const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, idx = bid >> 3;
         bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
     }
-    const int m0 = (bid / tiles_n) * F8_T, n0 = (bid % tiles_n) * F8_T;
+    const int m0 = group_select<F8_T>(p, bid / tiles_n), n0 = (bid % tiles_n) * F8_T;      // (before the weight descriptor is built)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, lg = lane >> 4;
     const int wm0 = (wave >> 1) * 64, wn0 = (wave & 1) * 64;
@@ -1258,9 +1259,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_mx8_kernel(GemmParams p) {
     constexpr int BM = 128, BN = 160, MT = 4, NT = 5, KB = 128;      // KB: bytes (= e4m3 elements) per K-tile
     constexpr int STAGE = (BM + BN) * KB;                            // bytes
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const unsigned char* A8 = reinterpret_cast<const unsigned char*>(p.A);
-    const unsigned char* W8 = reinterpret_cast<const unsigned char*>(p.W);
-    const int tiles_n = p.N / BN, tiles_m = (p.M + BM - 1) / BM;
+    const int tiles_n = p.N / BN, tiles_m = m_tiles_rt(p, BM);
     const int ntile = tiles_n * tiles_m;
     const int nk_all = MODE == 1 ? 9 * ((p.Cin + KB - 1) / KB) : (p.K + KB - 1) / KB;
     const int nsplit = p.kt_per_split ? (nk_all + p.kt_per_split - 1) / p.kt_per_split : 1;
@@ -1281,7 +1280,10 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_mx8_kernel(GemmParams p) {
         mt = first_m + in_g % gm;
         nt = in_g / gm;
     }
-    const int m0 = mt * BM, n0 = nt * BN;
+    // grouped launch: the block's set (weights, scales, bias, row limit) is chosen here, before W8 and its descriptor are read off p
+    const int m0 = group_select<BM>(p, mt), n0 = nt * BN;
+    const unsigned char* A8 = reinterpret_cast<const unsigned char*>(p.A);
+    const unsigned char* W8 = reinterpret_cast<const unsigned char*>(p.W);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm0 = (wave >> 1) * 64, wn0 = (wave & 1) * 80;
@@ -1466,7 +1468,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_mx8_kernel(GemmParams p) {
 #pragma unroll
             for (int mi = 0; mi < MT; mi++) {
                 const int m = m0 + wm0 + mi * 16 + li;
-                if (m < p.M) *reinterpret_cast<f32x4*>(p.ws + ((size_t)split * p.M + m) * p.N + nb) = acc[ni][mi] * sc;
+                if (m < p.M) *reinterpret_cast<f32x4*>(p.ws + ((size_t)split * p.Mtot + m) * p.N + nb) = acc[ni][mi] * sc;
             }
         }
         return;
@@ -1497,7 +1499,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_mx8_kernel(GemmParams p) {
 
 template <int MODE>
 static int launch_gemm_mx8(const GemmParams& p, hipStream_t s) {
-    const int tiles = ((p.M + 127) / 128) * (p.N / 160);
+    const int tiles = m_tiles_rt(p, 128) * (p.N / 160);
     const size_t lds = (size_t)2 * (128 + 160) * 128;
     static bool attr_done = false;
     if (!attr_done) {
@@ -1506,6 +1508,7 @@ static int launch_gemm_mx8(const GemmParams& p, hipStream_t s) {
     }
     GemmParams q = p;
     q.group_m = 4;
+    q.Mtot = p.M;            // row count of a split-K slab (a block of a grouped launch narrows its own M)
     // few tiles (8x8 / 16x16 stages) and a long contraction: split K so that ~512 blocks exist (as gemm_v3_kernel does)
     const int nk = MODE == 1 ? 9 * ((p.Cin + 127) / 128) : (p.K + 127) / 128;
     int splits = 1;
@@ -3096,9 +3099,20 @@ int sidlsg_quantize_fp8_rows(const void* src_bf16, void* dst_fp8, float* scale, 
     return sidlsg_last_error();
 }
 
-int sidlsg_gemm_fp8w(const void* A, int lda, const void* W8, const float* wscale, void* C, int ldc, const float* bias, const void* res,
-                     int ldres, const float* rowvec, int ld_rowvec, int rows_per_batch, int M, int N, int K, float alpha,
-                     int flags, void* stream) {
+// The grouped forms (sidlsg_*_g2, include/sidlsg_hip.h "grouped launches"): a second set (W8_1, wscale1, bias1) for the rows / samples of the
+// second half; g2 = false: the ordinary launch (Mg = 0), exactly as before the grouped forms existed.
+static void set_group2(GemmParams& p, bool g2, const void* W8_1, const float* wscale1, const float* bias1) {
+    if (!g2) return;
+    p.W1 = (const bf16*)W8_1; p.wscale1 = wscale1; p.bias1 = bias1; p.Mg = p.M / 2;
+}
+static bool group2_args_ok(int rows, const void* W8_1, const float* wscale1, const float* bias, const float* bias1) {
+    return W8_1 && wscale1 && !(rows & 1) && (bias != nullptr) == (bias1 != nullptr);
+}
+
+static int gemm_fp8w_impl(bool g2, const void* A, int lda, const void* W8, const float* wscale, const void* W8_1, const float* wscale1, void* C,
+                          int ldc, const float* bias, const float* bias1, const void* res, int ldres, const float* rowvec, int ld_rowvec,
+                          int rows_per_batch, int M, int N, int K, float alpha, int flags, void* stream) {
+    if (g2 && !group2_args_ok(M, W8_1, wscale1, bias, bias1)) return SIDLSG_EINVAL;
     GemmParams p{};
     p.A = (const bf16*)A; p.W = (const bf16*)W8; p.wscale = wscale; p.C = C; p.bias = bias; p.res = (const bf16*)res; p.rowvec = rowvec;
     p.ldrv = ld_rowvec > 0 ? ld_rowvec : N;
@@ -3109,14 +3123,28 @@ int sidlsg_gemm_fp8w(const void* A, int lda, const void* W8, const float* wscale
     const unsigned long long ab = ((unsigned long long)(M - 1) * lda + K) * 2ull, wb = (unsigned long long)N * K;
     if (!fits31(ab) || !fits31(wb)) return SIDLSG_EINVAL;
     p.a_bytes = (unsigned)ab; p.w_bytes = (unsigned)wb;
-    const int tiles = ((M + F8_T - 1) / F8_T) * ((N + F8_T - 1) / F8_T);
+    set_group2(p, g2, W8_1, wscale1, bias1);
+    const int tiles = m_tiles_rt(p, F8_T) * ((N + F8_T - 1) / F8_T);
     SIDLSG_LAUNCH((gemm_fp8w_kernel<0>), dim3(tiles), dim3(NTHREADS), 0, (hipStream_t)stream, p);
     return sidlsg_last_error();
 }
+int sidlsg_gemm_fp8w(const void* A, int lda, const void* W8, const float* wscale, void* C, int ldc, const float* bias, const void* res,
+                     int ldres, const float* rowvec, int ld_rowvec, int rows_per_batch, int M, int N, int K, float alpha,
+                     int flags, void* stream) {
+    return gemm_fp8w_impl(false, A, lda, W8, wscale, nullptr, nullptr, C, ldc, bias, nullptr, res, ldres, rowvec, ld_rowvec, rows_per_batch, M, N, K,
+                          alpha, flags, stream);
+}
+int sidlsg_gemm_fp8w_g2(const void* A, int lda, const void* W8, const float* wscale, const void* W8_1, const float* wscale1, void* C, int ldc,
+                        const float* bias, const float* bias1, const void* res, int ldres, const float* rowvec, int ld_rowvec,
+                        int rows_per_batch, int M, int N, int K, float alpha, int flags, void* stream) {
+    return gemm_fp8w_impl(true, A, lda, W8, wscale, W8_1, wscale1, C, ldc, bias, bias1, res, ldres, rowvec, ld_rowvec, rows_per_batch, M, N, K,
+                          alpha, flags, stream);
+}
 
-int sidlsg_gemm_mx8(const void* A8, int lda, const void* W8, const float* wscale, void* C, int ldc, const float* bias, const void* res,
-                    int ldres, const float* rowvec, int ld_rowvec, int rows_per_batch, int M, int N, int K, float alpha,
-                    int flags, void* stream) {
+static int gemm_mx8_impl(bool g2, const void* A8, int lda, const void* W8, const float* wscale, const void* W8_1, const float* wscale1, void* C,
+                         int ldc, const float* bias, const float* bias1, const void* res, int ldres, const float* rowvec, int ld_rowvec,
+                         int rows_per_batch, int M, int N, int K, float alpha, int flags, void* stream) {
+    if (g2 && !group2_args_ok(M, W8_1, wscale1, bias, bias1)) return SIDLSG_EINVAL;
     GemmParams p{};
     p.A = (const bf16*)A8; p.W = (const bf16*)W8; p.wscale = wscale; p.C = C; p.bias = bias; p.res = (const bf16*)res; p.rowvec = rowvec;
     p.ldrv = ld_rowvec > 0 ? ld_rowvec : N;
@@ -3129,13 +3157,27 @@ int sidlsg_gemm_mx8(const void* A8, int lda, const void* W8, const float* wscale
     const unsigned long long ab = (unsigned long long)(M - 1) * lda + K, wb = (unsigned long long)N * K;
     if (!fits31(ab) || !fits31(wb)) return SIDLSG_EINVAL;
     p.a_bytes = (unsigned)ab; p.w_bytes = (unsigned)wb;
+    set_group2(p, g2, W8_1, wscale1, bias1);
     SidlsgTraceScope ts(SIDLSG_FAM_GEMM, 2.0 * p.M * (double)p.N * p.K);
     return launch_gemm_mx8<0>(p, (hipStream_t)stream);
 }
+int sidlsg_gemm_mx8(const void* A8, int lda, const void* W8, const float* wscale, void* C, int ldc, const float* bias, const void* res,
+                    int ldres, const float* rowvec, int ld_rowvec, int rows_per_batch, int M, int N, int K, float alpha,
+                    int flags, void* stream) {
+    return gemm_mx8_impl(false, A8, lda, W8, wscale, nullptr, nullptr, C, ldc, bias, nullptr, res, ldres, rowvec, ld_rowvec, rows_per_batch, M, N, K,
+                         alpha, flags, stream);
+}
+int sidlsg_gemm_mx8_g2(const void* A8, int lda, const void* W8, const float* wscale, const void* W8_1, const float* wscale1, void* C, int ldc,
+                       const float* bias, const float* bias1, const void* res, int ldres, const float* rowvec, int ld_rowvec,
+                       int rows_per_batch, int M, int N, int K, float alpha, int flags, void* stream) {
+    return gemm_mx8_impl(true, A8, lda, W8, wscale, W8_1, wscale1, C, ldc, bias, bias1, res, ldres, rowvec, ld_rowvec, rows_per_batch, M, N, K,
+                         alpha, flags, stream);
+}
 
-int sidlsg_conv3x3_mx8(const void* X8, int ldx, const void* W8, const float* wscale, void* Y, int ldc, const float* bias, const void* res,
-                       int ldres, const float* rowvec, int ld_rowvec, int B, int H, int Wd, int Cin, int Cout, float alpha, int flags,
-                       void* stream) {
+static int conv3x3_mx8_impl(bool g2, const void* X8, int ldx, const void* W8, const float* wscale, const void* W8_1, const float* wscale1,
+                            void* Y, int ldc, const float* bias, const float* bias1, const void* res, int ldres, const float* rowvec,
+                            int ld_rowvec, int B, int H, int Wd, int Cin, int Cout, float alpha, int flags, void* stream) {
+    if (g2 && !group2_args_ok(B, W8_1, wscale1, bias, bias1)) return SIDLSG_EINVAL;
     if (B <= 0 || H <= 0 || Wd <= 0 || Cin <= 0 || Cout <= 0 || !X8 || !W8 || !Y || !wscale) return SIDLSG_EINVAL;
     if ((Cin & 15) || (ldx & 15) || (Cout % 160) || ldx < Cin) return SIDLSG_EINVAL;
     if ((flags & F_ACCUM) && !(flags & F_OUT_F32)) return SIDLSG_EINVAL;
@@ -3149,8 +3191,21 @@ int sidlsg_conv3x3_mx8(const void* X8, int ldx, const void* W8, const float* wsc
     const unsigned long long wb = (unsigned long long)Cout * 9 * Cin;
     if (!fits31(ab) || !fits31(wb)) return SIDLSG_EINVAL;
     p.a_bytes = (unsigned)(ab - (unsigned long long)(Wd + 1) * ldx); p.w_bytes = (unsigned)wb;
+    set_group2(p, g2, W8_1, wscale1, bias1);
     SidlsgTraceScope ts(SIDLSG_FAM_CONV, 2.0 * p.M * (double)p.N * p.K);
     return launch_gemm_mx8<1>(p, (hipStream_t)stream);
+}
+int sidlsg_conv3x3_mx8(const void* X8, int ldx, const void* W8, const float* wscale, void* Y, int ldc, const float* bias, const void* res,
+                       int ldres, const float* rowvec, int ld_rowvec, int B, int H, int Wd, int Cin, int Cout, float alpha, int flags,
+                       void* stream) {
+    return conv3x3_mx8_impl(false, X8, ldx, W8, wscale, nullptr, nullptr, Y, ldc, bias, nullptr, res, ldres, rowvec, ld_rowvec, B, H, Wd, Cin, Cout,
+                            alpha, flags, stream);
+}
+int sidlsg_conv3x3_mx8_g2(const void* X8, int ldx, const void* W8, const float* wscale, const void* W8_1, const float* wscale1, void* Y, int ldc,
+                          const float* bias, const float* bias1, const void* res, int ldres, const float* rowvec, int ld_rowvec, int B, int H,
+                          int Wd, int Cin, int Cout, float alpha, int flags, void* stream) {
+    return conv3x3_mx8_impl(true, X8, ldx, W8, wscale, W8_1, wscale1, Y, ldc, bias, bias1, res, ldres, rowvec, ld_rowvec, B, H, Wd, Cin, Cout,
+                            alpha, flags, stream);
 }
 
 __global__ __launch_bounds__(256) void cast_fp8_kernel(const bf16* __restrict__ src, unsigned char* __restrict__ dst, size_t n8) {
@@ -3170,9 +3225,11 @@ int sidlsg_cast_fp8(const void* src_bf16, void* dst_fp8, long long n, void* stre
     return sidlsg_last_error();
 }
 
-int sidlsg_conv3x3_fp8w(const void* X, int ldx, const void* W8, const float* wscale, void* Y, int ldc, const float* bias,
-                        const void* res, int ldres, const float* rowvec, int ld_rowvec, int B, int H, int Wd, int Cin, int Cout,
-                        int stride, int ups, float alpha, int flags, void* stream) {
+static int conv3x3_fp8w_impl(bool g2, const void* X, int ldx, const void* W8, const float* wscale, const void* W8_1, const float* wscale1,
+                             void* Y, int ldc, const float* bias, const float* bias1, const void* res, int ldres, const float* rowvec,
+                             int ld_rowvec, int B, int H, int Wd, int Cin, int Cout, int stride, int ups, float alpha, int flags,
+                             void* stream) {
+    if (g2 && !group2_args_ok(B, W8_1, wscale1, bias, bias1)) return SIDLSG_EINVAL;
     if ((stride != 1 && stride != 2) || (Cin & 15) || !wscale) return SIDLSG_EINVAL;
     if (ups && ((H | Wd) & 1)) return SIDLSG_EINVAL;
     GemmParams p{};
@@ -3187,9 +3244,22 @@ int sidlsg_conv3x3_fp8w(const void* X, int ldx, const void* W8, const float* wsc
     const unsigned long long ab = (((unsigned long long)B * Hs * Wss - 1) * ldx + Cin) * 2ull, wb = (unsigned long long)Cout * 9 * Cin;
     if (!fits31(ab) || !fits31(wb)) return SIDLSG_EINVAL;
     p.a_bytes = (unsigned)ab; p.w_bytes = (unsigned)wb;
-    const int tiles = ((p.M + F8_T - 1) / F8_T) * ((p.N + F8_T - 1) / F8_T);
+    set_group2(p, g2, W8_1, wscale1, bias1);
+    const int tiles = m_tiles_rt(p, F8_T) * ((p.N + F8_T - 1) / F8_T);
     SIDLSG_LAUNCH((gemm_fp8w_kernel<2>), dim3(tiles), dim3(NTHREADS), 0, (hipStream_t)stream, p);
     return sidlsg_last_error();
+}
+int sidlsg_conv3x3_fp8w(const void* X, int ldx, const void* W8, const float* wscale, void* Y, int ldc, const float* bias,
+                        const void* res, int ldres, const float* rowvec, int ld_rowvec, int B, int H, int Wd, int Cin, int Cout,
+                        int stride, int ups, float alpha, int flags, void* stream) {
+    return conv3x3_fp8w_impl(false, X, ldx, W8, wscale, nullptr, nullptr, Y, ldc, bias, nullptr, res, ldres, rowvec, ld_rowvec, B, H, Wd, Cin, Cout,
+                             stride, ups, alpha, flags, stream);
+}
+int sidlsg_conv3x3_fp8w_g2(const void* X, int ldx, const void* W8, const float* wscale, const void* W8_1, const float* wscale1, void* Y, int ldc,
+                           const float* bias, const float* bias1, const void* res, int ldres, const float* rowvec, int ld_rowvec, int B, int H,
+                           int Wd, int Cin, int Cout, int stride, int ups, float alpha, int flags, void* stream) {
+    return conv3x3_fp8w_impl(true, X, ldx, W8, wscale, W8_1, wscale1, Y, ldc, bias, bias1, res, ldres, rowvec, ld_rowvec, B, H, Wd, Cin, Cout,
+                             stride, ups, alpha, flags, stream);
 }
 
 }  // extern "C"

@@ -1373,6 +1373,18 @@ int sidlsg_layernorm_bwd_g2(const void* x, const void* dy, const float* stats, c
     if (!gamma1) return SIDLSG_EINVAL;
     return layernorm_bwd_t<bf16>(x, dy, stats, gamma, dres, dx, nullptr, nullptr, nullptr, rows, C, stream, gamma1);
 }
+// Grouped variants with e4m3 outputs (the forward of ops.norm_linear_mx8 / norm_conv_mx8 in a grouped pass of two e4m3 networks): the per-half
+// parameter choice is made before anything is read, the e4m3 conversion sits in the store alone.  Same restrictions as the bf16 grouped forms.
+int sidlsg_groupnorm_fwd_fp8_g2(const void* x, const float* gamma, const float* beta, const float* gamma1, const float* beta1, void* y8,
+                                float* stats, float* ws, int B, int HW, int C, int G, float eps, int silu, void* stream) {
+    if (!gamma1) return SIDLSG_EINVAL;
+    return groupnorm_fwd_t<bf16, true>(x, gamma, beta, y8, stats, ws, B, HW, C, G, eps, silu, stream, gamma1, beta1);
+}
+int sidlsg_layernorm_fwd_fp8_g2(const void* x, const float* gamma, const float* beta, const float* gamma1, const float* beta1, void* y8,
+                                float* stats, int rows, int C, float eps, void* stream) {
+    if (!gamma1) return SIDLSG_EINVAL;
+    return layernorm_fwd_t<bf16, true>(x, gamma, beta, y8, stats, rows, C, eps, stream, gamma1, beta1);
+}
 SIDLSG_BOTH(sidlsg_layernorm_bwd, layernorm_bwd_t,
             (const void* x, const void* dy, const float* stats, const float* gamma, const void* dres, void* dx, float* dgamma, float* dbeta, float* ws, int rows, int C, void* stream),
             (x, dy, stats, gamma, dres, dx, dgamma, dbeta, ws, rows, C, stream))

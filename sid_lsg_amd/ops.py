@@ -528,6 +528,14 @@ def _pair(t):
                            'architectures, fp8 weights, or compute copies re-created after the partner map was built)') from None
 
 
+def _fp8_pair(w, what):
+    """Is this Pair two Fp8Weights (of one shape)?  A pair of one e4m3 and one bf16 copy cannot share a launch."""
+    n8 = sum(isinstance(q, Fp8Weight) for q in w)
+    if n8 == 1 or (n8 == 2 and w[0].shape != w[1].shape):
+        raise RuntimeError(f'{what}: the two weight sets must both be bf16 or both be Fp8Weights, of one shape')
+    return n8 == 2
+
+
 # raw launches
 def gemm(a, w16, out=None, bias=None, res=None, rowvec=None, rows_per_batch=1, alpha=1.0, out_f32=False, lda=None):
     """C[M,N] = alpha*A[M,K] W[N,K]^T + bias + rowvec[m//rpb] + res.  w16 / bias may be Pairs (grouped launch: rows of the
@@ -538,11 +546,18 @@ def gemm(a, w16, out=None, bias=None, res=None, rowvec=None, rows_per_batch=1, a
     lda = a.stride(0) if lda is None else lda
     f32 = a.dtype == F32
     if isinstance(w16, Pair):
-        if a.dtype != BF16 or w16[0].dtype != BF16 or w16[1].dtype != BF16 or w16[0].shape != w16[1].shape:
+        f8 = _fp8_pair(w16, 'grouped GEMM')
+        if a.dtype != BF16 or (not f8 and (w16[0].dtype != BF16 or w16[1].dtype != BF16 or w16[0].shape != w16[1].shape)):
             raise RuntimeError('grouped GEMM: bf16 activations and two bf16 weight matrices of one shape')
         ensure_workspace(a.device)
         if out is None:
             out = torch.empty((M, N), device=a.device, dtype=F32 if out_f32 else BF16)
+        if f8:
+            lib.sidlsg_gemm_fp8w_g2(_p(a), lda, _p(w16[0].q), _p(w16[0].scale), _p(w16[1].q), _p(w16[1].scale), _p(out), out.stride(0),
+                                    _p(bias[0]) if bias is not None else None, _p(bias[1]) if bias is not None else None, _p(res),
+                                    res.stride(0) if res is not None else 0, _p(rowvec), rowvec.stride(0) if rowvec is not None else 0,
+                                    rows_per_batch, M, N, K, float(alpha), 1 if out_f32 else 0, _s())
+            return out
         lib.sidlsg_gemm_bf16_g2(_p(a), lda, _p(w16[0]), _p(w16[1]), _p(out), out.stride(0), _p(bias[0]) if bias is not None else None,
                                 _p(bias[1]) if bias is not None else None, _p(res), res.stride(0) if res is not None else 0, _p(rowvec),
                                 rowvec.stride(0) if rowvec is not None else 0, rows_per_batch, M, N, K, float(alpha), 1 if out_f32 else 0, _s())
@@ -586,10 +601,17 @@ def conv3x3(x, w16, bias=None, res=None, rowvec=None, stride=1, ups=0, out_f32=F
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     f32 = x.dtype == F32
     if isinstance(w16, Pair):
-        if x.dtype != BF16 or w16[0].dtype != BF16 or w16[1].dtype != BF16 or w16[0].shape != w16[1].shape:
+        f8 = _fp8_pair(w16, 'grouped conv')
+        if x.dtype != BF16 or (not f8 and (w16[0].dtype != BF16 or w16[1].dtype != BF16 or w16[0].shape != w16[1].shape)):
             raise RuntimeError('grouped conv: bf16 activations and two bf16 weight matrices of one shape')
         ensure_workspace(x.device)
         out = torch.empty((B, Ho, Wo, Cout), device=x.device, dtype=F32 if out_f32 else BF16)
+        if f8:
+            lib.sidlsg_conv3x3_fp8w_g2(_p(x), Cin, _p(w16[0].q), _p(w16[0].scale), _p(w16[1].q), _p(w16[1].scale), _p(out), Cout,
+                                       _p(bias[0]) if bias is not None else None, _p(bias[1]) if bias is not None else None, _p(res),
+                                       Cout if res is not None else 0, _p(rowvec), rowvec.stride(0) if rowvec is not None else 0, B, H, W, Cin, Cout,
+                                       stride, ups, 1.0, 1 if out_f32 else 0, _s())
+            return out
         lib.sidlsg_conv3x3_bf16_g2(_p(x), Cin, _p(w16[0]), _p(w16[1]), _p(out), Cout, _p(bias[0]) if bias is not None else None,
                                    _p(bias[1]) if bias is not None else None, _p(res), Cout if res is not None else 0, _p(rowvec),
                                    rowvec.stride(0) if rowvec is not None else 0, B, H, W, Cin, Cout, stride, ups, 1.0, 1 if out_f32 else 0, _s())
@@ -1029,27 +1051,46 @@ def layer_norm(x, gamma, beta, eps=1e-5, fork=False):
 
 def gemm_mx8(a8, w8, out=None, bias=None, res=None, out_f32=False):
     """C[M,N] = wscale[n] * A8[M,K] W8[N,K]^T + bias + res with BOTH operands e4m3 (sidlsg_gemm_mx8: MX MFMA).
-    a8: uint8 [M,K] e4m3 bytes at unit scale; w8: Fp8Weight with N % 160 == 0."""
-    if not isinstance(w8, Fp8Weight) or a8.dtype != torch.uint8:
+    a8: uint8 [M,K] e4m3 bytes at unit scale; w8: Fp8Weight with N % 160 == 0.  Inside dual_networks (or with w8 / bias given as
+    Pairs) the grouped launch: rows of the first half of a8 with set 0, of the second half with set 1."""
+    if _dual is not None and not isinstance(w8, Pair):
+        w8, bias = _pair(w8), _pair(bias)
+    g2 = isinstance(w8, Pair)
+    if a8.dtype != torch.uint8 or not (_fp8_pair(w8, 'gemm_mx8') if g2 else isinstance(w8, Fp8Weight)):
         raise RuntimeError('gemm_mx8: e4m3 activations (uint8) and an Fp8Weight')
     M, K = a8.shape
     N = w8.shape[0]
     ensure_workspace(a8.device)
     if out is None:
         out = torch.empty((M, N), device=a8.device, dtype=F32 if out_f32 else BF16)
+    if g2:
+        lib.sidlsg_gemm_mx8_g2(_p(a8), a8.stride(0), _p(w8[0].q), _p(w8[0].scale), _p(w8[1].q), _p(w8[1].scale), _p(out), out.stride(0),
+                               _p(bias[0]) if bias is not None else None, _p(bias[1]) if bias is not None else None, _p(res),
+                               res.stride(0) if res is not None else 0, None, 0, 1, M, N, K, 1.0, 1 if out_f32 else 0, _s())
+        return out
     lib.sidlsg_gemm_mx8(_p(a8), a8.stride(0), _p(w8.q), _p(w8.scale), _p(out), out.stride(0), _p(bias), _p(res),
                         res.stride(0) if res is not None else 0, None, 0, 1, M, N, K, 1.0, 1 if out_f32 else 0, _s())
     return out
 
 
 def conv3x3_mx8(x8, w8, bias=None, res=None, rowvec=None, out_f32=False):
-    """3x3 conv, pad 1, stride 1, on an e4m3 NHWC image x8 [B,H,W,Cin] (uint8) with an Fp8Weight [Cout, 9*Cin] (Cout % 160 == 0)."""
-    if not isinstance(w8, Fp8Weight) or x8.dtype != torch.uint8:
+    """3x3 conv, pad 1, stride 1, on an e4m3 NHWC image x8 [B,H,W,Cin] (uint8) with an Fp8Weight [Cout, 9*Cin] (Cout % 160 == 0).
+    Inside dual_networks (or with w8 / bias given as Pairs) the grouped launch: samples of the first half with set 0, the others set 1."""
+    if _dual is not None and not isinstance(w8, Pair):
+        w8, bias = _pair(w8), _pair(bias)
+    g2 = isinstance(w8, Pair)
+    if x8.dtype != torch.uint8 or not (_fp8_pair(w8, 'conv3x3_mx8') if g2 else isinstance(w8, Fp8Weight)):
         raise RuntimeError('conv3x3_mx8: e4m3 activations (uint8) and an Fp8Weight')
     B, H, W, Cin = x8.shape
     Cout = w8.shape[0]
     ensure_workspace(x8.device)
     out = torch.empty((B, H, W, Cout), device=x8.device, dtype=F32 if out_f32 else BF16)
+    if g2:
+        lib.sidlsg_conv3x3_mx8_g2(_p(x8), x8.stride(2), _p(w8[0].q), _p(w8[0].scale), _p(w8[1].q), _p(w8[1].scale), _p(out), Cout,
+                                  _p(bias[0]) if bias is not None else None, _p(bias[1]) if bias is not None else None, _p(res),
+                                  res.stride(2) if res is not None else 0, _p(rowvec), rowvec.stride(0) if rowvec is not None else 0, B, H, W, Cin,
+                                  Cout, 1.0, 1 if out_f32 else 0, _s())
+        return out
     lib.sidlsg_conv3x3_mx8(_p(x8), x8.stride(2), _p(w8.q), _p(w8.scale), _p(out), Cout, _p(bias), _p(res), res.stride(2) if res is not None else 0,
                            _p(rowvec), rowvec.stride(0) if rowvec is not None else 0, B, H, W, Cin, Cout, 1.0, 1 if out_f32 else 0, _s())
     return out
@@ -1175,6 +1216,136 @@ class _NormConvMX8(torch.autograd.Function):
         return (dx,) + (None,) * 9 + (dres, None)
 
 
+def groupnorm_fp8_g2(x, gamma, beta, groups, eps, silu):
+    """Grouped GroupNorm (+ SiLU) with an e4m3 output: x [B, ..., C] bf16 (B even), gamma / beta Pairs -> (y8, stats, ws floats)."""
+    B, C = x.shape[0], x.shape[-1]
+    HW = x.numel() // (B * C)
+    n = lib.sidlsg_groupnorm_ws_floats.raw(B, HW, C, groups)
+    if n < 0 or B % 2:
+        raise RuntimeError(f'grouped groupnorm: unsupported shape B={B} HW={HW} C={C} G={groups}')
+    ws = torch.empty(n, device=x.device, dtype=F32)
+    stats = torch.empty((B, groups, 2), device=x.device, dtype=F32)
+    y8 = torch.empty(x.shape, device=x.device, dtype=torch.uint8)
+    lib.sidlsg_groupnorm_fwd_fp8_g2(_p(x), _p(gamma[0]), _p(beta[0]), _p(gamma[1]), _p(beta[1]), _p(y8), _p(stats), _p(ws), B, HW, C, groups,
+                                    float(eps), int(silu), _s())
+    return y8, stats, n
+
+
+def layernorm_fp8_g2(x, gamma, beta, eps):
+    """Grouped LayerNorm with an e4m3 output: x [..., C] bf16 (even row count), gamma / beta Pairs -> (y8, stats, grouped).  As in
+    _LayerNormG2: halves the kernel cannot align its per-wave row ranges with run as two ordinary launches on the half views."""
+    C = x.shape[-1]
+    rows = x.numel() // C
+    if rows % 2:
+        raise RuntimeError('grouped layernorm: odd row count')
+    half = rows // 2
+    y8 = torch.empty(x.shape, device=x.device, dtype=torch.uint8)
+    stats = torch.empty((rows, 2), device=x.device, dtype=F32)
+    grouped = half % 16 == 0
+    if grouped:
+        lib.sidlsg_layernorm_fwd_fp8_g2(_p(x), _p(gamma[0]), _p(beta[0]), _p(gamma[1]), _p(beta[1]), _p(y8), _p(stats), rows, C, float(eps), _s())
+    else:
+        for h in (0, 1):
+            lib.sidlsg_layernorm_fwd_fp8(x.data_ptr() + h * half * C * x.element_size(), _p(gamma[h]), _p(beta[h]), y8.data_ptr() + h * half * C,
+                                         stats.data_ptr() + h * half * 8, half, C, float(eps), _s())
+    return y8, stats, grouped
+
+
+def _bf16c(t):
+    if t is None:
+        return None
+    t = t.contiguous()
+    return t if t.dtype == BF16 else t.to(BF16)
+
+
+class _NormLinearMX8G2(torch.autograd.Function):
+    """_NormLinearMX8 for the grouped pass of two frozen e4m3 networks: gamma / beta / w8 / bias / w16t are Pairs.  Forward = grouped
+    e4m3 norm + sidlsg_gemm_mx8_g2; backward (data gradient only) = the bf16 grouped GEMM on the paired backward-data operands, then
+    the bf16 grouped norm backward."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps, groups, silu, fork, w8, bias, w16t):
+        _chk(x, BF16)
+        C = x.shape[-1]
+        if groups:
+            y8, stats, n = groupnorm_fp8_g2(x, gamma, beta, groups, eps, silu)
+            ctx.cfg = (x.shape[0], x.numel() // (x.shape[0] * C), C, groups, int(silu), n)
+        else:
+            y8, stats, ctx.grouped = layernorm_fp8_g2(x, gamma, beta, eps)
+            ctx.cfg = None
+        y = gemm_mx8(y8.view(-1, C), w8, bias=bias)
+        ctx.save_for_backward(x, stats)
+        ctx.params = (gamma, beta, w16t)
+        if fork:
+            return y, x.view(x.shape)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy, dkeep=None):
+        x, stats = ctx.saved_tensors
+        gamma, beta, w16t = ctx.params
+        none = (None,) * 9
+        if dy is None:
+            return (dkeep,) + none
+        dn = gemm(_bf16c(dy), w16t)
+        dkeep = _bf16c(dkeep)
+        dx = torch.empty_like(x)
+        C = x.shape[-1]
+        if ctx.cfg is not None:
+            B, HW, C, groups, silu, n = ctx.cfg
+            ws = torch.empty(n, device=x.device, dtype=F32)
+            lib.sidlsg_groupnorm_bwd_g2(_p(x), _p(dn), _p(stats), _p(gamma[0]), _p(beta[0]), _p(gamma[1]), _p(beta[1]), _p(dkeep), _p(dx), _p(ws),
+                                        B, HW, C, groups, silu, _s())
+        else:
+            rows = x.numel() // C
+            if ctx.grouped:
+                lib.sidlsg_layernorm_bwd_g2(_p(x), _p(dn), _p(stats), _p(gamma[0]), _p(gamma[1]), _p(dkeep), _p(dx), rows, C, _s())
+            else:
+                half = rows // 2
+                for h in (0, 1):
+                    o = h * half * C * x.element_size()
+                    lib.sidlsg_layernorm_bwd(x.data_ptr() + o, dn.data_ptr() + o, stats.data_ptr() + h * half * 8, _p(gamma[h]),
+                                             dkeep.data_ptr() + o if dkeep is not None else None, dx.data_ptr() + o, None, None, None, half, C, _s())
+        return (dx,) + none
+
+
+class _NormConvMX8G2(torch.autograd.Function):
+    """_NormConvMX8 for the grouped pass of two frozen e4m3 networks (Pairs; data gradient only, through the bf16 grouped kernels)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps, groups, fork, w8, bias, w16t, res, rowvec):
+        _chk(x, BF16)
+        B, H, W, C = x.shape
+        y8, stats, n = groupnorm_fp8_g2(x, gamma, beta, groups, eps, 1)
+        y = conv3x3_mx8(y8, w8, bias=bias, res=res, rowvec=rowvec)
+        ctx.save_for_backward(x, stats)
+        ctx.params = (gamma, beta, w16t)
+        ctx.cfg = (B, H * W, C, groups, n, res is not None, rowvec is not None)
+        ctx.rv_slot = getattr(rowvec, '_col_slot', None)
+        if fork:
+            return y, x.view(x.shape)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy, dkeep=None):
+        x, stats = ctx.saved_tensors
+        gamma, beta, w16t = ctx.params
+        B, HW, C, groups, n, has_res, has_rv = ctx.cfg
+        if dy is None:
+            return (dkeep,) + (None,) * 10
+        dy = _bf16c(dy)
+        dn = conv3x3(dy, w16t)
+        dkeep = _bf16c(dkeep)
+        dx = torch.empty_like(x)
+        ws = torch.empty(n, device=x.device, dtype=F32)
+        lib.sidlsg_groupnorm_bwd_g2(_p(x), _p(dn), _p(stats), _p(gamma[0]), _p(beta[0]), _p(gamma[1]), _p(beta[1]), _p(dkeep), _p(dx), _p(ws),
+                                    B, HW, C, groups, 1, _s())
+        dres = dy if (has_res and ctx.needs_input_grad[9]) else None
+        Cout = dy.shape[-1]
+        drv = colsum(dy.view(B * HW, Cout), HW, per_batch=True, slot=ctx.rv_slot) if (has_rv and ctx.needs_input_grad[10]) else None
+        return (dx,) + (None,) * 8 + (dres, drv)
+
+
 def _mx8_no_weight_grads(weight, gamma):
     """The e4m3 forward has no weight-gradient backward: fine under no_grad and for frozen parameters, an error otherwise."""
     if torch.is_grad_enabled() and ((weight is not None and weight.requires_grad) or (gamma is not None and gamma.requires_grad)):
@@ -1183,12 +1354,20 @@ def _mx8_no_weight_grads(weight, gamma):
 
 def norm_conv_mx8(x, gamma, beta, eps, groups, w8, bias, w16t, weight, res=None, rowvec=None, fork=False):
     """conv3x3(SiLU(GroupNorm(x))) for a frozen network, e4m3 in between."""
+    if _dual is not None:
+        wp, gp, bp, cb = _pair(weight), _pair(gamma), _pair(beta), _pair(bias)
+        _frozen(wp, gp, bp, cb)
+        return _NormConvMX8G2.apply(x, gp, bp, eps, groups, fork, _pair(w8), cb, _pair(w16t), res, rowvec)
     _mx8_no_weight_grads(weight, gamma)
     return _NormConvMX8.apply(x, gamma, beta, eps, groups, fork, w8, bias, w16t, weight, res, rowvec)
 
 
 def norm_linear_mx8(x, gamma, beta, eps, w8, bias, w16t, weight, groups=0, silu=False, fork=False):
     """Linear(GroupNorm(x)) (groups > 0) or Linear(LayerNorm(x)) (groups = 0) for a frozen network, e4m3 in between."""
+    if _dual is not None:
+        wp, gp, bp, cb = _pair(weight), _pair(gamma), _pair(beta), _pair(bias)
+        _frozen(wp, gp, bp, cb)
+        return _NormLinearMX8G2.apply(x, gp, bp, eps, groups, silu, fork, _pair(w8), cb, _pair(w16t))
     _mx8_no_weight_grads(weight, gamma)
     return _NormLinearMX8.apply(x, gamma, beta, eps, groups, silu, fork, w8, bias, w16t, weight)
 

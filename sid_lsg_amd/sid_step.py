@@ -68,6 +68,10 @@ class _SegmentedUpdate:
 
 
 class SiDStep:
+    # does SIDLSG_GROUPED_FROZEN=auto group a pair of e4m3 networks (--teacher-weights fp8-frozen)?  Decided by measurement: see the comment
+    # at grouped_mode below and profiles/fp8_grouped_ab.txt
+    GROUP_E4M3_BY_DEFAULT = False
+
     def __init__(self, G, fake_score, true_score, G_ema, scheduler, opt_fake, opt_G, *, alpha=1.0, cfg_train_fake=1.0,
                  cfg_eval_fake=1.0, cfg_eval_real=1.0, loss_scaling=1.0, loss_scaling_G=1.0, batch_gpu_total=1,
                  init_timestep=625, reducer=None, world_size=1, num_steps=1):
@@ -100,9 +104,13 @@ class SiDStep:
         # batch_gpu 4 / 8 against the two-STREAM path.  Round 5, after the attention renumbering / rotated walk and the deferred
         # reductions (profiles/r05_grouped_ab.txt, five in-session alternations at batch_gpu 8): 209.4 -> 203.5 ms (-2.8 %), and with the
         # gradient exchange forced (RCCL world 1, `bench.py --force-exchange`) 221.8 -> 210.4 -- the joint pass halves the launches of
-        # 4 F per image, and what it gives up (psi's optimizer step hidden under the teacher's forward) is 4-5 ms.  $SIDLSG_GROUPED_FROZEN:
-        # 1 / auto (default) = grouped wherever both networks allow it (_can_group: same architecture, bf16, no e4m3 copies), 0 = never
-        # (two-stream path).
+        # 4 F per image, and what it gives up (psi's optimizer step hidden under the teacher's forward) is 4-5 ms.
+        # Pairs of e4m3 networks (--teacher-weights fp8-frozen; the sidlsg_*_mx8_g2 / _fp8w_g2 / _fwd_fp8_g2 launches) can be grouped too, but
+        # are not by default: measured (profiles/fp8_grouped_ab.txt, sd21-base, batch_gpu 8, three in-session alternations) the grouped e4m3
+        # pair pass alone takes 27.67 ms against 15.63 + 15.62 ms one after the other, yet the step is 42.81 images/s grouped against 43.08 on
+        # two streams (-0.6 %, within-arm spread 0.17); like the bf16 pair in round 4, the joint pass has to wait for psi's optimizer step.
+        # $SIDLSG_GROUPED_FROZEN: auto (default) = grouped for bf16 pairs, two streams for e4m3 pairs (GROUP_E4M3_BY_DEFAULT); 1 = grouped
+        # wherever both networks allow it (_can_group: same architecture, bf16 compute, e4m3 copies in neither or in both); 0 = never.
         self.grouped_mode = os.environ.get('SIDLSG_GROUPED_FROZEN', 'auto').lower()
         self.grouped = self.grouped_mode == '1' and self._can_group()
         # opt-in: optimizer steps issued segment-wise from inside the backward, on their own stream (_SegmentedUpdate).  Same
@@ -130,13 +138,20 @@ class SiDStep:
     def _use_grouped(self, batch):
         if self.grouped_mode == '0':
             return False
+        if self._e4m3_pair() and not (self.grouped_mode == '1' or self.GROUP_E4M3_BY_DEFAULT):
+            return False
         return self._can_group()
 
+    def _e4m3_pair(self):
+        return 'fp8' in getattr(self.psi, '_flat', ()) and 'fp8' in getattr(self.phi, '_flat', ())
+
     def _can_group(self):
+        """Can psi and phi share grouped launches?  Same architecture, bf16 compute, and e4m3 copies in neither or in both (for the same
+        layers: HipUNet2DCondition.partner_map checks that and raises otherwise); a bf16 / e4m3 pair cannot."""
         from .unet import HipUNet2DCondition
         a, b = self.psi, self.phi
         return (torch.cuda.is_available() and type(a) is HipUNet2DCondition and type(b) is HipUNet2DCondition and a.cfg == b.cfg
-                and a.compute_dtype == b.compute_dtype == torch.bfloat16 and 'fp8' not in a._flat and 'fp8' not in b._flat)
+                and a.compute_dtype == b.compute_dtype == torch.bfloat16 and ('fp8' in a._flat) == ('fp8' in b._flat))
 
     def enable_segmented_optimizer(self, on=True):
         self.seg_opt = bool(on)
