@@ -537,6 +537,42 @@ def _fp8_pair(w, what):
 
 
 # raw launches
+def _weight_args(w):
+    """The weight operand of a GEMM / conv launch as the entry points take it: one pointer, (bytes, scales) of an Fp8Weight, or --
+    for a Pair of either -- set 0 followed by set 1."""
+    if isinstance(w, Pair):
+        return _weight_args(w[0]) + _weight_args(w[1])
+    if isinstance(w, Fp8Weight):
+        return w.q.data_ptr(), w.scale.data_ptr()
+    return (w.data_ptr(),)
+
+
+def _epilogue_args(g2, bias, res, rowvec, res_dim=0, ldres=None):
+    """The epilogue operands every GEMM / conv entry point takes after its output: bias (of both sets in a grouped launch), the
+    residual and its row stride (`ldres`, else the stride of its dimension `res_dim`), the row vector and its row stride."""
+    if res is None:
+        ldres = 0
+    elif ldres is None:
+        ldres = res.stride(res_dim)
+    b = (_p(bias),) if not g2 else (None, None) if bias is None else (_p(bias[0]), _p(bias[1]))
+    return b + (_p(res), ldres, _p(rowvec), rowvec.stride(0) if rowvec is not None else 0)
+
+
+def _weight_form(act_dtype, w, what):
+    """-> (a Pair?, e4m3 weights?) for the weight operand of a bf16 / fp32 contraction, after the checks gemm() and conv3x3() share."""
+    if isinstance(w, Pair):
+        f8 = _fp8_pair(w, what)
+        if act_dtype != BF16 or (not f8 and (w[0].dtype != BF16 or w[1].dtype != BF16 or w[0].shape != w[1].shape)):
+            raise RuntimeError(f'{what}: bf16 activations and two bf16 weight matrices of one shape')
+        return True, f8
+    if act_dtype == F32 and w.dtype != F32:
+        raise RuntimeError('fp32 activations need the fp32 compute copy of the weights')
+    f8 = isinstance(w, Fp8Weight)
+    if f8 and act_dtype != BF16:
+        raise RuntimeError('fp8 weights take bf16 activations')
+    return False, f8
+
+
 def gemm(a, w16, out=None, bias=None, res=None, rowvec=None, rows_per_batch=1, alpha=1.0, out_f32=False, lda=None):
     """C[M,N] = alpha*A[M,K] W[N,K]^T + bias + rowvec[m//rpb] + res.  w16 / bias may be Pairs (grouped launch: rows of the
     first half of A with set 0, of the second half with set 1)."""
@@ -545,38 +581,16 @@ def gemm(a, w16, out=None, bias=None, res=None, rowvec=None, rows_per_batch=1, a
     N = w16.shape[0]
     lda = a.stride(0) if lda is None else lda
     f32 = a.dtype == F32
-    if isinstance(w16, Pair):
-        f8 = _fp8_pair(w16, 'grouped GEMM')
-        if a.dtype != BF16 or (not f8 and (w16[0].dtype != BF16 or w16[1].dtype != BF16 or w16[0].shape != w16[1].shape)):
-            raise RuntimeError('grouped GEMM: bf16 activations and two bf16 weight matrices of one shape')
-        ensure_workspace(a.device)
-        if out is None:
-            out = torch.empty((M, N), device=a.device, dtype=F32 if out_f32 else BF16)
-        if f8:
-            lib.sidlsg_gemm_fp8w_g2(_p(a), lda, _p(w16[0].q), _p(w16[0].scale), _p(w16[1].q), _p(w16[1].scale), _p(out), out.stride(0),
-                                    _p(bias[0]) if bias is not None else None, _p(bias[1]) if bias is not None else None, _p(res),
-                                    res.stride(0) if res is not None else 0, _p(rowvec), rowvec.stride(0) if rowvec is not None else 0,
-                                    rows_per_batch, M, N, K, float(alpha), 1 if out_f32 else 0, _s())
-            return out
-        lib.sidlsg_gemm_bf16_g2(_p(a), lda, _p(w16[0]), _p(w16[1]), _p(out), out.stride(0), _p(bias[0]) if bias is not None else None,
-                                _p(bias[1]) if bias is not None else None, _p(res), res.stride(0) if res is not None else 0, _p(rowvec),
-                                rowvec.stride(0) if rowvec is not None else 0, rows_per_batch, M, N, K, float(alpha), 1 if out_f32 else 0, _s())
-        return out
-    if f32 and w16.dtype != F32:
-        raise RuntimeError('fp32 activations need the fp32 compute copy of the weights')
+    g2, f8 = _weight_form(a.dtype, w16, 'grouped GEMM')
     ensure_workspace(a.device)
     if out is None:
         out = torch.empty((M, N), device=a.device, dtype=F32 if (out_f32 or f32) else BF16)
-    if isinstance(w16, Fp8Weight):
-        if a.dtype != BF16:
-            raise RuntimeError('fp8 weights take bf16 activations')
-        lib.sidlsg_gemm_fp8w(_p(a), lda, _p(w16.q), _p(w16.scale), _p(out), out.stride(0), _p(bias), _p(res),
-                             res.stride(0) if res is not None else 0, _p(rowvec), rowvec.stride(0) if rowvec is not None else 0,
-                             rows_per_batch, M, N, K, float(alpha), 1 if out_f32 else 0, _s())
-        return out
-    _fn('gemm', a.dtype, '_bf16')(_p(a), lda, _p(w16), _p(out), out.stride(0), _p(bias), _p(res), res.stride(0) if res is not None else 0,
-                                  _p(rowvec), rowvec.stride(0) if rowvec is not None else 0, rows_per_batch, M, N, K, float(alpha),
-                                  0 if f32 else (1 if out_f32 else 0), _s())
+    if f8:
+        fn = lib.sidlsg_gemm_fp8w_g2 if g2 else lib.sidlsg_gemm_fp8w
+    else:
+        fn = lib.sidlsg_gemm_bf16_g2 if g2 else _fn('gemm', a.dtype, '_bf16')
+    fn(_p(a), lda, *_weight_args(w16), _p(out), out.stride(0), *_epilogue_args(g2, bias, res, rowvec), rows_per_batch, M, N, K,
+       float(alpha), 1 if (out_f32 and not f32) else 0, _s())
     return out
 
 
@@ -600,36 +614,15 @@ def conv3x3(x, w16, bias=None, res=None, rowvec=None, stride=1, ups=0, out_f32=F
     Cout = w16.shape[0]
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     f32 = x.dtype == F32
-    if isinstance(w16, Pair):
-        f8 = _fp8_pair(w16, 'grouped conv')
-        if x.dtype != BF16 or (not f8 and (w16[0].dtype != BF16 or w16[1].dtype != BF16 or w16[0].shape != w16[1].shape)):
-            raise RuntimeError('grouped conv: bf16 activations and two bf16 weight matrices of one shape')
-        ensure_workspace(x.device)
-        out = torch.empty((B, Ho, Wo, Cout), device=x.device, dtype=F32 if out_f32 else BF16)
-        if f8:
-            lib.sidlsg_conv3x3_fp8w_g2(_p(x), Cin, _p(w16[0].q), _p(w16[0].scale), _p(w16[1].q), _p(w16[1].scale), _p(out), Cout,
-                                       _p(bias[0]) if bias is not None else None, _p(bias[1]) if bias is not None else None, _p(res),
-                                       Cout if res is not None else 0, _p(rowvec), rowvec.stride(0) if rowvec is not None else 0, B, H, W, Cin, Cout,
-                                       stride, ups, 1.0, 1 if out_f32 else 0, _s())
-            return out
-        lib.sidlsg_conv3x3_bf16_g2(_p(x), Cin, _p(w16[0]), _p(w16[1]), _p(out), Cout, _p(bias[0]) if bias is not None else None,
-                                   _p(bias[1]) if bias is not None else None, _p(res), Cout if res is not None else 0, _p(rowvec),
-                                   rowvec.stride(0) if rowvec is not None else 0, B, H, W, Cin, Cout, stride, ups, 1.0, 1 if out_f32 else 0, _s())
-        return out
-    if f32 and w16.dtype != F32:
-        raise RuntimeError('fp32 activations need the fp32 compute copy of the weights')
+    g2, f8 = _weight_form(x.dtype, w16, 'grouped conv')
     ensure_workspace(x.device)
     out = torch.empty((B, Ho, Wo, Cout), device=x.device, dtype=F32 if (out_f32 or f32) else BF16)
-    if isinstance(w16, Fp8Weight):
-        if x.dtype != BF16:
-            raise RuntimeError('fp8 weights take bf16 activations')
-        lib.sidlsg_conv3x3_fp8w(_p(x), Cin, _p(w16.q), _p(w16.scale), _p(out), Cout, _p(bias), _p(res), Cout if res is not None else 0,
-                                _p(rowvec), rowvec.stride(0) if rowvec is not None else 0, B, H, W, Cin, Cout, stride, ups, 1.0,
-                                1 if out_f32 else 0, _s())
-        return out
-    _fn('conv3x3', x.dtype, '_bf16')(_p(x), Cin, _p(w16), _p(out), Cout, _p(bias), _p(res), Cout if res is not None else 0, _p(rowvec),
-                                     rowvec.stride(0) if rowvec is not None else 0, B, H, W, Cin, Cout, stride, ups, 1.0,
-                                     0 if f32 else (1 if out_f32 else 0), _s())
+    if f8:
+        fn = lib.sidlsg_conv3x3_fp8w_g2 if g2 else lib.sidlsg_conv3x3_fp8w
+    else:
+        fn = lib.sidlsg_conv3x3_bf16_g2 if g2 else _fn('conv3x3', x.dtype, '_bf16')
+    fn(_p(x), Cin, *_weight_args(w16), _p(out), Cout, *_epilogue_args(g2, bias, res, rowvec, ldres=Cout), B, H, W, Cin, Cout, stride, ups,
+       1.0, 1 if (out_f32 and not f32) else 0, _s())
     return out
 
 
@@ -652,15 +645,48 @@ def colsum(g2d, rows_per_batch, per_batch=False, total=None, slot=None):
     return pb
 
 
+def _gradc(t, dtype=BF16):
+    """An incoming gradient as the kernels take it: contiguous and of the activation dtype (None stays None)."""
+    if t is None:
+        return None
+    t = t.contiguous()
+    return t if t.dtype == dtype else t.to(dtype)
+
+
+def _conv_dgrad(dy, w16t, x_shape, stride, ups, dtype):
+    """Data gradient of conv3x3 (w16t: [Cin, 9*Cout], taps flipped; a Pair in the grouped pass): a stride-2 conv zero-inserts dy
+    first, a fused x2 upsample sum-pools the full-resolution gradient down to the input's size."""
+    B, Ho, Wo, Cout = dy.shape
+    g = dy
+    if stride == 2:
+        g = torch.empty((B, x_shape[1], x_shape[2], Cout), device=dy.device, dtype=dtype)
+        _fn('zero_insert2', dtype)(_p(dy), _p(g), B, Ho, Wo, x_shape[1], x_shape[2], Cout, _s())
+    dx = conv3x3(g, w16t)
+    if ups:
+        full = dx
+        dx = torch.empty(x_shape, device=dy.device, dtype=dtype)
+        _fn('sumpool2x2', dtype)(_p(full), _p(dx), B, x_shape[1], x_shape[2], x_shape[3], _s())
+    return dx
+
+
 # ------------------------------------------------------------------------------------------------
+# One autograd node per weight-bearing op.  A node is in its GROUPED form when its parameters arrive as Pairs (the pass of two
+# FROZEN networks over a stacked batch, dual_networks): the backward is then the data gradient only and nothing of the forward
+# input is kept alive for a weight gradient -- the Pairs live on ctx (they are not tensors).
 class _Linear(torch.autograd.Function):
-    """y = x W^T + b (+ res) (+ rowvec broadcast over rows_per_batch rows).  x: [M,K] bf16."""
+    """y = x W^T + b (+ res) (+ rowvec broadcast over rows_per_batch rows).  x: [M,K] bf16.  Grouped: bias / w16 / w16t are Pairs and
+    weight is None."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, w16, w16t, res, rowvec, rows_per_batch, out_f32):
-        _chk(x, ACT)
+        ctx.g2 = isinstance(w16, Pair)
+        _chk(x, BF16 if ctx.g2 else ACT)
         y = gemm(x, w16, bias=bias, res=res, rowvec=rowvec, rows_per_batch=rows_per_batch, out_f32=out_f32)
-        ctx.save_for_backward(x, weight, bias, w16t)
+        if ctx.g2:
+            ctx.w16t = w16t
+        else:
+            ctx.save_for_backward(x, weight, bias, w16t)
+        ctx.dtype = x.dtype
         ctx.rpb = rows_per_batch
         ctx.has_res = res is not None
         ctx.has_rv = rowvec is not None
@@ -668,13 +694,16 @@ class _Linear(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
+        dy = _gradc(dy, ctx.dtype)
+        need_rv = ctx.has_rv and ctx.needs_input_grad[6]
+        dres = dy if (ctx.has_res and ctx.needs_input_grad[5]) else None
+        if ctx.g2:
+            dx = gemm(dy, ctx.w16t) if ctx.needs_input_grad[0] else None
+            drv = colsum(dy, ctx.rpb, per_batch=True) if need_rv else None
+            return dx, None, None, None, None, dres, drv, None, None
         x, weight, bias, w16t = ctx.saved_tensors
-        dy = dy.contiguous()
-        if dy.dtype != x.dtype:
-            dy = dy.to(x.dtype)
         dx = gemm(dy, w16t) if ctx.needs_input_grad[0] else None
         need_b = _wants_grad(bias)
-        need_rv = ctx.has_rv and ctx.needs_input_grad[6]
         # bias gradient comes out of the bf16 wgrad kernel (the fp32 family computes it with a column sum)
         fused_b = need_b and not need_rv and _wants_grad(weight) and x.dtype == BF16
         if _wants_grad(weight):
@@ -689,31 +718,7 @@ class _Linear(torch.autograd.Function):
             drv = colsum(dy, ctx.rpb, per_batch=True, total=bias.grad if need_b else None)
         elif need_b and not fused_b:
             colsum(dy, dy.shape[0], total=bias.grad)
-        dres = dy if (ctx.has_res and ctx.needs_input_grad[5]) else None
         return dx, None, None, None, None, dres, drv, None, None
-
-
-class _LinearG2(torch.autograd.Function):
-    """_Linear for the grouped pass of two FROZEN networks: parameters arrive as Pairs, the backward is the data gradient only
-    (nothing of the forward input is kept alive for a weight gradient)."""
-
-    @staticmethod
-    def forward(ctx, x, bias, w16, w16t, res, rowvec, rows_per_batch, out_f32):
-        _chk(x, BF16)
-        y = gemm(x, w16, bias=bias, res=res, rowvec=rowvec, rows_per_batch=rows_per_batch, out_f32=out_f32)
-        ctx.w16t, ctx.rpb = w16t, rows_per_batch
-        ctx.has_res, ctx.has_rv = res is not None, rowvec is not None
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        dy = dy.contiguous()
-        if dy.dtype != BF16:
-            dy = dy.to(BF16)
-        dx = gemm(dy, ctx.w16t) if ctx.needs_input_grad[0] else None
-        drv = colsum(dy, ctx.rpb, per_batch=True) if (ctx.has_rv and ctx.needs_input_grad[5]) else None
-        dres = dy if (ctx.has_res and ctx.needs_input_grad[4]) else None
-        return dx, None, None, None, dres, drv, None, None
 
 
 def _frozen(*params):
@@ -727,53 +732,52 @@ def linear(x, weight, bias, w16, w16t, res=None, rowvec=None, rows_per_batch=1, 
     if _dual is not None:
         wp, bp = _pair(weight), _pair(bias)
         _frozen(wp, bp)
-        return _LinearG2.apply(x, Pair(bp[0], bp[1]) if bp is not None else None, _pair(w16), _pair(w16t), res, rowvec, rows_per_batch, out_f32)
+        return _Linear.apply(x, None, bp, _pair(w16), _pair(w16t), res, rowvec, rows_per_batch, out_f32)
     if isinstance(w16, Fp8Weight):
         _mx8_no_weight_grads(weight, None)
     return _Linear.apply(x, weight, bias, w16, w16t, res, rowvec, rows_per_batch, out_f32)
 
 
 class _Conv3x3(torch.autograd.Function):
-    """NHWC 3x3 conv, pad 1, stride 1|2, optional fused nearest-x2 upsample of the input."""
+    """NHWC 3x3 conv, pad 1, stride 1|2, optional fused nearest-x2 upsample of the input.  Grouped: bias / w16 / w16t are Pairs and
+    weight is None."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, w16, w16t, res, rowvec, stride, ups, out_f32, bias_p):
-        _chk(x, ACT)
+        ctx.g2 = isinstance(w16, Pair)
+        _chk(x, BF16 if ctx.g2 else ACT)
         y = conv3x3(x, w16, bias=bias_p if bias_p is not None else bias, res=res, rowvec=rowvec, stride=stride, ups=ups,
                     out_f32=out_f32)
-        ctx.save_for_backward(x, weight, bias, w16t)
-        ctx.cfg = (stride, ups, res is not None, rowvec is not None)
+        if ctx.g2:
+            ctx.w16t = w16t
+        else:
+            ctx.save_for_backward(x, weight, bias, w16t)
+        ctx.cfg = (stride, ups, res is not None, rowvec is not None, x.shape, x.dtype)
         ctx.rv_slot = getattr(rowvec, '_col_slot', None)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, weight, bias, w16t = ctx.saved_tensors
-        stride, ups, has_res, has_rv = ctx.cfg
-        dy = dy.contiguous()
-        if dy.dtype != x.dtype:
-            dy = dy.to(x.dtype)
+        stride, ups, has_res, has_rv, xs, dtype = ctx.cfg
+        dy = _gradc(dy, dtype)
         B, Ho, Wo, Cout = dy.shape
-        Cin = x.shape[3]
-        dx = None
-        if ctx.needs_input_grad[0]:
-            g = dy
-            if stride == 2:
-                g = torch.empty((B, x.shape[1], x.shape[2], Cout), device=dy.device, dtype=x.dtype)
-                _fn('zero_insert2', x.dtype)(_p(dy), _p(g), B, Ho, Wo, x.shape[1], x.shape[2], Cout, _s())
-            dx = conv3x3(g, w16t)           # w16t: [Cin, 9*Cout], taps flipped
-            if ups:
-                full = dx
-                dx = torch.empty_like(x)
-                _fn('sumpool2x2', x.dtype)(_p(full), _p(dx), B, x.shape[1], x.shape[2], Cin, _s())
+        dy2 = dy.view(B * Ho * Wo, Cout)
+        need_rv = has_rv and ctx.needs_input_grad[6]
+        dres = dy if (has_res and ctx.needs_input_grad[5]) else None
+        if ctx.g2:
+            dx = _conv_dgrad(dy, ctx.w16t, xs, stride, ups, dtype) if ctx.needs_input_grad[0] else None
+            drv = colsum(dy2, Ho * Wo, per_batch=True, slot=ctx.rv_slot) if need_rv else None
+            return dx, None, None, None, None, dres, drv, None, None, None, None
+        x, weight, bias, w16t = ctx.saved_tensors
+        Cin = xs[3]
+        dx = _conv_dgrad(dy, w16t, xs, stride, ups, dtype) if ctx.needs_input_grad[0] else None
         co_w, ci_w = weight.shape[0], weight.shape[1]     # logical (unpadded) sizes of the master
         padded = (co_w != Cout) or (ci_w != Cin)           # conv_in (Cin 4->8) / conv_out (Cout 4->8)
         need_b = _wants_grad(bias)
-        need_rv = has_rv and ctx.needs_input_grad[6]
         # bias gradient from the (bf16) wgrad kernel
         fused_b = need_b and not need_rv and not padded and _wants_grad(weight) and x.dtype == BF16
         if _wants_grad(weight):
-            H, W = (2 * x.shape[1], 2 * x.shape[2]) if ups else (x.shape[1], x.shape[2])
+            H, W = (2 * xs[1], 2 * xs[2]) if ups else (xs[1], xs[2])
             wgrad = _fn('conv3x3_wgrad', x.dtype, '_bf16')
             if not padded and _take_assign(weight, x.dtype):
                 wgrad = lib.sidlsg_conv3x3_wgrad_assign_bf16
@@ -785,7 +789,6 @@ class _Conv3x3(torch.autograd.Function):
                 tmp = torch.zeros((Cout, 9, Cin), device=dy.device, dtype=F32)
                 wgrad(_p(dy), Cout, _p(x), Cin, _p(tmp), None, B, H, W, Cin, Cout, stride, ups, _s())
                 weight.grad.permute(0, 2, 3, 1).reshape(co_w, 9, ci_w).add_(tmp[:co_w, :, :ci_w])
-        dy2 = dy.view(B * Ho * Wo, Cout)
         drv = None
         btot = None
         if need_b and not fused_b:
@@ -796,43 +799,7 @@ class _Conv3x3(torch.autograd.Function):
             colsum(dy2, dy2.shape[0], total=btot)
         if need_b and not fused_b and co_w != Cout:
             bias.grad.add_(btot[:co_w])
-        dres = dy if (has_res and ctx.needs_input_grad[5]) else None
         return dx, None, None, None, None, dres, drv, None, None, None, None
-
-
-class _Conv3x3G2(torch.autograd.Function):
-    """_Conv3x3 for the grouped pass of two frozen networks (Pairs; data gradient only)."""
-
-    @staticmethod
-    def forward(ctx, x, bias, w16, w16t, res, rowvec, stride, ups, out_f32):
-        _chk(x, BF16)
-        y = conv3x3(x, w16, bias=bias, res=res, rowvec=rowvec, stride=stride, ups=ups, out_f32=out_f32)
-        ctx.w16t = w16t
-        ctx.cfg = (stride, ups, res is not None, rowvec is not None, x.shape)
-        ctx.rv_slot = getattr(rowvec, '_col_slot', None)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        stride, ups, has_res, has_rv, xs = ctx.cfg
-        dy = dy.contiguous()
-        if dy.dtype != BF16:
-            dy = dy.to(BF16)
-        B, Ho, Wo, Cout = dy.shape
-        dx = None
-        if ctx.needs_input_grad[0]:
-            g = dy
-            if stride == 2:
-                g = torch.empty((B, xs[1], xs[2], Cout), device=dy.device, dtype=BF16)
-                lib.sidlsg_zero_insert2(_p(dy), _p(g), B, Ho, Wo, xs[1], xs[2], Cout, _s())
-            dx = conv3x3(g, ctx.w16t)
-            if ups:
-                full = dx
-                dx = torch.empty(xs, device=dy.device, dtype=BF16)
-                lib.sidlsg_sumpool2x2(_p(full), _p(dx), B, xs[1], xs[2], xs[3], _s())
-        drv = colsum(dy.view(B * Ho * Wo, Cout), Ho * Wo, per_batch=True, slot=ctx.rv_slot) if (has_rv and ctx.needs_input_grad[5]) else None
-        dres = dy if (has_res and ctx.needs_input_grad[4]) else None
-        return dx, None, None, None, dres, drv, None, None, None
 
 
 def conv3x3_op(x, weight, bias, w16, w16t, res=None, rowvec=None, stride=1, ups=0, out_f32=False, bias_p=None):
@@ -840,10 +807,133 @@ def conv3x3_op(x, weight, bias, w16, w16t, res=None, rowvec=None, stride=1, ups=
         wp, bp = _pair(weight), _pair(bias)
         _frozen(wp, bp)
         bq = _pair(bias_p) if bias_p is not None else bp        # (conv_out: the zero-padded bias of the padded output channels)
-        return _Conv3x3G2.apply(x, Pair(bq[0], bq[1]) if bq is not None else None, _pair(w16), _pair(w16t), res, rowvec, stride, ups, out_f32)
+        return _Conv3x3.apply(x, None, bq, _pair(w16), _pair(w16t), res, rowvec, stride, ups, out_f32, None)
     if isinstance(w16, Fp8Weight):
         _mx8_no_weight_grads(weight, None)
     return _Conv3x3.apply(x, weight, bias, w16, w16t, res, rowvec, stride, ups, out_f32, bias_p)
+
+
+# ---- norm launches: parameters are tensors, or Pairs (samples / token rows of the first half of the batch with set 0, the others set 1) ----
+def _groupnorm_fwd(x, gamma, beta, groups, eps, silu, out_e4m3=False):
+    """GroupNorm (+ SiLU) of x [B, ..., C] -> (y, stats, ws floats); out_e4m3: y as e4m3 bytes (uint8; bf16 x only)."""
+    g2 = isinstance(gamma, Pair)
+    B, C = x.shape[0], x.shape[-1]
+    HW = x.numel() // (B * C)
+    n = lib.sidlsg_groupnorm_ws_floats.raw(B, HW, C, groups)
+    if n < 0 or (g2 and B % 2):
+        raise RuntimeError(f'{"grouped " if g2 else ""}groupnorm: unsupported shape B={B} HW={HW} C={C} G={groups}')
+    ws = torch.empty(n, device=x.device, dtype=F32)
+    stats = torch.empty((B, groups, 2), device=x.device, dtype=F32)
+    y = torch.empty(x.shape, device=x.device, dtype=torch.uint8) if out_e4m3 else torch.empty_like(x)
+    if g2:
+        fn = lib.sidlsg_groupnorm_fwd_fp8_g2 if out_e4m3 else lib.sidlsg_groupnorm_fwd_g2
+        params = (_p(gamma[0]), _p(beta[0]), _p(gamma[1]), _p(beta[1]))
+    else:
+        fn = lib.sidlsg_groupnorm_fwd_fp8 if out_e4m3 else _fn('groupnorm_fwd', x.dtype)
+        params = (_p(gamma), _p(beta))
+    fn(_p(x), *params, _p(y), _p(stats), _p(ws), B, HW, C, groups, float(eps), int(silu), _s())
+    return y, stats, n
+
+
+def _groupnorm_bwd(x, dy, stats, gamma, beta, dkeep, cfg, param_grads=False):
+    """-> dx (+ dkeep, summed inside the kernel).  cfg: (groups, silu, ws floats) of the forward.  param_grads: also reduce dgamma /
+    dbeta into the parameters' .grad where they want one (the single trainable form; a Pair is frozen)."""
+    groups, silu, n = cfg
+    B, C = x.shape[0], x.shape[-1]
+    HW = x.numel() // (B * C)
+    ws = torch.empty(n, device=x.device, dtype=F32)
+    dx = torch.empty_like(x)
+    if isinstance(gamma, Pair):
+        lib.sidlsg_groupnorm_bwd_g2(_p(x), _p(dy), _p(stats), _p(gamma[0]), _p(beta[0]), _p(gamma[1]), _p(beta[1]), _p(dkeep), _p(dx), _p(ws),
+                                    B, HW, C, groups, silu, _s())
+        return dx
+    pg = param_grads and _wants_grad(gamma) and _wants_grad(beta)
+    h = _defer_begin(x.device) if pg else None
+    _fn('groupnorm_bwd', x.dtype)(_p(x), _p(dy), _p(stats), _p(gamma), _p(beta), _p(dkeep), _p(dx), _p(gamma.grad) if pg else None,
+                                  _p(beta.grad) if pg else None, _p(ws), B, HW, C, groups, silu, _s())
+    _defer_end(h, ws)
+    return dx
+
+
+def _row(t, r):
+    """Address of row r of a contiguous [..., C] tensor seen as [rows, C] (None stays None)."""
+    return None if t is None else t.view(-1, t.shape[-1])[r:].data_ptr()
+
+
+def _layernorm_fwd(x, gamma, beta, eps, out_e4m3=False):
+    """LayerNorm of x [..., C] -> (y, stats, grouped); out_e4m3: y as e4m3 bytes (uint8; bf16 x only).  grouped: the two-set kernel
+    ran.  Halves whose row count it cannot align its per-wave row ranges with (tiny test networks) run as two ordinary launches on
+    the half views."""
+    C = x.shape[-1]
+    rows = x.numel() // C
+    g2 = isinstance(gamma, Pair)
+    if g2 and rows % 2:
+        raise RuntimeError('grouped layernorm: odd row count')
+    y = torch.empty(x.shape, device=x.device, dtype=torch.uint8) if out_e4m3 else torch.empty_like(x)
+    stats = torch.empty((rows, 2), device=x.device, dtype=F32)
+    half = rows // 2
+    if g2 and half % 16 == 0:
+        (lib.sidlsg_layernorm_fwd_fp8_g2 if out_e4m3 else lib.sidlsg_layernorm_fwd_g2)(
+            _p(x), _p(gamma[0]), _p(beta[0]), _p(gamma[1]), _p(beta[1]), _p(y), _p(stats), rows, C, float(eps), _s())
+        return y, stats, True
+    single = lib.sidlsg_layernorm_fwd_fp8 if out_e4m3 else _fn('layernorm_fwd', x.dtype)
+    if not g2:
+        single(_p(x), _p(gamma), _p(beta), _p(y), _p(stats), rows, C, float(eps), _s())
+    else:
+        for h in (0, 1):
+            single(_row(x, h * half), _p(gamma[h]), _p(beta[h]), _row(y, h * half), _row(stats, h * half), half, C, float(eps), _s())
+    return y, stats, False
+
+
+def _layernorm_bwd(x, dy, stats, gamma, beta, dkeep, grouped, param_grads=False):
+    """-> dx (+ dkeep).  grouped: what _layernorm_fwd returned; param_grads: as in _groupnorm_bwd."""
+    C = x.shape[-1]
+    rows = x.numel() // C
+    dx = torch.empty_like(x)
+    if grouped:
+        lib.sidlsg_layernorm_bwd_g2(_p(x), _p(dy), _p(stats), _p(gamma[0]), _p(gamma[1]), _p(dkeep), _p(dx), rows, C, _s())
+        return dx
+    single = _fn('layernorm_bwd', x.dtype)
+    if not isinstance(gamma, Pair):
+        pg = param_grads and _wants_grad(gamma) and _wants_grad(beta)
+        ws = torch.empty(lib.sidlsg_layernorm_bwd_nblocks.raw(rows) * C * 2, device=x.device, dtype=F32) if pg else None
+        h = _defer_begin(x.device) if pg else None
+        single(_p(x), _p(dy), _p(stats), _p(gamma), _p(dkeep), _p(dx), _p(gamma.grad) if pg else None, _p(beta.grad) if pg else None,
+               _p(ws), rows, C, _s())
+        _defer_end(h, ws)
+    else:
+        half = rows // 2
+        for h in (0, 1):
+            r = h * half
+            single(_row(x, r), _row(dy, r), _row(stats, r), _p(gamma[h]), _row(dkeep, r), _row(dx, r), None, None, None, half, C, _s())
+    return dx
+
+
+def groupnorm_fp8_g2(x, gamma, beta, groups, eps, silu):
+    """Grouped GroupNorm (+ SiLU) with an e4m3 output: x [B, ..., C] bf16 (B even), gamma / beta (set 0, set 1) -> (y8, stats, ws floats)."""
+    return _groupnorm_fwd(x, Pair(*gamma), Pair(*beta), groups, eps, silu, out_e4m3=True)
+
+
+def layernorm_fp8_g2(x, gamma, beta, eps):
+    """Grouped LayerNorm with an e4m3 output: x [..., C] bf16 (even row count), gamma / beta (set 0, set 1) -> (y8, stats, grouped)."""
+    return _layernorm_fwd(x, Pair(*gamma), Pair(*beta), eps, out_e4m3=True)
+
+
+def _keep(ctx, x, stats, *params):
+    """What a norm node keeps for its backward: x and stats as saved tensors, and its parameters -- saved tensors too in the single
+    form, Pairs on ctx in the grouped one."""
+    if isinstance(params[0], Pair):
+        ctx.save_for_backward(x, stats)
+        ctx.params = params
+    else:
+        ctx.save_for_backward(x, stats, *params)
+        ctx.params = None
+
+
+def _kept(ctx):
+    """-> x, stats, parameters as _keep() got them."""
+    x, stats, *params = ctx.saved_tensors
+    return x, stats, ctx.params or params
 
 
 class _GroupNorm(torch.autograd.Function):
@@ -853,94 +943,27 @@ class _GroupNorm(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, groups, eps, silu, fork):
-        _chk(x, ACT)
-        B, C = x.shape[0], x.shape[-1]
-        HW = x.numel() // (B * C)
-        n = lib.sidlsg_groupnorm_ws_floats.raw(B, HW, C, groups)
-        if n < 0:
-            raise RuntimeError(f'groupnorm: unsupported shape B={B} HW={HW} C={C} G={groups}')
-        ws = torch.empty(n, device=x.device, dtype=F32)
-        stats = torch.empty((B, groups, 2), device=x.device, dtype=F32)
-        y = torch.empty_like(x)
-        _fn('groupnorm_fwd', x.dtype)(_p(x), _p(gamma), _p(beta), _p(y), _p(stats), _p(ws), B, HW, C, groups, float(eps), int(silu), _s())
-        ctx.save_for_backward(x, gamma, beta, stats)
-        ctx.cfg = (B, HW, C, groups, int(silu), n)
+        _chk(x, BF16 if isinstance(gamma, Pair) else ACT)
+        y, stats, n = _groupnorm_fwd(x, gamma, beta, groups, eps, silu)
+        _keep(ctx, x, stats, gamma, beta)
+        ctx.cfg = (groups, int(silu), n)
         if fork:
             return y, x.view(x.shape)
         return y
 
     @staticmethod
     def backward(ctx, dy, dkeep=None):
-        x, gamma, beta, stats = ctx.saved_tensors
-        B, HW, C, groups, silu, n = ctx.cfg
         if dy is None:                       # only the pass-through output was used
             return dkeep, None, None, None, None, None, None
-        dy = dy.contiguous()
-        if dy.dtype != x.dtype:
-            dy = dy.to(x.dtype)
-        if dkeep is not None:
-            dkeep = dkeep.contiguous()
-            if dkeep.dtype != x.dtype:
-                dkeep = dkeep.to(x.dtype)
-        ws = torch.empty(n, device=x.device, dtype=F32)
-        dx = torch.empty_like(x)
-        pg = _wants_grad(gamma) and _wants_grad(beta)
-        h = _defer_begin(x.device) if pg else None
-        _fn('groupnorm_bwd', x.dtype)(_p(x), _p(dy), _p(stats), _p(gamma), _p(beta), _p(dkeep) if dkeep is not None else None, _p(dx),
-                                      _p(gamma.grad) if pg else None, _p(beta.grad) if pg else None, _p(ws), B, HW, C, groups, silu, _s())
-        _defer_end(h, ws)
-        return dx, None, None, None, None, None, None
-
-
-class _GroupNormG2(torch.autograd.Function):
-    """_GroupNorm for the grouped pass: samples of the first half of the batch use (gamma, beta) of set 0, the others set 1."""
-
-    @staticmethod
-    def forward(ctx, x, gamma, beta, groups, eps, silu, fork):
-        _chk(x, BF16)
-        B, C = x.shape[0], x.shape[-1]
-        HW = x.numel() // (B * C)
-        n = lib.sidlsg_groupnorm_ws_floats.raw(B, HW, C, groups)
-        if n < 0 or B % 2:
-            raise RuntimeError(f'grouped groupnorm: unsupported shape B={B} HW={HW} C={C} G={groups}')
-        ws = torch.empty(n, device=x.device, dtype=F32)
-        stats = torch.empty((B, groups, 2), device=x.device, dtype=F32)
-        y = torch.empty_like(x)
-        lib.sidlsg_groupnorm_fwd_g2(_p(x), _p(gamma[0]), _p(beta[0]), _p(gamma[1]), _p(beta[1]), _p(y), _p(stats), _p(ws), B, HW, C, groups,
-                                    float(eps), int(silu), _s())
-        ctx.save_for_backward(x, stats)
-        ctx.params = (gamma, beta)
-        ctx.cfg = (B, HW, C, groups, int(silu), n)
-        if fork:
-            return y, x.view(x.shape)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy, dkeep=None):
-        x, stats = ctx.saved_tensors
-        gamma, beta = ctx.params
-        B, HW, C, groups, silu, n = ctx.cfg
-        if dy is None:
-            return dkeep, None, None, None, None, None, None
-        dy = dy.contiguous()
-        if dy.dtype != BF16:
-            dy = dy.to(BF16)
-        if dkeep is not None:
-            dkeep = dkeep.contiguous()
-            if dkeep.dtype != BF16:
-                dkeep = dkeep.to(BF16)
-        ws = torch.empty(n, device=x.device, dtype=F32)
-        dx = torch.empty_like(x)
-        lib.sidlsg_groupnorm_bwd_g2(_p(x), _p(dy), _p(stats), _p(gamma[0]), _p(beta[0]), _p(gamma[1]), _p(beta[1]),
-                                    _p(dkeep) if dkeep is not None else None, _p(dx), _p(ws), B, HW, C, groups, silu, _s())
+        x, stats, (gamma, beta) = _kept(ctx)
+        dx = _groupnorm_bwd(x, _gradc(dy, x.dtype), stats, gamma, beta, _gradc(dkeep, x.dtype), ctx.cfg, param_grads=True)
         return dx, None, None, None, None, None, None
 
 
 def group_norm(x, gamma, beta, groups, eps, silu, fork=False):
     if _dual is not None:
-        gp, bp = _pair(gamma), _pair(beta)
-        _frozen(gp, bp)
-        return _GroupNormG2.apply(x, gp, bp, groups, eps, silu, fork)
+        gamma, beta = _pair(gamma), _pair(beta)
+        _frozen(gamma, beta)
     return _GroupNorm.apply(x, gamma, beta, groups, eps, silu, fork)
 
 
@@ -949,103 +972,26 @@ class _LayerNorm(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, eps, fork):
-        _chk(x, ACT)
-        C = x.shape[-1]
-        rows = x.numel() // C
-        y = torch.empty_like(x)
-        stats = torch.empty((rows, 2), device=x.device, dtype=F32)
-        _fn('layernorm_fwd', x.dtype)(_p(x), _p(gamma), _p(beta), _p(y), _p(stats), rows, C, float(eps), _s())
-        ctx.save_for_backward(x, gamma, beta, stats)
+        _chk(x, BF16 if isinstance(gamma, Pair) else ACT)
+        y, stats, ctx.grouped = _layernorm_fwd(x, gamma, beta, eps)
+        _keep(ctx, x, stats, gamma, beta)
         if fork:
             return y, x.view(x.shape)
         return y
 
     @staticmethod
     def backward(ctx, dy, dkeep=None):
-        x, gamma, beta, stats = ctx.saved_tensors
         if dy is None:
             return dkeep, None, None, None, None
-        C = x.shape[-1]
-        rows = x.numel() // C
-        dy = dy.contiguous()
-        if dy.dtype != x.dtype:
-            dy = dy.to(x.dtype)
-        if dkeep is not None:
-            dkeep = dkeep.contiguous()
-            if dkeep.dtype != x.dtype:
-                dkeep = dkeep.to(x.dtype)
-        dx = torch.empty_like(x)
-        pg = _wants_grad(gamma) and _wants_grad(beta)
-        ws = torch.empty(lib.sidlsg_layernorm_bwd_nblocks.raw(rows) * C * 2, device=x.device, dtype=F32) if pg else None
-        h = _defer_begin(x.device) if pg else None
-        _fn('layernorm_bwd', x.dtype)(_p(x), _p(dy), _p(stats), _p(gamma), _p(dkeep) if dkeep is not None else None, _p(dx),
-                                      _p(gamma.grad) if pg else None, _p(beta.grad) if pg else None, _p(ws), rows, C, _s())
-        _defer_end(h, ws)
-        return dx, None, None, None, None
-
-
-class _LayerNormG2(torch.autograd.Function):
-    """_LayerNorm for the grouped pass: token rows of the first half use set 0, of the second half set 1.  Halves whose row count
-    the kernel cannot align its per-wave row ranges with (tiny test networks) run as two ordinary launches on the half views."""
-
-    @staticmethod
-    def forward(ctx, x, gamma, beta, eps, fork):
-        _chk(x, BF16)
-        C = x.shape[-1]
-        rows = x.numel() // C
-        if rows % 2:
-            raise RuntimeError('grouped layernorm: odd row count')
-        half = rows // 2
-        y = torch.empty_like(x)
-        stats = torch.empty((rows, 2), device=x.device, dtype=F32)
-        grouped = half % 16 == 0
-        if grouped:
-            lib.sidlsg_layernorm_fwd_g2(_p(x), _p(gamma[0]), _p(beta[0]), _p(gamma[1]), _p(beta[1]), _p(y), _p(stats), rows, C, float(eps), _s())
-        else:
-            es = x.element_size()
-            for h in (0, 1):
-                lib.sidlsg_layernorm_fwd(x.data_ptr() + h * half * C * es, _p(gamma[h]), _p(beta[h]), y.data_ptr() + h * half * C * es,
-                                         stats.data_ptr() + h * half * 8, half, C, float(eps), _s())
-        ctx.save_for_backward(x, stats)
-        ctx.params, ctx.grouped = gamma, grouped
-        if fork:
-            return y, x.view(x.shape)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy, dkeep=None):
-        x, stats = ctx.saved_tensors
-        gamma = ctx.params
-        if dy is None:
-            return dkeep, None, None, None, None
-        C = x.shape[-1]
-        rows = x.numel() // C
-        half = rows // 2
-        dy = dy.contiguous()
-        if dy.dtype != BF16:
-            dy = dy.to(BF16)
-        if dkeep is not None:
-            dkeep = dkeep.contiguous()
-            if dkeep.dtype != BF16:
-                dkeep = dkeep.to(BF16)
-        dx = torch.empty_like(x)
-        if ctx.grouped:
-            lib.sidlsg_layernorm_bwd_g2(_p(x), _p(dy), _p(stats), _p(gamma[0]), _p(gamma[1]), _p(dkeep) if dkeep is not None else None, _p(dx),
-                                        rows, C, _s())
-        else:
-            es = x.element_size()
-            for h in (0, 1):
-                o = h * half * C * es
-                lib.sidlsg_layernorm_bwd(x.data_ptr() + o, dy.data_ptr() + o, stats.data_ptr() + h * half * 8, _p(gamma[h]),
-                                         dkeep.data_ptr() + o if dkeep is not None else None, dx.data_ptr() + o, None, None, None, half, C, _s())
+        x, stats, (gamma, beta) = _kept(ctx)
+        dx = _layernorm_bwd(x, _gradc(dy, x.dtype), stats, gamma, beta, _gradc(dkeep, x.dtype), ctx.grouped, param_grads=True)
         return dx, None, None, None, None
 
 
 def layer_norm(x, gamma, beta, eps=1e-5, fork=False):
     if _dual is not None:
-        gp, bp = _pair(gamma), _pair(beta)
-        _frozen(gp, bp)
-        return _LayerNormG2.apply(x, gp, bp, eps, fork)
+        gamma, beta = _pair(gamma), _pair(beta)
+        _frozen(gamma, beta)
     return _LayerNorm.apply(x, gamma, beta, eps, fork)
 
 
@@ -1063,13 +1009,9 @@ def gemm_mx8(a8, w8, out=None, bias=None, res=None, out_f32=False):
     ensure_workspace(a8.device)
     if out is None:
         out = torch.empty((M, N), device=a8.device, dtype=F32 if out_f32 else BF16)
-    if g2:
-        lib.sidlsg_gemm_mx8_g2(_p(a8), a8.stride(0), _p(w8[0].q), _p(w8[0].scale), _p(w8[1].q), _p(w8[1].scale), _p(out), out.stride(0),
-                               _p(bias[0]) if bias is not None else None, _p(bias[1]) if bias is not None else None, _p(res),
-                               res.stride(0) if res is not None else 0, None, 0, 1, M, N, K, 1.0, 1 if out_f32 else 0, _s())
-        return out
-    lib.sidlsg_gemm_mx8(_p(a8), a8.stride(0), _p(w8.q), _p(w8.scale), _p(out), out.stride(0), _p(bias), _p(res),
-                        res.stride(0) if res is not None else 0, None, 0, 1, M, N, K, 1.0, 1 if out_f32 else 0, _s())
+    (lib.sidlsg_gemm_mx8_g2 if g2 else lib.sidlsg_gemm_mx8)(
+        _p(a8), a8.stride(0), *_weight_args(w8), _p(out), out.stride(0), *_epilogue_args(g2, bias, res, None), 1, M, N, K, 1.0,
+        1 if out_f32 else 0, _s())
     return out
 
 
@@ -1085,14 +1027,9 @@ def conv3x3_mx8(x8, w8, bias=None, res=None, rowvec=None, out_f32=False):
     Cout = w8.shape[0]
     ensure_workspace(x8.device)
     out = torch.empty((B, H, W, Cout), device=x8.device, dtype=F32 if out_f32 else BF16)
-    if g2:
-        lib.sidlsg_conv3x3_mx8_g2(_p(x8), x8.stride(2), _p(w8[0].q), _p(w8[0].scale), _p(w8[1].q), _p(w8[1].scale), _p(out), Cout,
-                                  _p(bias[0]) if bias is not None else None, _p(bias[1]) if bias is not None else None, _p(res),
-                                  res.stride(2) if res is not None else 0, _p(rowvec), rowvec.stride(0) if rowvec is not None else 0, B, H, W, Cin,
-                                  Cout, 1.0, 1 if out_f32 else 0, _s())
-        return out
-    lib.sidlsg_conv3x3_mx8(_p(x8), x8.stride(2), _p(w8.q), _p(w8.scale), _p(out), Cout, _p(bias), _p(res), res.stride(2) if res is not None else 0,
-                           _p(rowvec), rowvec.stride(0) if rowvec is not None else 0, B, H, W, Cin, Cout, 1.0, 1 if out_f32 else 0, _s())
+    (lib.sidlsg_conv3x3_mx8_g2 if g2 else lib.sidlsg_conv3x3_mx8)(
+        _p(x8), x8.stride(2), *_weight_args(w8), _p(out), Cout, *_epilogue_args(g2, bias, res, rowvec, res_dim=2), B, H, W, Cin, Cout, 1.0,
+        1 if out_f32 else 0, _s())
     return out
 
 
@@ -1109,218 +1046,58 @@ def mx8_ok(w):
     return isinstance(w, Fp8Weight) and w.shape[0] % 160 == 0 and w.shape[1] % 16 == 0
 
 
-class _NormLinearMX8(torch.autograd.Function):
+class _NormLinear(torch.autograd.Function):
     """FROZEN networks with e4m3 weights: y = Linear(Norm(x)) as ONE autograd node -- the GroupNorm / LayerNorm kernel writes
     its output as e4m3 bytes (half the bytes of the bf16 output it replaces), the contraction runs on the MX-fp8 MFMA
-    (sidlsg_gemm_mx8).  One node because the e4m3 intermediate is an integer tensor autograd cannot carry.  Backward (the data
+    (gemm_mx8).  One node because the e4m3 intermediate is an integer tensor autograd cannot carry.  Backward (the data
     gradient the generator's update needs through the frozen networks): dnorm_out = dy W through the bf16 backward-data
-    operand, then the ordinary norm backward on the saved input.  fork: as in _GroupNorm / _LayerNorm."""
+    operand, then the ordinary norm backward on the saved input.  fork: as in _GroupNorm / _LayerNorm.  Grouped (two frozen e4m3
+    networks): gamma / beta / w8 / bias / w16t are Pairs, every launch is the two-set one."""
 
     @staticmethod
     def forward(ctx, x, gamma, beta, eps, groups, silu, fork, w8, bias, w16t, weight):
         _chk(x, BF16)
-        C = x.shape[-1]
-        y8 = torch.empty(x.shape, device=x.device, dtype=torch.uint8)
         if groups:
-            B = x.shape[0]
-            HW = x.numel() // (B * C)
-            n = lib.sidlsg_groupnorm_ws_floats.raw(B, HW, C, groups)
-            if n < 0:
-                raise RuntimeError(f'groupnorm: unsupported shape B={B} HW={HW} C={C} G={groups}')
-            ws = torch.empty(n, device=x.device, dtype=F32)
-            stats = torch.empty((B, groups, 2), device=x.device, dtype=F32)
-            lib.sidlsg_groupnorm_fwd_fp8(_p(x), _p(gamma), _p(beta), _p(y8), _p(stats), _p(ws), B, HW, C, groups, float(eps), int(silu), _s())
-            ctx.cfg = (B, HW, C, groups, int(silu), n)
+            y8, stats, n = _groupnorm_fwd(x, gamma, beta, groups, eps, silu, out_e4m3=True)
+            ctx.cfg = (groups, int(silu), n)
         else:
-            rows = x.numel() // C
-            stats = torch.empty((rows, 2), device=x.device, dtype=F32)
-            lib.sidlsg_layernorm_fwd_fp8(_p(x), _p(gamma), _p(beta), _p(y8), _p(stats), rows, C, float(eps), _s())
+            y8, stats, ctx.grouped = _layernorm_fwd(x, gamma, beta, eps, out_e4m3=True)
             ctx.cfg = None
-        y = gemm_mx8(y8.view(-1, C), w8, bias=bias)
-        ctx.save_for_backward(x, gamma, beta, stats, w16t)
+        y = gemm_mx8(y8.view(-1, x.shape[-1]), w8, bias=bias)
+        _keep(ctx, x, stats, gamma, beta, w16t)
         if fork:
             return y, x.view(x.shape)
         return y
 
     @staticmethod
     def backward(ctx, dy, dkeep=None):
-        x, gamma, beta, stats, w16t = ctx.saved_tensors
         none = (None,) * 10
         if dy is None:
             return (dkeep,) + none
-        dy = dy.contiguous()
-        if dy.dtype != BF16:
-            dy = dy.to(BF16)
-        dn = gemm(dy, w16t)                                        # gradient at the norm's output, [M, C]
-        if dkeep is not None:
-            dkeep = dkeep.contiguous()
-            if dkeep.dtype != BF16:
-                dkeep = dkeep.to(BF16)
-        dx = torch.empty_like(x)
-        C = x.shape[-1]
+        x, stats, (gamma, beta, w16t) = _kept(ctx)
+        dn = gemm(_gradc(dy), w16t)                                # gradient at the norm's output, [M, C]
+        dkeep = _gradc(dkeep)
         if ctx.cfg is not None:
-            B, HW, C, groups, silu, n = ctx.cfg
-            ws = torch.empty(n, device=x.device, dtype=F32)
-            lib.sidlsg_groupnorm_bwd(_p(x), _p(dn), _p(stats), _p(gamma), _p(beta), _p(dkeep) if dkeep is not None else None, _p(dx),
-                                     None, None, _p(ws), B, HW, C, groups, silu, _s())
+            dx = _groupnorm_bwd(x, dn, stats, gamma, beta, dkeep, ctx.cfg)
         else:
-            rows = x.numel() // C
-            lib.sidlsg_layernorm_bwd(_p(x), _p(dn), _p(stats), _p(gamma), _p(dkeep) if dkeep is not None else None, _p(dx), None, None, None,
-                                     rows, C, _s())
+            dx = _layernorm_bwd(x, dn, stats, gamma, beta, dkeep, ctx.grouped)
         return (dx,) + none
 
 
-class _NormConvMX8(torch.autograd.Function):
+class _NormConv(torch.autograd.Function):
     """FROZEN networks: y = conv3x3(SiLU(GroupNorm(x))) + bias + rowvec (+ res) as one autograd node with the e4m3 image in
-    between (see _NormLinearMX8).  Backward: data gradient of the conv through the bf16 backward-data operand (flipped taps),
-    then the GroupNorm + SiLU backward on the saved input; res receives dy."""
+    between (see _NormLinear).  Backward: data gradient of the conv through the bf16 backward-data operand (flipped taps),
+    then the GroupNorm + SiLU backward on the saved input; res receives dy, rowvec its per-sample column sums.  Grouped: as
+    _NormLinear."""
 
     @staticmethod
     def forward(ctx, x, gamma, beta, eps, groups, fork, w8, bias, w16t, weight, res, rowvec):
         _chk(x, BF16)
-        B, H, W, C = x.shape
-        HW = H * W
-        n = lib.sidlsg_groupnorm_ws_floats.raw(B, HW, C, groups)
-        if n < 0:
-            raise RuntimeError(f'groupnorm: unsupported shape B={B} HW={HW} C={C} G={groups}')
-        ws = torch.empty(n, device=x.device, dtype=F32)
-        stats = torch.empty((B, groups, 2), device=x.device, dtype=F32)
-        y8 = torch.empty(x.shape, device=x.device, dtype=torch.uint8)
-        lib.sidlsg_groupnorm_fwd_fp8(_p(x), _p(gamma), _p(beta), _p(y8), _p(stats), _p(ws), B, HW, C, groups, float(eps), 1, _s())
+        y8, stats, n = _groupnorm_fwd(x, gamma, beta, groups, eps, 1, out_e4m3=True)
         y = conv3x3_mx8(y8, w8, bias=bias, res=res, rowvec=rowvec)
-        ctx.save_for_backward(x, gamma, beta, stats, w16t)
-        ctx.cfg = (B, HW, C, groups, n, res is not None)
-        if fork:
-            return y, x.view(x.shape)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy, dkeep=None):
-        x, gamma, beta, stats, w16t = ctx.saved_tensors
-        B, HW, C, groups, n, has_res = ctx.cfg
-        if dy is None:
-            return (dkeep,) + (None,) * 11
-        dy = dy.contiguous()
-        if dy.dtype != BF16:
-            dy = dy.to(BF16)
-        dn = conv3x3(dy, w16t)                                     # gradient at the conv's input, [B,H,W,C]
-        if dkeep is not None:
-            dkeep = dkeep.contiguous()
-            if dkeep.dtype != BF16:
-                dkeep = dkeep.to(BF16)
-        dx = torch.empty_like(x)
-        ws = torch.empty(n, device=x.device, dtype=F32)
-        lib.sidlsg_groupnorm_bwd(_p(x), _p(dn), _p(stats), _p(gamma), _p(beta), _p(dkeep) if dkeep is not None else None, _p(dx),
-                                 None, None, _p(ws), B, HW, C, groups, 1, _s())
-        dres = dy if (has_res and ctx.needs_input_grad[10]) else None
-        return (dx,) + (None,) * 9 + (dres, None)
-
-
-def groupnorm_fp8_g2(x, gamma, beta, groups, eps, silu):
-    """Grouped GroupNorm (+ SiLU) with an e4m3 output: x [B, ..., C] bf16 (B even), gamma / beta Pairs -> (y8, stats, ws floats)."""
-    B, C = x.shape[0], x.shape[-1]
-    HW = x.numel() // (B * C)
-    n = lib.sidlsg_groupnorm_ws_floats.raw(B, HW, C, groups)
-    if n < 0 or B % 2:
-        raise RuntimeError(f'grouped groupnorm: unsupported shape B={B} HW={HW} C={C} G={groups}')
-    ws = torch.empty(n, device=x.device, dtype=F32)
-    stats = torch.empty((B, groups, 2), device=x.device, dtype=F32)
-    y8 = torch.empty(x.shape, device=x.device, dtype=torch.uint8)
-    lib.sidlsg_groupnorm_fwd_fp8_g2(_p(x), _p(gamma[0]), _p(beta[0]), _p(gamma[1]), _p(beta[1]), _p(y8), _p(stats), _p(ws), B, HW, C, groups,
-                                    float(eps), int(silu), _s())
-    return y8, stats, n
-
-
-def layernorm_fp8_g2(x, gamma, beta, eps):
-    """Grouped LayerNorm with an e4m3 output: x [..., C] bf16 (even row count), gamma / beta Pairs -> (y8, stats, grouped).  As in
-    _LayerNormG2: halves the kernel cannot align its per-wave row ranges with run as two ordinary launches on the half views."""
-    C = x.shape[-1]
-    rows = x.numel() // C
-    if rows % 2:
-        raise RuntimeError('grouped layernorm: odd row count')
-    half = rows // 2
-    y8 = torch.empty(x.shape, device=x.device, dtype=torch.uint8)
-    stats = torch.empty((rows, 2), device=x.device, dtype=F32)
-    grouped = half % 16 == 0
-    if grouped:
-        lib.sidlsg_layernorm_fwd_fp8_g2(_p(x), _p(gamma[0]), _p(beta[0]), _p(gamma[1]), _p(beta[1]), _p(y8), _p(stats), rows, C, float(eps), _s())
-    else:
-        for h in (0, 1):
-            lib.sidlsg_layernorm_fwd_fp8(x.data_ptr() + h * half * C * x.element_size(), _p(gamma[h]), _p(beta[h]), y8.data_ptr() + h * half * C,
-                                         stats.data_ptr() + h * half * 8, half, C, float(eps), _s())
-    return y8, stats, grouped
-
-
-def _bf16c(t):
-    if t is None:
-        return None
-    t = t.contiguous()
-    return t if t.dtype == BF16 else t.to(BF16)
-
-
-class _NormLinearMX8G2(torch.autograd.Function):
-    """_NormLinearMX8 for the grouped pass of two frozen e4m3 networks: gamma / beta / w8 / bias / w16t are Pairs.  Forward = grouped
-    e4m3 norm + sidlsg_gemm_mx8_g2; backward (data gradient only) = the bf16 grouped GEMM on the paired backward-data operands, then
-    the bf16 grouped norm backward."""
-
-    @staticmethod
-    def forward(ctx, x, gamma, beta, eps, groups, silu, fork, w8, bias, w16t):
-        _chk(x, BF16)
-        C = x.shape[-1]
-        if groups:
-            y8, stats, n = groupnorm_fp8_g2(x, gamma, beta, groups, eps, silu)
-            ctx.cfg = (x.shape[0], x.numel() // (x.shape[0] * C), C, groups, int(silu), n)
-        else:
-            y8, stats, ctx.grouped = layernorm_fp8_g2(x, gamma, beta, eps)
-            ctx.cfg = None
-        y = gemm_mx8(y8.view(-1, C), w8, bias=bias)
-        ctx.save_for_backward(x, stats)
-        ctx.params = (gamma, beta, w16t)
-        if fork:
-            return y, x.view(x.shape)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy, dkeep=None):
-        x, stats = ctx.saved_tensors
-        gamma, beta, w16t = ctx.params
-        none = (None,) * 9
-        if dy is None:
-            return (dkeep,) + none
-        dn = gemm(_bf16c(dy), w16t)
-        dkeep = _bf16c(dkeep)
-        dx = torch.empty_like(x)
-        C = x.shape[-1]
-        if ctx.cfg is not None:
-            B, HW, C, groups, silu, n = ctx.cfg
-            ws = torch.empty(n, device=x.device, dtype=F32)
-            lib.sidlsg_groupnorm_bwd_g2(_p(x), _p(dn), _p(stats), _p(gamma[0]), _p(beta[0]), _p(gamma[1]), _p(beta[1]), _p(dkeep), _p(dx), _p(ws),
-                                        B, HW, C, groups, silu, _s())
-        else:
-            rows = x.numel() // C
-            if ctx.grouped:
-                lib.sidlsg_layernorm_bwd_g2(_p(x), _p(dn), _p(stats), _p(gamma[0]), _p(gamma[1]), _p(dkeep), _p(dx), rows, C, _s())
-            else:
-                half = rows // 2
-                for h in (0, 1):
-                    o = h * half * C * x.element_size()
-                    lib.sidlsg_layernorm_bwd(x.data_ptr() + o, dn.data_ptr() + o, stats.data_ptr() + h * half * 8, _p(gamma[h]),
-                                             dkeep.data_ptr() + o if dkeep is not None else None, dx.data_ptr() + o, None, None, None, half, C, _s())
-        return (dx,) + none
-
-
-class _NormConvMX8G2(torch.autograd.Function):
-    """_NormConvMX8 for the grouped pass of two frozen e4m3 networks (Pairs; data gradient only, through the bf16 grouped kernels)."""
-
-    @staticmethod
-    def forward(ctx, x, gamma, beta, eps, groups, fork, w8, bias, w16t, res, rowvec):
-        _chk(x, BF16)
-        B, H, W, C = x.shape
-        y8, stats, n = groupnorm_fp8_g2(x, gamma, beta, groups, eps, 1)
-        y = conv3x3_mx8(y8, w8, bias=bias, res=res, rowvec=rowvec)
-        ctx.save_for_backward(x, stats)
-        ctx.params = (gamma, beta, w16t)
-        ctx.cfg = (B, H * W, C, groups, n, res is not None, rowvec is not None)
+        _keep(ctx, x, stats, gamma, beta, w16t)
+        ctx.cfg = (groups, 1, n)
+        ctx.has_res, ctx.has_rv = res is not None, rowvec is not None
         ctx.rv_slot = getattr(rowvec, '_col_slot', None)
         if fork:
             return y, x.view(x.shape)
@@ -1328,22 +1105,18 @@ class _NormConvMX8G2(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy, dkeep=None):
-        x, stats = ctx.saved_tensors
-        gamma, beta, w16t = ctx.params
-        B, HW, C, groups, n, has_res, has_rv = ctx.cfg
         if dy is None:
-            return (dkeep,) + (None,) * 10
-        dy = _bf16c(dy)
-        dn = conv3x3(dy, w16t)
-        dkeep = _bf16c(dkeep)
-        dx = torch.empty_like(x)
-        ws = torch.empty(n, device=x.device, dtype=F32)
-        lib.sidlsg_groupnorm_bwd_g2(_p(x), _p(dn), _p(stats), _p(gamma[0]), _p(beta[0]), _p(gamma[1]), _p(beta[1]), _p(dkeep), _p(dx), _p(ws),
-                                    B, HW, C, groups, 1, _s())
-        dres = dy if (has_res and ctx.needs_input_grad[9]) else None
-        Cout = dy.shape[-1]
-        drv = colsum(dy.view(B * HW, Cout), HW, per_batch=True, slot=ctx.rv_slot) if (has_rv and ctx.needs_input_grad[10]) else None
-        return (dx,) + (None,) * 8 + (dres, drv)
+            return (dkeep,) + (None,) * 11
+        x, stats, (gamma, beta, w16t) = _kept(ctx)
+        dy = _gradc(dy)
+        dn = _conv_dgrad(dy, w16t, x.shape, 1, 0, BF16)           # gradient at the conv's input, [B,H,W,C]
+        dx = _groupnorm_bwd(x, dn, stats, gamma, beta, _gradc(dkeep), ctx.cfg)
+        dres = dy if (ctx.has_res and ctx.needs_input_grad[10]) else None
+        drv = None
+        if ctx.has_rv and ctx.needs_input_grad[11]:
+            B, H, W, Cout = dy.shape
+            drv = colsum(dy.view(B * H * W, Cout), H * W, per_batch=True, slot=ctx.rv_slot)
+        return (dx,) + (None,) * 9 + (dres, drv)
 
 
 def _mx8_no_weight_grads(weight, gamma):
@@ -1352,24 +1125,26 @@ def _mx8_no_weight_grads(weight, gamma):
         raise RuntimeError('the MX-fp8 path is for passes without weight gradients (frozen network, or torch.no_grad())')
 
 
+def _mx8_params(weight, gamma, beta, w8, bias, w16t):
+    """The parameters of an e4m3 node as it takes them: as they are (after the frozen check) or, inside dual_networks, as Pairs."""
+    if _dual is None:
+        _mx8_no_weight_grads(weight, gamma)
+        return weight, gamma, beta, w8, bias, w16t
+    wp, gp, bp, cb = _pair(weight), _pair(gamma), _pair(beta), _pair(bias)
+    _frozen(wp, gp, bp, cb)
+    return None, gp, bp, _pair(w8), cb, _pair(w16t)
+
+
 def norm_conv_mx8(x, gamma, beta, eps, groups, w8, bias, w16t, weight, res=None, rowvec=None, fork=False):
     """conv3x3(SiLU(GroupNorm(x))) for a frozen network, e4m3 in between."""
-    if _dual is not None:
-        wp, gp, bp, cb = _pair(weight), _pair(gamma), _pair(beta), _pair(bias)
-        _frozen(wp, gp, bp, cb)
-        return _NormConvMX8G2.apply(x, gp, bp, eps, groups, fork, _pair(w8), cb, _pair(w16t), res, rowvec)
-    _mx8_no_weight_grads(weight, gamma)
-    return _NormConvMX8.apply(x, gamma, beta, eps, groups, fork, w8, bias, w16t, weight, res, rowvec)
+    weight, gamma, beta, w8, bias, w16t = _mx8_params(weight, gamma, beta, w8, bias, w16t)
+    return _NormConv.apply(x, gamma, beta, eps, groups, fork, w8, bias, w16t, weight, res, rowvec)
 
 
 def norm_linear_mx8(x, gamma, beta, eps, w8, bias, w16t, weight, groups=0, silu=False, fork=False):
     """Linear(GroupNorm(x)) (groups > 0) or Linear(LayerNorm(x)) (groups = 0) for a frozen network, e4m3 in between."""
-    if _dual is not None:
-        wp, gp, bp, cb = _pair(weight), _pair(gamma), _pair(beta), _pair(bias)
-        _frozen(wp, gp, bp, cb)
-        return _NormLinearMX8G2.apply(x, gp, bp, eps, groups, silu, fork, _pair(w8), cb, _pair(w16t))
-    _mx8_no_weight_grads(weight, gamma)
-    return _NormLinearMX8.apply(x, gamma, beta, eps, groups, silu, fork, w8, bias, w16t, weight)
+    weight, gamma, beta, w8, bias, w16t = _mx8_params(weight, gamma, beta, w8, bias, w16t)
+    return _NormLinear.apply(x, gamma, beta, eps, groups, silu, fork, w8, bias, w16t, weight)
 
 
 _ATTN_ALWAYS_KV = os.environ.get('SIDLSG_ATTN_SKIP_KV', '1') == '0'      # A/B switch: compute dK / dV even when nobody wants them
@@ -1517,9 +1292,7 @@ class _LinearGEGLU(torch.autograd.Function):
         elif dh is None:
             return None, None, None, None, None, None, None
         else:
-            dh = dh.contiguous()
-            if dh.dtype != BF16:
-                dh = dh.to(BF16)
+            dh = _gradc(dh)
         dx = gemm(dh, w16t) if ctx.needs_input_grad[0] else None
         if _wants_grad(weight):
             M, K = x.shape
@@ -1576,9 +1349,7 @@ class _GegluLinear(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         h, y, weight, bias, w16t = ctx.saved_tensors
-        dout = dout.contiguous()
-        if dout.dtype != BF16:
-            dout = dout.to(BF16)
+        dout = _gradc(dout)
         M, F2 = h.shape
         K = dout.shape[1]
         dh = None
@@ -1638,9 +1409,7 @@ class _FeedForwardG2(torch.autograd.Function):
     def backward(ctx, dout):
         (h,) = ctx.saved_tensors
         w1_16t, w2_16t = ctx.ops
-        dout = dout.contiguous()
-        if dout.dtype != BF16:
-            dout = dout.to(BF16)
+        dout = _gradc(dout)
         dx = None
         if ctx.needs_input_grad[0]:
             M, F2 = h.shape

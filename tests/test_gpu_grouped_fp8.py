@@ -181,7 +181,7 @@ def test_groupnorm_fp8_g2_equals_two_launches(dev, Bh, HW, C, G, silu):
     assert not torch.equal(y8[Bh:], single(x[Bh:].contiguous(), g0, be0)[0]), 'the second half must have used the second parameter set'
 
 
-# 77 rows per half: no multiple of the kernel's rows per wave -- ops runs the halves as two ordinary launches (as ops._LayerNormG2 does);
+# 77 rows per half: no multiple of the kernel's rows per wave -- ops runs the halves as two ordinary launches (ops._layernorm_fwd, as for ops.layer_norm);
 # 256: the grouped launch
 @pytest.mark.parametrize('rows_h,C', [(77, 160), (256, 320)])
 def test_layernorm_fp8_g2_equals_two_launches(dev, rows_h, C):
