@@ -23,6 +23,15 @@ sid_lsg_amd.sd_util.teacher_sample), with the same seeds, prompts and file names
 `--teacher_sampler {ddim,dpmpp2m}`, `--teacher_spacing {leading,trailing,linspace}`, `--teacher_eta`, `--guidance_rescale` and
 `--negative_prompt` choose the solver family of sd_util.teacher_sample_solver instead (DPM-Solver++ 2M, stochastic DDIM, 'trailing'
 spacing with guidance rescale as SD 2.1 768-v is usually run); with none of them given the DDIM path above runs unchanged.
+`--network teacher --init_images DIR --strength S` is image-to-image with the teacher, under every sampler option above: the chain of
+`--teacher_steps` steps is entered at step k = N - min(int(N S), N) (sd_util.teacher_start_index, diffusers' rule) from the encoded
+image noised to t_k with the sample's z.  `--strength` has no default here and must be given.
+
+`--mask_images DIR` (with `--init_images`) is inpainting: one mask file, or one per init image (sorted by name; sample `idx` uses
+file `idx % len`), white = repaint.  A mask gets the init image's centre crop and a NEAREST resize; a latent cell is repainted if any
+pixel of its 8 x 8 block is >= 128, so everything marked is repainted (diffusers takes the nearest pixel).  The samplers re-impose the
+kept region at every step boundary (sidlsg_masked_renoise).  `--mask_composite 1` also takes the pixels whose mask value is < 128
+from the init image as loaded, after decoding: the VAE round trip alone changes kept pixels slightly.
 """
 import math
 import os
@@ -36,7 +45,7 @@ import torch
 from sid_lsg_amd import distributed as dist
 from sid_lsg_amd.preview import save_png
 from sid_lsg_amd.sd_util import (TEACHER, TEACHER_CFG, TEACHER_STEPS, check_prediction_type, load_sd15, load_vae_encoder, sid_sd_sampler,
-                                 teacher_sample, teacher_sample_solver)
+                                 teacher_sample_i2i, teacher_sample_solver_i2i, teacher_start_index)
 
 
 class StackedRandomGenerator:
@@ -156,6 +165,77 @@ def init_image_options(network_pkl, init_images, strength, sample_posterior, num
     return files, strength_to_step(1.0 if strength is None else strength, num_steps_eval), bool(sample_posterior)
 
 
+def teacher_init_image_options(init_images, strength, sample_posterior, teacher_steps):
+    """--network teacher with --init_images -> (files, entry step k of the --teacher_steps chain, sample the posterior?).  --strength
+    has no natural default for the teacher (diffusers' 0.8 is not this tool's 1.0) and must be given."""
+    if strength is None:
+        raise click.UsageError(f'--init_images with --network {TEACHER}: image-to-image with the teacher sampler needs an explicit --strength '
+                               '(the share of the --teacher_steps steps that run)')
+    try:
+        k = teacher_start_index(teacher_steps, strength)
+    except ValueError as e:
+        raise click.UsageError(f'--strength {strength:g} with --network {TEACHER}: {e}')
+    return list_init_images(init_images), k, bool(sample_posterior)
+
+
+def image_to_image_options(network_pkl, init_images, strength, sample_posterior, num_steps_eval, teacher_steps=None):
+    """init_image_options for a snapshot (and for every refusal without --init_images), teacher_init_image_options for the teacher."""
+    if network_pkl == TEACHER and init_images is not None:
+        return teacher_init_image_options(init_images, strength, sample_posterior, TEACHER_STEPS if teacher_steps is None else teacher_steps)
+    return init_image_options(network_pkl, init_images, strength, sample_posterior, num_steps_eval)
+
+
+def list_mask_images(path, num_init):
+    """The PNG / JPEG files of --mask_images, sorted by name: one for all samples, or one per init image."""
+    if not os.path.isdir(path):
+        raise click.UsageError(f'--mask_images {path}: not a directory')
+    files = sorted(f for f in os.listdir(path) if f.lower().endswith(IMAGE_EXTENSIONS) and os.path.isfile(os.path.join(path, f)))
+    if len(files) not in (1, num_init):
+        raise click.UsageError(f'--mask_images {path}: {len(files)} PNG or JPEG files, expected 1 or one per init image ({num_init})')
+    return [os.path.join(path, f) for f in files]
+
+
+def mask_options(init_images, mask_images, mask_composite, num_init):
+    """-> None without --mask_images, else (mask files, composite the kept pixels?); the mask options need --init_images."""
+    if mask_images is None:
+        if mask_composite:
+            raise click.UsageError('--mask_composite applies to --mask_images only')
+        return None
+    if init_images is None:
+        raise click.UsageError('--mask_images applies to --init_images only: the init image is the region that is kept')
+    return list_mask_images(mask_images, num_init), bool(mask_composite)
+
+
+def load_mask_image(path, resolution):
+    """-> uint8 [resolution, resolution]: 'L', the centre crop of load_init_image, resized with PIL's NEAREST filter."""
+    import PIL.Image
+    with PIL.Image.open(path) as im:
+        im = im.convert('L')
+        w, h = im.size
+        side = min(w, h)
+        left, top = (w - side) // 2, (h - side) // 2
+        im = im.crop((left, top, left + side, top + side))
+        if side != resolution:
+            im = im.resize((resolution, resolution), PIL.Image.NEAREST)
+        return np.ascontiguousarray(np.asarray(im, dtype=np.uint8))
+
+
+def load_mask_batch(files, indices, resolution):
+    """Sample idx takes file idx % len(files) -> uint8 [B, resolution, resolution]."""
+    return np.stack([load_mask_image(files[i % len(files)], resolution) for i in indices])
+
+
+def latent_mask(pixel_mask):
+    """uint8 [B, 8h, 8w] pixel masks -> uint8 [B, h, w]: 1 (repaint) where any pixel of the cell's 8 x 8 block is >= 128."""
+    b, H, W = pixel_mask.shape
+    return (pixel_mask.reshape(b, H // 8, 8, W // 8, 8) >= 128).any(axis=(2, 4)).astype(np.uint8)
+
+
+def composite(generated, init_pixels, pixel_mask):
+    """uint8 [B, H, W, 3] generated and init pixels, uint8 [B, H, W] masks -> the init pixels where the mask is < 128."""
+    return np.where((pixel_mask >= 128)[..., None], generated, init_pixels)
+
+
 @click.command()
 @click.option('--network', 'network_pkl', type=str, required=True, metavar='PATH', help=f'Network snapshot pickle, or "{TEACHER}": sample the UNet of --repo_id itself')
 @click.option('--outdir', type=str, required=True, metavar='DIR', help='Where to save the output images')
@@ -183,16 +263,19 @@ def init_image_options(network_pkl, init_images, strength, sample_posterior, num
               help='With --init_images: share of the --num_steps_eval steps that run, k = N - ceil(S N) is the entry step; a one-step '
                    'generator has no such choice, its knob is --init_timestep  [default: 1]')
 @click.option('--sample_posterior', type=bool, default=None, help='With --init_images: sample the VAE posterior (eps from the per-seed generator, after z) instead of its mean  [default: False]')
+@click.option('--mask_images', type=str, default=None, metavar='DIR', help='Inpainting, with --init_images: mask files (sorted by name; one for all, or one per init image), >= 128 = repaint')
+@click.option('--mask_composite', type=bool, default=False, show_default=True, help='With --mask_images: take the pixels whose mask value is < 128 from the init image after decoding')
 @click.option('--text_encoder', type=click.Choice(['torch', 'hip']), default=None, help='CLIP text encoder: the PyTorch module, or the same weights on the HIP kernels  [default: $SIDLSG_TEXT_ENCODER, else torch] (not a reference option)')
 def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, init_timestep, text_prompts, repo_id, resolution, use_fp16,
          enable_compress_npz, num_steps_eval, custom_seed, teacher_steps, guidance_scale, init_images, strength, sample_posterior, text_encoder,
-         teacher_sampler, teacher_spacing, teacher_eta, guidance_rescale, negative_prompt):
+         teacher_sampler, teacher_spacing, teacher_eta, guidance_rescale, negative_prompt, mask_images, mask_composite):
     text_encoder_kind = text_encoder
     if resolution % 8:
         raise click.BadParameter(f'{resolution}: must be a multiple of 8', param_hint='--resolution')
     teacher = teacher_options(network_pkl, teacher_steps, guidance_scale)
     solver_kw = teacher_solver_options(network_pkl, teacher_sampler, teacher_spacing, teacher_eta, guidance_rescale, negative_prompt)
-    img2img = init_image_options(network_pkl, init_images, strength, sample_posterior, num_steps_eval)
+    img2img = image_to_image_options(network_pkl, init_images, strength, sample_posterior, num_steps_eval, teacher_steps)
+    masks = mask_options(init_images, mask_images, mask_composite, 0 if img2img is None else len(img2img[0]))
     dist.init()
     device = torch.device('cuda')
     rank, world = dist.get_rank(), dist.get_world_size()
@@ -224,7 +307,10 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
             dist.print0(f'Note: --num_steps_eval {num_steps_eval} is ignored with --network {TEACHER} (the step count is --teacher_steps)')
     if img2img is not None:
         vae_encoder = load_vae_encoder(repo_id, device)
-        dist.print0(f'Image-to-image: {len(img2img[0])} init images from "{init_images}", entering at step {img2img[1]} of {num_steps_eval}')
+        dist.print0(f'Image-to-image: {len(img2img[0])} init images from "{init_images}", entering at step {img2img[1]} of '
+                    f'{num_steps_eval if teacher is None else teacher[0]}')
+    if masks is not None:
+        dist.print0(f'Inpainting: {len(masks[0])} mask image(s) from "{mask_images}"' + (', kept pixels composited from the init images' if masks[1] else ''))
     if world > 1 and rank == 0:
         torch.distributed.barrier()
     if teacher is None and num_steps_eval > 1:
@@ -245,21 +331,25 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
         i2i = {}
         if img2img is not None:
             files, start_step, sample = img2img
-            pixels = torch.from_numpy(load_init_batch(files, batch, resolution)).to(device)
+            init_pixels = load_init_batch(files, batch, resolution)
+            pixels = torch.from_numpy(init_pixels).to(device)
             eps = rnd.randn([len(batch), 4, lat, lat], device=device) if sample else None
-            i2i = dict(init_latents=vae_encoder.encode_latents(pixels, eps=eps), start_step=start_step)
+            i2i = {'init_latents': vae_encoder.encode_latents(pixels, eps=eps), 'start_step' if teacher is None else 'start_index': start_step}
+            if masks is not None:
+                pixel_mask = load_mask_batch(masks[0], batch, resolution)
+                i2i['mask'] = torch.from_numpy(latent_mask(pixel_mask)).to(device)
         with torch.no_grad():
             if teacher is not None and solver_kw is not None:
                 kw = {k: v for k, v in solver_kw.items() if k != 'negative_prompt'}
                 neg = None if solver_kw['negative_prompt'] is None else [solver_kw['negative_prompt']] * len(batch)
-                images = teacher_sample_solver(unet=G_ema, latents=z, contexts=prompts, noise_scheduler=sched, text_encoder=text_encoder,
+                images = teacher_sample_solver_i2i(unet=G_ema, latents=z, contexts=prompts, noise_scheduler=sched, text_encoder=text_encoder,
                                                tokenizer=tokenizer, resolution=resolution, guidance_scale=teacher[1],
                                                num_inference_steps=teacher[0], return_images=True, vae=vae, negative_contexts=neg,
-                                               randn=lambda shape: rnd.randn(list(shape), device=device), **kw)
+                                               randn=lambda shape: rnd.randn(list(shape), device=device), **kw, **i2i)
             elif teacher is not None:
-                images = teacher_sample(unet=G_ema, latents=z, contexts=prompts, noise_scheduler=sched, text_encoder=text_encoder,
+                images = teacher_sample_i2i(unet=G_ema, latents=z, contexts=prompts, noise_scheduler=sched, text_encoder=text_encoder,
                                         tokenizer=tokenizer, resolution=resolution, guidance_scale=teacher[1],
-                                        num_inference_steps=teacher[0], return_images=True, vae=vae)
+                                        num_inference_steps=teacher[0], return_images=True, vae=vae, **i2i)
             else:
                 images = sid_sd_sampler(unet=G_ema, latents=z, contexts=prompts,
                                         init_timesteps=init_timestep * torch.ones(len(batch), device=device, dtype=torch.long),
@@ -267,6 +357,8 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
                                         dtype=torch.bfloat16, return_images=True, vae=vae, num_steps=1, train_sampler=False,
                                         num_steps_eval=num_steps_eval, **i2i)
         arr = (images.float() * 127.5 + 128).clip(0, 255).to(torch.uint8).permute(0, 2, 3, 1).cpu().numpy()
+        if masks is not None and masks[1]:
+            arr = composite(arr, init_pixels, pixel_mask)
         for key, img in zip(batch, arr):
             d = os.path.join(outdir, f'{key - key % 1000:06d}') if subdirs else outdir
             os.makedirs(d, exist_ok=True)

@@ -281,6 +281,18 @@ int sidlsg_solver_step(const float* eps, const float* xt, const float* s0, const
  * the C*HW real channels, centred (two passes), summed in a fixed order without atomics; std(g_b) = 0 gives the factor 1 (diffusers
  * yields NaN).  C*HW < 2 or a NULL pointer -> SIDLSG_EINVAL. */
 int sidlsg_cfg_rescale_stats(const float* eps, float* scale, int B, int C, int HW, int Ce, float kappa, float phi, void* stream);
+/* masked_renoise (csrc/inpaint.hip): the masked step boundary of inpainting as one launch, forward only.  x fp32 NCHW [B][C][HW] is
+ * what a sampler step produced at its target level, z0 fp32 NCHW the scaled init latents, noise fp32 NCHW the initial noise (may be
+ * NULL), mask uint8 [B][HW], or [1][HW] when mask_shared != 0 (nonzero: repaint), a0 / a1 [B] the coefficients of the target level
+ * (a0 NULL means 1; a1 is given exactly when noise is):
+ *   known = a0*z0 + a1*noise: rounded a1*noise, then one fma -- bit-equal to the fp32 x_t of noisy_input(z0, noise, a0, a1); without
+ *   noise known = a0*z0 (one rounded product), without noise and a0 it is z0 itself;  xn = mask ? x : known, a select
+ *   -> xn fp32 NCHW (may be x itself) and, when out != NULL, the next network input NHWC [dup*B][HW][Cp] activations (both halves
+ *   equal, channels C.. zero), bit-equal to noisy_input(NULL, xn, 1, 1, dup).
+ * A NULL x / z0 / mask / xn, C > 8, Cp % 8 or Cp < 8, dup other than 1 / 2, noise without a1 or a1 without noise, B*HW > 2^31 - 1
+ * -> SIDLSG_EINVAL, nothing launched. */
+int sidlsg_masked_renoise(const float* x, const float* z0, const float* noise, const unsigned char* mask, const float* a0,
+                          const float* a1, void* out, float* xn, int B, int C, int HW, int Cp, int dup, int mask_shared, void* stream);
 
 /* ---- losses with closed-form gradients (sid_training_loop.py:423-445, 508-530) -------------
  * Per-sample NaN filtering is done in-kernel (a sample containing NaN contributes 0 and gets zero
@@ -559,6 +571,9 @@ int sidlsg_ddim_step_f32(const float* eps, const float* xt, const float* s0, con
 int sidlsg_solver_step_f32(const float* eps, const float* xt, const float* s0, const float* s1, const float* coef, const float* x0p,
                            const float* noise, const float* scale, void* out, float* xtn, float* x0, int B, int C, int HW, int Ce,
                            int Cp, int dup, float kappa, int mode, int need_prev, void* stream);
+int sidlsg_masked_renoise_f32(const float* x, const float* z0, const float* noise, const unsigned char* mask, const float* a0,
+                              const float* a1, void* out, float* xn, int B, int C, int HW, int Cp, int dup, int mask_shared,
+                              void* stream);
 int sidlsg_timestep_embed_f32(const long long* t, void* out, int B, int dim, void* stream);
 int sidlsg_silu_fwd_f32(const void* x, void* y, long long n, void* stream);
 int sidlsg_silu_bwd_f32(const void* x, const void* dy, void* dx, long long n, void* stream);

@@ -1649,7 +1649,7 @@ def ddim_step(eps, xt, s0, s1, s0p, s1p, kappa, act_dtype=BF16, prediction_type=
     return out, xtn, x0
 
 
-solver_launches = dict(solver_step=0, cfg_rescale_stats=0)   # launches issued through the two wrappers below (tests count them)
+solver_launches = dict(solver_step=0, cfg_rescale_stats=0, masked_renoise=0)   # launches issued through the wrappers below (tests count them)
 
 
 def cfg_rescale_stats(eps, channels, kappa, phi):
@@ -1701,6 +1701,41 @@ def solver_step(eps, xt, s0, s1, coef, kappa, act_dtype=BF16, prediction_type='e
                                   int(x0p is not None if need_prev is None else need_prev), _s())
     solver_launches['solver_step'] += 1
     return out, xtn, x0
+
+
+def masked_renoise(x, z0, mask, noise=None, a0=None, a1=None, dup=1, act_dtype=BF16, want_input=True, inplace=False, cp=8):
+    """The masked step boundary of inpainting (sidlsg_masked_renoise): x fp32 NCHW is what a sampler step produced at its target level,
+    z0 the scaled init latents, `mask` uint8 / bool [B,h,w] or [1,h,w] (nonzero: repaint), noise the initial noise and a0 / a1 [B] the
+    coefficients of the target level: known = a0*z0 + a1*noise with the roundings of noisy_input (a0 None means 1; without noise and
+    a0, z0 itself), x_n = mask ? x : known -- a select.  `inplace` writes x_n over x.  Returns (next network input NHWC
+    [dup*B,h,w,cp] of `act_dtype` -- the bits of noisy_input(None, x_n, 1, 1, dup) -- or None unless `want_input`; x_n fp32 NCHW).
+    Forward only."""
+    tensors = (x, z0, noise, a0, a1)
+    if torch.is_grad_enabled() and any(torch.is_tensor(v) and v.requires_grad for v in tensors):
+        raise RuntimeError('masked_renoise is forward only: call it under torch.no_grad() (the masked samplers are not differentiated)')
+    if x.dim() != 4:
+        raise RuntimeError(f'masked_renoise: x {tuple(x.shape)} is not [B, C, h, w]')
+    B, C, H, W = x.shape
+    for name, v in (('z0', z0), ('noise', noise)):
+        if v is not None and tuple(v.shape) != tuple(x.shape):
+            raise RuntimeError(f'masked_renoise: {name} {tuple(v.shape)} does not match x {tuple(x.shape)}')
+    if mask.dtype not in (torch.uint8, torch.bool) or mask.dim() != 3 or tuple(mask.shape[1:]) != (H, W) or mask.shape[0] not in (1, B):
+        raise RuntimeError(f'masked_renoise: mask {tuple(mask.shape)} {mask.dtype} is not a uint8 / bool [{B} or 1, {H}, {W}]')
+    for name, v in (('a0', a0), ('a1', a1)):
+        if v is not None and v.numel() != B:
+            raise RuntimeError(f'masked_renoise: {name} has {v.numel()} elements, the batch has {B}')
+    if (noise is None) != (a1 is None):
+        raise RuntimeError('masked_renoise: noise and a1 are given together or not at all')
+    m = _chk(mask, mask.dtype)
+    m = m.view(torch.uint8) if m.dtype == torch.bool else m
+    shared = int(mask.shape[0] == 1 and B > 1)
+    out = torch.empty((dup * B, H, W, cp), device=x.device, dtype=act_dtype) if want_input else None
+    xn = x if inplace else torch.empty_like(x)
+    opt = lambda v: None if v is None else _chk(v, F32)  # noqa: E731
+    _fn('masked_renoise', act_dtype)(_p(_chk(x, F32)), _p(_chk(z0, F32)), _p(opt(noise)), _p(m), _p(opt(a0)), _p(opt(a1)), _p(out), _p(xn),
+                                     B, C, H * W, int(cp), int(dup), shared, _s())
+    solver_launches['masked_renoise'] += 1
+    return out, xn
 
 
 class _GLoss(torch.autograd.Function):

@@ -68,7 +68,7 @@ SOLVERS = ('ddim', 'dpmpp2m')
 SPACINGS = ('leading', 'trailing', 'linspace')
 
 
-def solver_tables(scheduler, config_dict, num_inference_steps, solver='dpmpp2m', spacing=None, eta=0.0):
+def solver_tables(scheduler, config_dict, num_inference_steps, solver='dpmpp2m', spacing=None, eta=0.0, start=0):
     """The timesteps and update coefficients of an N-step teacher sampler for sidlsg_solver_step.  One step from s (now) to t
     (target) is  x_t = c_x*x_s + c_cur*x0_s + c_prev*x0_r + c_n*xi  with x0_s the x0 prediction at s, x0_r that of the step before
     and xi fresh N(0, 1) noise.  With abar the scheduler's alphas_cumprod, alpha = sqrt(abar), sigma = sqrt(1 - abar),
@@ -87,7 +87,10 @@ def solver_tables(scheduler, config_dict, num_inference_steps, solver='dpmpp2m',
       any step onto abar = 1 (dpmpp2m's last one): the row (0, 1, 0, 0) exactly -- x_t is the x0 prediction, no lambda = inf is formed.
 
     These rules restate diffusers 0.27.2's DDIMScheduler and DPMSolverMultistepScheduler; agreement with the package is not pinned
-    by a test.  `config_dict` as ddim_schedule (steps_offset, set_alpha_to_one, timestep_spacing); `spacing` None takes its
+    by a test.  `start` = k (image-to-image: the chain is entered at step k, 0 <= k < N, sd_util.teacher_start_index): 'dpmpp2m' has no
+    x0 history at its first executed step, so row k is the first-order row (sigma_t/sigma_s, A, 0, 0) that step 0 has; every other row,
+    the timesteps and alpha / sigma do not depend on it, and 'ddim' has no history at all.  The tables keep N rows, the loop indexes
+    them from k.  `config_dict` as ddim_schedule (steps_offset, set_alpha_to_one, timestep_spacing); `spacing` None takes its
     timestep_spacing.  All arithmetic is fp64 from the scheduler's own fp32 alphas_cumprod.
     -> numpy (timesteps int64[N], alpha f64[N], sigma f64[N] at t_i, coef f64[N, 4] = (c_x, c_cur, c_prev, c_n)); solver_schedule
     rounds them to fp32 once.  Raises ValueError naming the argument it refuses."""
@@ -112,6 +115,9 @@ def solver_tables(scheduler, config_dict, num_inference_steps, solver='dpmpp2m',
         raise ValueError(f'num_inference_steps={N}: expected at least 1')
     if N > T:
         raise ValueError(f'num_inference_steps={N}: more than num_train_timesteps={T}')
+    start = int(start)
+    if not 0 <= start < N:
+        raise ValueError(f'start={start}: expected a step in [0, {N})')
     offset = int(c.get('steps_offset', 0))
     i = np.arange(N, dtype=np.int64)
     if spacing == 'trailing':
@@ -152,7 +158,7 @@ def solver_tables(scheduler, config_dict, num_inference_steps, solver='dpmpp2m',
         else:
             h = lam(a_t[k]) - lam(a_s[k])
             A = -al_t * np.expm1(-h)
-            if k == 0:
+            if k == start or k == 0:
                 coef[k] = (sg_t / sg_s, A, 0.0, 0.0)
             else:
                 r0 = (lam(a_s[k]) - lam(a_s[k - 1])) / h
@@ -160,10 +166,10 @@ def solver_tables(scheduler, config_dict, num_inference_steps, solver='dpmpp2m',
     return t.copy(), np.sqrt(a_s), np.sqrt(1 - a_s), coef
 
 
-def solver_schedule(scheduler, config_dict, num_inference_steps, solver='dpmpp2m', spacing=None, eta=0.0):
+def solver_schedule(scheduler, config_dict, num_inference_steps, solver='dpmpp2m', spacing=None, eta=0.0, start=0):
     """solver_tables rounded to fp32 once, as the tensors sidlsg_solver_step takes:
     -> (timesteps Long[N], s0 f32[N], s1 f32[N], coef f32[N, 4]) on the scheduler's device, s0 / s1 being alpha / sigma at t_i."""
-    t, al, sg, coef = solver_tables(scheduler, config_dict, num_inference_steps, solver=solver, spacing=spacing, eta=eta)
+    t, al, sg, coef = solver_tables(scheduler, config_dict, num_inference_steps, solver=solver, spacing=spacing, eta=eta, start=start)
     dev = scheduler.alphas_cumprod.device
     f32 = lambda v: torch.from_numpy(v).to(torch.float32).to(dev)  # noqa: E731
     return torch.from_numpy(t).to(dev), f32(al), f32(sg), f32(coef)

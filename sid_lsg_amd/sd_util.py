@@ -7,6 +7,9 @@
                                sampling of the teacher itself, one sidlsg_ddim_step launch per step boundary
     teacher_sample_solver  (no counterpart)  the same under DPM-Solver++ 2M or DDIM with any eta, 'leading' / 'trailing' / 'linspace'
                                spacing and guidance rescale, one sidlsg_solver_step launch per step boundary
+    teacher_sample_i2i / teacher_sample_solver_i2i  (no counterpart)  the two above entered in the middle of their chain from encoded
+                               init latents (image-to-image) and, with a mask, inpainting: one sidlsg_masked_renoise launch per step
+                               boundary re-imposes the kept region; sid_sd_sampler(mask=...) does the same for a distilled generator
 
 `unet` must be a HipUNet2DCondition (bare or wrapped in DistributedDataParallel, as the reference's loop passes it):
 the whole glue runs as fused HIP kernels (sidlsg_noisy_input / UNet / sidlsg_cfg_x0: no per-sample python loop, no
@@ -338,10 +341,13 @@ def hip_denoise(unet, prep, guidance_scale, predict_x0):
 # ------------------------------------------------------------------------------------------------
 def sid_sd_sampler(unet, latents, contexts, init_timesteps, noise_scheduler, text_encoder, tokenizer, resolution,
                    dtype=torch.float16, return_images=False, vae=None, guidance_scale=1, num_steps=1, train_sampler=True,
-                   num_steps_eval=1, init_latents=None, start_step=0):
+                   num_steps_eval=1, init_latents=None, start_step=0, mask=None):
     """init_latents / start_step (eval mode only; image-to-image): the chain is entered at step `start_step` with D_x = init_latents
     (scaled latents [B, 4, h, w], e.g. HipAutoencoderKLEncoder.encode_latents); the first executed step takes `latents` as its noise,
-    so its input is x_{t_k} = s0 init_latents + s1 latents -- what a generator trained with --num_steps N saw at step k."""
+    so its input is x_{t_k} = s0 init_latents + s1 latents -- what a generator trained with --num_steps N saw at step k.
+    mask (eval mode only, needs init_latents; inpainting): uint8 / bool [B, h, w] or [1, h, w], nonzero = repaint.  After every
+    executed step's x0 prediction D_x <- mask ? D_x : init_latents (one sidlsg_masked_renoise launch, a select); the next step noises
+    the kept region to its level with its own noise."""
     steps = num_steps if train_sampler else num_steps_eval
     if init_latents is None:
         if start_step != 0:
@@ -352,6 +358,10 @@ def sid_sd_sampler(unet, latents, contexts, init_timesteps, noise_scheduler, tex
         raise ValueError(f'sid_sd_sampler: start_step {start_step} outside [0, {steps})')
     elif init_latents.shape != latents.shape:
         raise ValueError(f'sid_sd_sampler: init_latents {tuple(init_latents.shape)} vs latents {tuple(latents.shape)}')
+    if mask is not None:
+        if train_sampler:
+            raise ValueError('sid_sd_sampler: mask is for the evaluation sampler (train_sampler=False)')
+        mask = check_mask(mask, init_latents, latents, 'sid_sd_sampler')
     _require_hip(unet)
     check_prediction_type(unet, noise_scheduler)
     emb = encode_contexts(contexts, text_encoder, tokenizer, latents.device).to(_unwrap(unet).compute_dtype).contiguous()
@@ -365,11 +375,13 @@ def sid_sd_sampler(unet, latents, contexts, init_timesteps, noise_scheduler, tex
                                      noise_scheduler)
         else:
             if init_latents is not None:
-                D_x = init_latents.to(torch.float32).contiguous()
+                D_x = z0 = init_latents.to(torch.float32).contiguous()
             for i in range(start_step, steps):
                 noise = latents if i == start_step else torch.randn_like(latents)
                 t_i = (init_timesteps * (1 - i / steps)).to(torch.long)
                 D_x = hip_generate(unet, noise.to(torch.float32).contiguous(), emb, t_i.contiguous(), noise_scheduler, x0=D_x)
+                if mask is not None:
+                    D_x = ops.masked_renoise(D_x, z0, mask, want_input=False, inplace=True)[1]
     if not return_images:
         return D_x.to(torch.float32)
     upcast = vae.dtype == torch.float16 and getattr(vae.config, 'force_upcast', False)
@@ -396,6 +408,50 @@ def sid_sd_denoise(unet, images, noise, contexts, timesteps, noise_scheduler, te
     return hip_denoise(unet, prep, float(guidance_scale), predict_x0)
 
 
+def teacher_start_index(num_inference_steps, strength):
+    """Image-to-image entry of an N-step teacher sampler at `strength` S: run = min(int(N*S), N) steps are executed, the steps
+    k .. N-1 with k = N - run -- a restatement of diffusers' StableDiffusionImg2ImgPipeline.get_timesteps, N*S formed in floating
+    point as there (int(10*0.3) == 3, int(100*0.29) == 28).  -> k; fewer than one executed step is a ValueError."""
+    n = int(num_inference_steps)
+    if n < 1:
+        raise ValueError(f'num_inference_steps={n}: expected at least 1')
+    run = min(int(n * strength), n)
+    if run < 1:
+        raise ValueError(f'strength={strength}: int({n}*{strength}) = {run} of the {n} steps would run; expected at least 1')
+    return n - run
+
+
+def check_mask(mask, init_latents, latents, who):
+    """An inpainting mask (uint8 / bool [B, h, w] or [1, h, w], nonzero = repaint) for latents [B, C, h, w] -> contiguous, on their
+    device.  A mask needs init_latents: they are the known region."""
+    if init_latents is None:
+        raise ValueError(f'{who}: mask without init_latents (they are the region that is kept)')
+    b, _, h, w = latents.shape
+    if not torch.is_tensor(mask) or mask.dtype not in (torch.uint8, torch.bool) or mask.dim() != 3 or mask.shape[0] not in (1, b) \
+            or tuple(mask.shape[1:]) != (h, w):
+        got = f'{tuple(mask.shape)} {mask.dtype}' if torch.is_tensor(mask) else type(mask).__name__
+        raise ValueError(f'{who}: mask {got}: expected uint8 or bool [{b} or 1, {h}, {w}]')
+    return mask.to(latents.device).contiguous()
+
+
+def _teacher_entry(latents, init_latents, start_index, mask, n, who):
+    """The image-to-image / inpainting arguments of the teacher samplers, checked -> (z0 fp32 or None, mask or None, noised start?).
+    The start state is alpha_k*z0 + sigma_k*z, except with a mask at k = 0 (diffusers' is_strength_max): pure noise, as without init."""
+    if init_latents is None:
+        if start_index != 0:
+            raise ValueError(f'{who}: start_index without init_latents')
+        if mask is not None:
+            check_mask(mask, init_latents, latents, who)
+        return None, None, False
+    if not 0 <= start_index < n:
+        raise ValueError(f'{who}: start_index {start_index} outside [0, {n})')
+    if init_latents.shape != latents.shape:
+        raise ValueError(f'{who}: init_latents {tuple(init_latents.shape)} vs latents {tuple(latents.shape)}')
+    if mask is not None:
+        mask = check_mask(mask, init_latents, latents, who)
+    return init_latents.to(torch.float32).contiguous(), mask, not (mask is not None and start_index == 0)
+
+
 def sampling_config_of(noise_scheduler, schedule_config=None):
     """The DDIM sampling keys teacher_sample uses: `schedule_config` when given, else what resolve_scheduler attached to the scheduler
     (an EMPTY dict there means a scheduler_config.json without these keys, i.e. diffusers' defaults), else the SD values."""
@@ -407,6 +463,14 @@ def sampling_config_of(noise_scheduler, schedule_config=None):
 
 def teacher_sample(unet, latents, contexts, noise_scheduler, text_encoder, tokenizer, resolution, guidance_scale=TEACHER_CFG,
                    num_inference_steps=TEACHER_STEPS, return_images=False, vae=None, schedule_config=None):
+    """teacher_sample_i2i from pure noise: the text-to-image teacher row, under the signature it has always had."""
+    return teacher_sample_i2i(unet, latents, contexts, noise_scheduler, text_encoder, tokenizer, resolution, guidance_scale=guidance_scale,
+                              num_inference_steps=num_inference_steps, return_images=return_images, vae=vae, schedule_config=schedule_config)
+
+
+def teacher_sample_i2i(unet, latents, contexts, noise_scheduler, text_encoder, tokenizer, resolution, guidance_scale=TEACHER_CFG,
+                       num_inference_steps=TEACHER_STEPS, return_images=False, vae=None, schedule_config=None, init_latents=None,
+                       start_index=0, mask=None):
     """The teacher itself, sampled the way every SiD-LSG table samples it: classifier-free guidance and an N-step deterministic DDIM
     sampler (Song et al. 2021, eta = 0; diffusers' DDIMScheduler with 'leading' spacing).  x_T = latents (DDIM's init_noise_sigma is
     1); per step one UNet pass on the stacked [uncond ; cond] batch (unconditional prompt '', as sid_sd_denoise) and one
@@ -415,6 +479,12 @@ def teacher_sample(unet, latents, contexts, noise_scheduler, text_encoder, token
     (scheduler.ddim_schedule); None = what resolve_scheduler found for the model, else the SD values (sampling_config_of).
     `resolution` is accepted for the signature of the other samplers and not used: the size is the latents'.  The scheduler is not
     moved: the N-entry tables are built where it lives and copied to the latents' device before the loop.
+    init_latents / start_index (image-to-image): scaled latents z0 [B, 4, h, w]; the chain is entered at step k = start_index
+    (teacher_start_index) from x_{t_k} = alpha_k*z0 + sigma_k*latents, one noisy_input launch, and steps k .. N-1 run.
+    mask (inpainting, needs init_latents): uint8 / bool [B, h, w] or [1, h, w], nonzero = repaint.  After every step one
+    sidlsg_masked_renoise launch re-imposes the known region at the step's target level, x <- mask ? x : s0p_i*z0 + s1p_i*latents
+    (after the last step: z0 itself), and writes the next network input; with a mask and k = 0 the start is pure noise (diffusers'
+    is_strength_max).  These rules restate diffusers' img2img / inpainting pipelines; agreement with the package is not pinned by a test.
     -> the final latent x_0 fp32 NCHW, or (return_images) the decoded images as sid_sd_sampler returns them."""
     _require_hip(unet)
     check_prediction_type(unet, noise_scheduler)
@@ -426,6 +496,7 @@ def teacher_sample(unet, latents, contexts, noise_scheduler, text_encoder, token
         b, dev = z.shape[0], z.device
         ts, s0, s1, s0p, s1p = (v.to(dev) for v in ddim_schedule(noise_scheduler, schedule_config, num_inference_steps))
         n = ts.numel()
+        z0, mask, noised = _teacher_entry(z, init_latents, start_index, mask, n, 'teacher_sample_i2i')
         guided = guidance_scale != 1
         dup = 2 if guided else 1
         ctx = encode_contexts(contexts, text_encoder, tokenizer, dev).to(dt)
@@ -435,10 +506,19 @@ def teacher_sample(unet, latents, contexts, noise_scheduler, text_encoder, token
         tt = ts[:, None].expand(n, dup * b).contiguous()
         s0, s1, s0p, s1p = (v.to(torch.float32)[:, None].expand(n, b).contiguous() for v in (s0, s1, s0p, s1p))
         ones = torch.ones(b, device=dev, dtype=torch.float32)
-        xin, xt = ops.noisy_input(None, z, ones, ones, dup, dt)          # x_T = z, as the [uncond ; cond] NHWC batch
-        for i in range(n):
+        if noised:
+            xin, xt = ops.noisy_input(z0, z, s0[start_index], s1[start_index], dup, dt)      # x_{t_k} = alpha_k z0 + sigma_k z
+        else:
+            xin, xt = ops.noisy_input(None, z, ones, ones, dup, dt)      # x_T = z, as the [uncond ; cond] NHWC batch
+        for i in range(start_index, n):
             eps = net.forward_nhwc(xin, tt[i], ctx)
-            xin, xt, _ = ops.ddim_step(eps, xt, s0[i], s1[i], s0p[i], s1p[i], guidance_scale, dt, prediction_type=pt, last=i == n - 1)
+            last = i == n - 1
+            xin, xt, _ = ops.ddim_step(eps, xt, s0[i], s1[i], s0p[i], s1p[i], guidance_scale, dt, prediction_type=pt,
+                                       last=last or mask is not None)
+            if mask is not None and last:
+                xt = ops.masked_renoise(xt, z0, mask, want_input=False, inplace=True)[1]
+            elif mask is not None:
+                xin, xt = ops.masked_renoise(xt, z0, mask, noise=z, a0=s0p[i], a1=s1p[i], dup=dup, act_dtype=dt, inplace=True)
         if not return_images:
             return xt
         upcast = vae.dtype == torch.float16 and getattr(vae.config, 'force_upcast', False)
@@ -453,6 +533,17 @@ def teacher_sample(unet, latents, contexts, noise_scheduler, text_encoder, token
 def teacher_sample_solver(unet, latents, contexts, noise_scheduler, text_encoder, tokenizer, resolution, guidance_scale=TEACHER_CFG,
                           num_inference_steps=TEACHER_STEPS, return_images=False, vae=None, schedule_config=None, solver='dpmpp2m',
                           spacing=None, eta=0.0, guidance_rescale=0.0, negative_contexts=None, randn=None):
+    """teacher_sample_solver_i2i from pure noise: the text-to-image solver rows, under the signature they have always had."""
+    return teacher_sample_solver_i2i(unet, latents, contexts, noise_scheduler, text_encoder, tokenizer, resolution,
+                                     guidance_scale=guidance_scale, num_inference_steps=num_inference_steps, return_images=return_images,
+                                     vae=vae, schedule_config=schedule_config, solver=solver, spacing=spacing, eta=eta,
+                                     guidance_rescale=guidance_rescale, negative_contexts=negative_contexts, randn=randn)
+
+
+def teacher_sample_solver_i2i(unet, latents, contexts, noise_scheduler, text_encoder, tokenizer, resolution, guidance_scale=TEACHER_CFG,
+                              num_inference_steps=TEACHER_STEPS, return_images=False, vae=None, schedule_config=None, solver='dpmpp2m',
+                              spacing=None, eta=0.0, guidance_rescale=0.0, negative_contexts=None, randn=None, init_latents=None,
+                              start_index=0, mask=None):
     """The teacher under the solvers it is usually run with: `solver` 'dpmpp2m' (DPM-Solver++ 2M) or 'ddim' (any `eta` >= 0), timestep
     `spacing` 'leading' / 'trailing' / 'linspace' (None: the model's timestep_spacing), guidance rescale `guidance_rescale` (phi of
     Lin et al. 2024; 0 = plain classifier-free guidance) and `negative_contexts` in place of '' in the unconditional half.  The
@@ -461,6 +552,9 @@ def teacher_sample_solver(unet, latents, contexts, noise_scheduler, text_encoder
     sidlsg_cfg_rescale_stats launch before it), tables as device tensors indexed by the step number, the two x0 history buffers
     swapped per step: nothing waits for the device between the first UNet pass and the result.  `randn(shape) -> fp32 tensor` supplies
     xi once per step whose c_n is non-zero, in step order (default: torch.randn on the latents' device).
+    init_latents / start_index / mask: image-to-image and inpainting as in teacher_sample.  The tables are solver_schedule's with
+    start = start_index (DPM-Solver++ 2M takes its first executed step at first order); the masked boundary of step i noises the known
+    region to the level of t_{i+1}, known = s0[i+1]*z0 + s1[i+1]*latents (after the last step: z0), and leaves the x0 history alone.
     -> the final latent x_0 fp32 NCHW, or (return_images) the decoded images as sid_sd_sampler returns them."""
     _require_hip(unet)
     check_prediction_type(unet, noise_scheduler)
@@ -473,7 +567,9 @@ def teacher_sample_solver(unet, latents, contexts, noise_scheduler, text_encoder
     with torch.no_grad():
         z = latents.to(torch.float32).contiguous()
         b, dev = z.shape[0], z.device
-        ts, s0, s1, coef = solver_schedule(noise_scheduler, schedule_config, num_inference_steps, solver=solver, spacing=spacing, eta=eta)
+        z0, mask, noised = _teacher_entry(z, init_latents, start_index, mask, int(num_inference_steps), 'teacher_sample_solver_i2i')
+        ts, s0, s1, coef = solver_schedule(noise_scheduler, schedule_config, num_inference_steps, solver=solver, spacing=spacing, eta=eta,
+                                           start=start_index)
         flags = (coef.cpu() != 0).tolist()          # per step: which terms exist (read before the loop; the loop itself reads nothing back)
         ts, s0, s1, coef = (v.to(dev) for v in (ts, s0, s1, coef))
         n = ts.numel()
@@ -492,16 +588,24 @@ def teacher_sample_solver(unet, latents, contexts, noise_scheduler, text_encoder
         s0, s1 = (v[:, None].expand(n, b).contiguous() for v in (s0, s1))
         coef = coef[:, None, :].expand(n, b, 4).contiguous()
         ones = torch.ones(b, device=dev, dtype=torch.float32)
-        xin, xt = ops.noisy_input(None, z, ones, ones, dup, dt)          # x_T = z, as the [uncond ; cond] NHWC batch
+        if noised:
+            xin, xt = ops.noisy_input(z0, z, s0[start_index], s1[start_index], dup, dt)      # x_{t_k} = alpha_k z0 + sigma_k z
+        else:
+            xin, xt = ops.noisy_input(None, z, ones, ones, dup, dt)      # x_T = z, as the [uncond ; cond] NHWC batch
         history = [torch.empty_like(z), torch.empty_like(z)]
         x0_prev = None
-        for i in range(n):
+        for i in range(start_index, n):
             eps = net.forward_nhwc(xin, tt[i], ctx)
             scale = ops.cfg_rescale_stats(eps, z.shape[1], guidance_scale, phi) if guided and phi != 0 else None
             noise = randn(tuple(z.shape)).to(device=dev, dtype=torch.float32).contiguous() if flags[i][3] else None
+            last = i == n - 1
             xin, xt, x0_prev = ops.solver_step(eps, xt, s0[i], s1[i], coef[i], guidance_scale, dt, prediction_type=pt,
-                                               x0p=x0_prev if flags[i][2] else None, noise=noise, scale=scale, last=i == n - 1,
-                                               x0_out=history[i & 1], need_prev=flags[i][2])
+                                               x0p=x0_prev if flags[i][2] else None, noise=noise, scale=scale,
+                                               last=last or mask is not None, x0_out=history[i & 1], need_prev=flags[i][2])
+            if mask is not None and last:
+                xt = ops.masked_renoise(xt, z0, mask, want_input=False, inplace=True)[1]
+            elif mask is not None:
+                xin, xt = ops.masked_renoise(xt, z0, mask, noise=z, a0=s0[i + 1], a1=s1[i + 1], dup=dup, act_dtype=dt, inplace=True)
         if not return_images:
             return xt
         upcast = vae.dtype == torch.float16 and getattr(vae.config, 'force_upcast', False)

@@ -12,7 +12,13 @@ the solver family of sd_util.teacher_sample_solver instead, measured the same tw
 (c) sidlsg_solver_step on a second-order DPM-Solver++ 2M row, alone and behind a sidlsg_cfg_rescale_stats launch, against
     sidlsg_ddim_step and against a chain of torch operations with the same arithmetic (guided combine, x0, three-term update, NHWC
     input of both halves), the four variants alternating;
-(d) images/s of teacher_sample_solver with 'dpmpp2m' at 20 steps against teacher_sample ('ddim') at 50, both without the VAE decode."""
+(d) images/s of teacher_sample_solver with 'dpmpp2m' at 20 steps against teacher_sample ('ddim') at 50, both without the VAE decode.
+    python tools/teacher_sampler_cost.py --masked
+the masked step boundary of inpainting (sd_util.teacher_sample_solver_i2i with a mask):
+(e) sidlsg_masked_renoise as the one new launch against the chain of existing launches that does the same job (noisy_input for the
+    known region, torch.where, noisy_input for the next input), measured as (a), the two variants alternating;
+(f) images/s of 'dpmpp2m' at 20 steps with and without a mask (image-to-image at start_index 0, half of the latent repainted),
+    without the VAE decode."""
 import argparse
 import os
 import statistics
@@ -24,10 +30,11 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from sid_lsg_amd import ops  # noqa: E402
 from sid_lsg_amd.scheduler import DDPMScheduler  # noqa: E402
-from sid_lsg_amd.sd_util import load_sd15, teacher_sample, teacher_sample_solver  # noqa: E402
+from sid_lsg_amd.sd_util import load_sd15, teacher_sample, teacher_sample_solver, teacher_sample_solver_i2i  # noqa: E402
 
 args = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
 args.add_argument('--solver', action='store_true', help='measure sidlsg_solver_step and teacher_sample_solver (sections c and d) instead of a and b')
+args.add_argument('--masked', action='store_true', help='measure sidlsg_masked_renoise and the masked dpmpp2m sampler (sections e and f) instead')
 args = args.parse_args()
 dev = torch.device('cuda:0')
 BF16 = torch.bfloat16
@@ -130,8 +137,53 @@ def solver_sections():
               f'({med:.2f} s per batch, median of 3 after one warm-up call; {min(times):.2f} .. {max(times):.2f} s)', flush=True)
 
 
+def masked_sections():
+    z0 = torch.randn(B, 4, lat, lat, generator=g).to(dev)
+    z = torch.randn(B, 4, lat, lat, generator=g).to(dev)
+    mask = torch.zeros(B, lat, lat, dtype=torch.uint8, device=dev)
+    mask[:, :, lat // 2:] = 1
+    m4 = mask.bool()[:, None]
+    ones = torch.ones(B, device=dev)
+
+    def fused_mask():
+        return ops.masked_renoise(xt, z0, mask, noise=z, a0=s0p, a1=s1p, dup=2, act_dtype=BF16)
+
+    def chain_mask():
+        xn = torch.where(m4, xt, ops.noisy_input(z0, z, s0p, s1p, 1, BF16)[1])
+        return ops.noisy_input(None, xn, ones, ones, 2, BF16)[0], xn
+    with torch.no_grad():
+        a, b = fused_mask(), chain_mask()
+        torch.cuda.synchronize()
+        print(f'(e) the two variants agree bit for bit: {torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])}', flush=True)
+    alternate((('masked_renoise (1 launch)', fused_mask), ('noisy_input + torch.where + noisy_input (3 launches)', chain_mask)), 'e')
+    print(f'    masked_renoise reads and writes {(4 * xt.numel() * 4 + mask.numel() + 2 * B * lat * lat * 8 * 2) / 1e6:.2f} MB per launch', flush=True)
+    res = 512
+    unet, vae, sched, te, tok = load_sd15('random:sd15', None, dev, BF16)
+    unet.eval().requires_grad_(False)
+    prompts = [f'a photo of object number {i} on a table, studio light' for i in range(B)]
+    kw = dict(guidance_scale=kappa, num_inference_steps=20, solver='dpmpp2m', init_latents=z0, start_index=0)
+    runs = (('teacher_sample_solver_i2i, dpmpp2m, no mask', lambda: teacher_sample_solver_i2i(unet, z, prompts, sched, te, tok, res, **kw)),
+            ('teacher_sample_solver_i2i, dpmpp2m, half mask', lambda: teacher_sample_solver_i2i(unet, z, prompts, sched, te, tok, res, mask=mask, **kw)))
+    times = {name: [] for name, _ in runs}
+    for rep in range(4):                    # the two runs alternate; the first round is the warm-up
+        for name, fn in runs:
+            torch.cuda.synchronize()
+            t0 = time.time()
+            fn()
+            torch.cuda.synchronize()
+            if rep:
+                times[name].append(time.time() - t0)
+    for name, v in times.items():
+        med = statistics.median(v)
+        print(f'(f) {name}, random:sd15, {res} x {res}, batch {B}, 20 steps, kappa {kappa}, without VAE decode: {B / med:.2f} images/s '
+              f'({med:.3f} s per batch, median of 3 alternating calls after one warm-up call each; {min(v):.3f} .. {max(v):.3f} s)', flush=True)
+
+
 if args.solver:
     solver_sections()
+    sys.exit(0)
+if args.masked:
+    masked_sections()
     sys.exit(0)
 
 moved = eps.numel() * 4 + 2 * xt.numel() * 4 + 2 * B * lat * lat * 8 * 2
