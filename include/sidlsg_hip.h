@@ -223,6 +223,16 @@ int sidlsg_attn_bwd_ps(const void* Q, const void* K, const void* V, const void* 
                        void* dK, void* dV, float* delta, int B, int H, int Nq, int Nk, int D, int ldq, int ldk, int ldv, int ldo,
                        long long bsq, long long bsk, long long bsv, long long bso, void* stream);
 
+/* Fused backward of the d = 40 self-attention (attn_bwd_fused_kernel: S, dP and the exponentials once for dQ, dK and dV; the key
+ * groups' partial dQ go to fp32 slabs in the stream's workspace and are added in a fixed order, so the result is bit-reproducible).
+ * Taken inside sidlsg_attn_bwd / _ps when 32 < D <= 48, dK and dV are requested, Nq == Nk is a multiple of 512 and at least the
+ * rule's threshold, and one batch element's slabs (H * Nk / 512 * Nq * D * 4 bytes) fit the workspace; every other call keeps the
+ * two-kernel path.  A/B switch: environment variable SIDLSG_ATTN_BWD_FUSED (read once) or sidlsg_debug_set_attn_bwd_fused: 0 never,
+ * 1 by rule, 2 every call the kernel can run (no length threshold); a negative argument only queries; returns the previous setting.
+ * sidlsg_attn_bwd_fused_takes: 1 when a call of that shape (default-stream workspace) takes the fused kernel under the current setting. */
+int sidlsg_debug_set_attn_bwd_fused(int mode);
+int sidlsg_attn_bwd_fused_takes(int B, int H, int Nq, int Nk, int D, int have_dkdv);
+
 /* ---- scheduler / guidance glue (sid_sd_util.py:182-185, 242, 259-272) ----------------------
  * noisy_input: x_t = s0[b]*x0 + s1[b]*noise (x0 NULL -> zeros: the one-step generator input),
  *   NCHW fp32 in, NHWC bf16 [dup*B][HW][Cp] out (dup=2: [uncond ; cond] halves of the CFG batch),

@@ -23,6 +23,8 @@
 //                    rowsum(dO*O) from its fragments in the prologue and publishes it for the second kernel
 //   attn_dkdv      : per key block, over query tiles, in the non-transposed orientation S[query][key] so that P / dS
 //                    are B operands of the contractions over queries.
+// The 4096-token d = 40 self-attention takes ONE sweep instead (attn_bwd_fused_kernel, below: S, dP and the exponentials once for
+// dQ, dK and dV; per-key-group partial dQ in fp32 slabs, added in a fixed order by attn_dq_reduce_kernel).
 #include "common.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -39,6 +41,8 @@ struct AttnParams {
     float scale2;                  // d^-0.5 * log2(e)
     float scale;                   // d^-0.5
     int xcd;                       // 1: blocks renumbered so that all blocks of one (batch, head) run on ONE XCD (attn_block_coords)
+    float* slab;                   // fused backward: the key groups' partial dQ, fp32 [B][H][G][Nq][D] (attn_bwd_fused_kernel -> attn_dq_reduce_kernel)
+    int G;                         // fused backward: key groups per (batch, head) = Nk / AF_KEYS
     int rot;                       // 1: every block starts its walk over the streamed tiles (keys: forward / dQ; queries: dK/dV) at its own
                                    //    offset and wraps around, so the co-resident blocks of a head do not read the same tile at the same time
 };
@@ -775,6 +779,264 @@ __global__ __launch_bounds__(256) void attn_dkdv_kernel(AttnParams p) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Fused backward for DP = 48 (d = 40): S, dP and one exp2 per score are computed ONCE and feed dV, dK and dQ.
+// One workgroup (8 waves) owns a group of AF_KEYS = 512 keys of one (batch, head); wave w owns keys w*64 .. w*64+63 and keeps
+// their dK^T / dV^T in 96 accumulator registers while the group sweeps the queries in slices of AF_QS = 32, exactly as
+// attn_dkdv_kernel does (key on the lane, -LSE / -delta as the initial accumulators for PS).  dS crosses LDS once, as bf16, in
+// the transposed image dsT[key][query]: every lane writes its 4 consecutive queries with one 8-byte store, and both operands
+// of the group's partial dQ^T[d][q] = sum_key K^T[d][key] dS^T[key][q] are transpose reads (tr_frag32) of row-major images
+// (the group's K rows stay in LDS for the whole sweep) with the same key order inside a K = 32 step.  The 3 x 2 output tiles
+// of a slice go to six of the eight waves (the idle pair alternates with the slice parity so that every SIMD gets 1.5 tiles per
+// slice on average) and from there, with plain 16-byte stores, to the group's own fp32 slab [B][H][G][Nq][D]: one writer per
+// element, one time -- no atomics, no flags, no wait on another workgroup.  attn_dq_reduce_kernel adds the G slabs in index
+// order.  One barrier per slice: it publishes the slice's dS^T (double buffered) together with the next Q / dO tile.
+constexpr int AF_KEYS = 512;   // keys per workgroup
+constexpr int AF_QS = 32;      // queries per slice
+constexpr int AF_LDT = 40;     // row stride (elements) of the dS^T image: 32 queries + 8 (80-byte rows, 8-byte aligned pieces)
+template <int DP>
+constexpr int attn_fused_lds_bytes() {
+    return (lds_tile_elems<DP, AF_KEYS>() + 2 * AF_KEYS * AF_LDT + 4 * lds_tile_elems<DP, AF_QS>()) * 2 + 4 * AF_QS * 4;
+}
+template <int DP, bool PS>
+__global__ __launch_bounds__(512) void attn_bwd_fused_kernel(AttnParams p) {
+    static_assert(DP == 48, "sized for d = 40");
+    constexpr int LD = tile_ld<DP>();
+    constexpr int DT = DP / 16, KT = 4, QS = AF_QS, LDT = AF_LDT;
+    constexpr int TE = lds_tile_elems<DP, QS>();
+    constexpr int KE = lds_tile_elems<DP, AF_KEYS>();
+    extern __shared__ __attribute__((aligned(16))) unsigned char af_smem[];
+    bf16* Ks = reinterpret_cast<bf16*>(af_smem);            // [AF_KEYS][LD] (+ slack)
+    bf16* dsT = Ks + KE;                                     // [2][AF_KEYS][LDT]
+    bf16* Qs2 = dsT + 2 * AF_KEYS * LDT;                     // [2][TE]
+    bf16* dOs2 = Qs2 + 2 * TE;                               // [2][TE]
+    float* lse_s = reinterpret_cast<float*>(dOs2 + 2 * TE);  // [2][QS]
+    float* dl_s = lse_s + 2 * QS;                            // [2][QS]
+#pragma unroll
+    for (int i = 0; i < 2; i++) { lds_tile_init<DP, QS>(Qs2 + i * TE); lds_tile_init<DP, QS>(dOs2 + i * TE); }
+    lds_tile_init<DP, AF_KEYS>(Ks);
+    int bx_, h_, b_;
+    attn_block_coords(p, bx_, h_, b_);
+    const int b = b_, h = h_, g = bx_;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), li = lane & 15, lg = lane >> 4;
+    const int gkey0 = g * AF_KEYS, key0 = gkey0 + wave * (KT * 16);
+    const bf16* Kb = p.K + b * p.bsk + (long long)h * p.D;
+    const bf16* Vb = p.V + b * p.bsv + (long long)h * p.D;
+    // the group's K rows -> LDS (pad columns D .. LD: zeros), published by the barrier in front of the sweep
+    for (int i = threadIdx.x; i < AF_KEYS * (LD / 8); i += 512) {
+        const int r = i / (LD / 8), c = (i - r * (LD / 8)) * 8;
+        st8(Ks + r * LD + c, c < p.D ? ld8(Kb + (long long)(gkey0 + r) * p.ldk + c) : zero8());
+    }
+    const __amdgpu_buffer_rsrc_t rq = mk_rsrc_rows(p.Q + b * p.bsq + (long long)h * p.D, p.Nq, p.ldq, p.D);
+    const __amdgpu_buffer_rsrc_t rdo = mk_rsrc_rows(p.dO + b * p.bso + (long long)h * p.D, p.Nq, p.ldo, p.D);
+    const float* LSEb = p.LSE + ((long long)b * p.H + h) * p.Nq;
+    const float* DLb = p.delta + ((long long)b * p.H + h) * p.Nq;
+    float* slab = p.slab + (((long long)b * p.H + h) * p.G + g) * (long long)p.Nq * p.D;
+    Frag<DP> fk[KT], fv[KT];  // B operands: (k = d, col = key)
+#pragma unroll
+    for (int kt = 0; kt < KT; kt++) {
+        const int key = key0 + kt * 16 + li;      // < Nk: the launcher takes whole groups only
+        frag_from_global<DP>(fk[kt], Kb + (long long)key * p.ldk, lg, p.D, true);
+        frag_from_global<DP>(fv[kt], Vb + (long long)key * p.ldv, lg, p.D, true);
+    }
+    f32x4 dk[KT][DT], dv[KT][DT];
+#pragma unroll
+    for (int kt = 0; kt < KT; kt++)
+#pragma unroll
+        for (int i = 0; i < DT; i++) { dk[kt][i] = (f32x4){0, 0, 0, 0}; dv[kt][i] = (f32x4){0, 0, 0, 0}; }
+
+    Tile<DP, QS, SIDLSG_ATTN_DMA != 0> tq, tdo;
+    tq.init(p.ldq, p.D, Qs2, Qs2 + TE, -1);
+    tdo.init(p.ldo, p.D, dOs2, dOs2 + TE, -1);
+    float lse_r = 0.f, dl_r = 0.f;
+    auto prefetch = [&](int q0, int into) {
+        tq.load(rq, p.ldq, q0, Qs2 + into * TE);
+        tdo.load(rdo, p.ldo, q0, dOs2 + into * TE);
+        if (threadIdx.x < QS) {
+            lse_r = LSEb[q0 + threadIdx.x];       // Nq is a whole number of slices (launcher)
+            dl_r = DLb[q0 + threadIdx.x];
+            if (PS) { lse_r = -lse_r; dl_r = -dl_r; }
+        }
+    };
+    // rotated walk over the query slices (see attn_q_kernel): every output is a sum over queries or belongs to one slice
+    const int nsl = p.Nq / QS;
+    const bool rotate = p.rot && nsl >= 2;
+    const int qbase = rotate ? (int)(((long long)bx_ * nsl) / gridDim.x) * QS : 0;
+    prefetch(qbase, 0);
+    tq.commit(Qs2, LD); tdo.commit(dOs2, LD);
+    if (threadIdx.x < QS) { lse_s[threadIdx.x] = lse_r; dl_s[threadIdx.x] = dl_r; }
+    __syncthreads();
+    int pb_ = 0;
+    for (int sl = 0; sl < nsl; sl++) {
+        int qcur = sl * QS + qbase;
+        if (qcur >= p.Nq) qcur -= p.Nq;
+        const bool more = sl + 1 < nsl;
+        if (more) { int qn = qcur + QS; if (qn >= p.Nq) qn -= p.Nq; prefetch(qn, pb_ ^ 1); }
+        const bf16* Qs = Qs2 + pb_ * TE;
+        const bf16* dOs = dOs2 + pb_ * TE;
+        const float* lse_c = lse_s + pb_ * QS;
+        const float* dl_c = dl_s + pb_ * QS;
+        bf16* dsc = dsT + (sl & 1) * (AF_KEYS * LDT);
+        bf16x4 ph[KT][2], dh[KT][2];       // P and dS of (key tile, 16-query tile), rounded: halves of the K = 32 B operands
+#pragma unroll
+        for (int qt = 0; qt < 2; qt++) {
+            Frag<DP> fq, fdo;  // A operands: (row = query, k = d)
+            frag_from_lds<DP>(fq, Qs + (qt * 16 + li) * LD, lg);
+            frag_from_lds<DP>(fdo, dOs + (qt * 16 + li) * LD, lg);
+            // all S and dP chains of the 16-query tile first (slice-major: the two MFMAs of one accumulator are KT instructions apart),
+            // then the exponentials: with two waves per SIMD a chain that feeds its own v_exp_f32 at once leaves the MFMA latency bare
+            f32x4 sa[KT], dpa[KT];
+            {
+                f32x4 nl = {0, 0, 0, 0}, nd = {0, 0, 0, 0};
+                if constexpr (PS) {     // S[q][key] - LSE[q] and dP - delta: lane col = key li, rows q = lg*4+r
+                    nl = *reinterpret_cast<const f32x4*>(&lse_c[qt * 16 + lg * 4]);
+                    nd = *reinterpret_cast<const f32x4*>(&dl_c[qt * 16 + lg * 4]);
+                }
+#pragma unroll
+                for (int s2 = 0; s2 < Frag<DP>::N32; s2++)
+#pragma unroll
+                    for (int kt = 0; kt < KT; kt++)
+                        sa[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fq.w[s2], fk[kt].w[s2], s2 == 0 ? nl : sa[kt], 0, 0, 0);
+#pragma unroll
+                for (int s2 = 0; s2 < Frag<DP>::N32; s2++)
+#pragma unroll
+                    for (int kt = 0; kt < KT; kt++)
+                        dpa[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fdo.w[s2], fv[kt].w[s2], s2 == 0 ? nd : dpa[kt], 0, 0, 0);
+            }
+#pragma unroll
+            for (int kt = 0; kt < KT; kt++) {
+                f32x4 pr, dsv;
+                const f32x4 s = sa[kt], dp = dpa[kt];
+                if constexpr (PS) {
+#pragma unroll
+                    for (int r = 0; r < 4; r++) { pr[r] = __builtin_amdgcn_exp2f(s[r]); dsv[r] = pr[r] * dp[r]; }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 4; r++) {
+                        const int ql = qt * 16 + lg * 4 + r;
+                        pr[r] = __builtin_amdgcn_exp2f(fmaf(s[r], p.scale2, -lse_c[ql]));
+                        dsv[r] = pr[r] * (dp[r] - dl_c[ql]);
+                    }
+                }
+                ph[kt][qt] = (bf16x4){f2bf(pr[0]), f2bf(pr[1]), f2bf(pr[2]), f2bf(pr[3])};
+                dh[kt][qt] = (bf16x4){f2bf(dsv[0]), f2bf(dsv[1]), f2bf(dsv[2]), f2bf(dsv[3])};
+                // dS^T image: row = this lane's key, columns = its 4 queries
+                *reinterpret_cast<bf16x4*>(dsc + (wave * (KT * 16) + kt * 16 + li) * LDT + qt * 16 + lg * 4) = dh[kt][qt];
+            }
+        }
+#pragma unroll
+        for (int dt = 0; dt < DT; dt++) {
+            const bf16x8 fa = tr_frag32(dOs, LD, 0, dt * 16, li, lg);   // dO^T (rows d, k = queries)
+            const bf16x8 fb = tr_frag32(Qs, LD, 0, dt * 16, li, lg);    // Q^T
+#pragma unroll
+            for (int kt = 0; kt < KT; kt++) {
+                const bf16x8 pbv = __builtin_shufflevector(ph[kt][0], ph[kt][1], 0, 1, 2, 3, 4, 5, 6, 7);
+                const bf16x8 dsb = __builtin_shufflevector(dh[kt][0], dh[kt][1], 0, 1, 2, 3, 4, 5, 6, 7);
+                dv[kt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, pbv, dv[kt][dt], 0, 0, 0);
+                dk[kt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb, dsb, dk[kt][dt], 0, 0, 0);
+            }
+        }
+        if (more) {          // the other buffers were last read in the previous slice, i.e. before the previous barrier
+            pb_ ^= 1;
+            tq.commit(Qs2 + pb_ * TE, LD); tdo.commit(dOs2 + pb_ * TE, LD);
+            if (threadIdx.x < QS) { lse_s[pb_ * QS + threadIdx.x] = lse_r; dl_s[pb_ * QS + threadIdx.x] = dl_r; }
+        }
+        __syncthreads();     // dS^T of this slice (and the next Q / dO tile) are complete
+        // the group's partial dQ^T tile (rows d = dt*16 .. +15, columns = 16 queries) of this wave: a chain over the 16 K = 32 steps
+        // of the group's keys, on two accumulators added at the end (fixed order).  The next write to this dS^T buffer is two
+        // slices ahead, behind the next barrier.
+        const int t = (wave - 2 * (sl & 1)) & 7;
+        if (t < 2 * DT) {
+            const int qt = t / DT, dt = t - qt * DT;
+            f32x4 a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0};
+            // fragments of AF_DQB K = 32 steps at a time, all read before their MFMAs (the scheduler, left alone, puts a read and a wait in
+            // front of every MFMA: the LDS latency bare 16 times per tile)
+            constexpr int AF_DQB = 4;
+#pragma unroll
+            for (int kb0 = 0; kb0 < AF_KEYS / 32; kb0 += AF_DQB) {
+                bf16x8 fa[AF_DQB], fb[AF_DQB];
+#pragma unroll
+                for (int j = 0; j < AF_DQB; j++) {
+                    fa[j] = tr_frag32(Ks, LD, (kb0 + j) * 32, dt * 16, li, lg);
+                    fb[j] = tr_frag32(dsc, LDT, (kb0 + j) * 32, qt * 16, li, lg);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int j = 0; j < AF_DQB; j += 2) {
+                    a0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[j], fb[j], a0, 0, 0, 0);
+                    a1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[j + 1], fb[j + 1], a1, 0, 0, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            a0 += a1;
+            const int d = dt * 16 + lg * 4;       // lane: column = query li, rows d .. d+3
+            if (d + 4 <= p.D) *reinterpret_cast<f32x4*>(slab + (long long)(qcur + qt * 16 + li) * p.D + d) = a0;
+        }
+    }
+#pragma unroll
+    for (int kt = 0; kt < KT; kt++) {
+        const int key = key0 + kt * 16 + li;
+        bf16* dKp = p.dK + b * p.bsk + (long long)key * p.ldk + (long long)h * p.D;
+        bf16* dVp = p.dV + b * p.bsv + (long long)key * p.ldv + (long long)h * p.D;
+#pragma unroll
+        for (int dt = 0; dt < DT; dt++) {
+            const int d = dt * 16 + lg * 4;
+            if (d + 4 <= p.D) {
+                const float kf = PS ? 0.6931471805599453f : p.scale;     // as attn_dkdv_kernel
+                bf16x4 a = {f2bf(dk[kt][dt][0] * kf), f2bf(dk[kt][dt][1] * kf), f2bf(dk[kt][dt][2] * kf), f2bf(dk[kt][dt][3] * kf)};
+                bf16x4 c = {f2bf(dv[kt][dt][0]), f2bf(dv[kt][dt][1]), f2bf(dv[kt][dt][2]), f2bf(dv[kt][dt][3])};
+                *reinterpret_cast<bf16x4*>(dKp + d) = a;
+                *reinterpret_cast<bf16x4*>(dVp + d) = c;
+            }
+        }
+    }
+}
+template __global__ void attn_bwd_fused_kernel<48, false>(AttnParams);
+template __global__ void attn_bwd_fused_kernel<48, true>(AttnParams);
+
+// delta[b][h][q] = rowsum(dO * O): one thread per (batch, query, head) row, heads fastest (neighbouring threads read neighbouring
+// D-element pieces of a token).  The two-kernel path gets this from the dQ kernel's prologue.
+__global__ __launch_bounds__(256) void attn_delta_kernel(const bf16* __restrict__ O, const bf16* __restrict__ dO, float* __restrict__ delta,
+                                                         int B, int H, int Nq, int D, int ldo, long long bso) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)B * Nq * H) return;
+    const int h = (int)(i % H);
+    const long long t = i / H;
+    const int q = (int)(t % Nq), b = (int)(t / Nq);
+    const long long off = b * bso + (long long)q * ldo + (long long)h * D;
+    float sum = 0.f;
+    for (int c = 0; c < D; c += 8) {
+        const bf16x8 x = ld8(dO + off + c), y = ld8(O + off + c);
+#pragma unroll
+        for (int e = 0; e < 8; e++) sum += bf2f(x[e]) * bf2f(y[e]);
+    }
+    delta[((long long)b * H + h) * Nq + q] = sum;
+}
+// dQ[b][q][h*D + d] = alpha * (slab 0 + slab 1 + ... + slab G-1), fp32 adds in index order, one thread per 4 elements
+__global__ __launch_bounds__(256) void attn_dq_reduce_kernel(const float* __restrict__ slab, bf16* __restrict__ dQ, int B, int H, int G, int Nq,
+                                                             int D, int ldq, long long bsq, float alpha) {
+    const int C4 = D / 4;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)B * H * Nq * C4) return;
+    const int c = (int)(i % C4);
+    const long long t = i / C4;
+    const int q = (int)(t % Nq);
+    const long long bh = t / Nq;
+    const int h = (int)(bh % H), b = (int)(bh / H);
+    const long long gs = (long long)Nq * D;
+    const float* src = slab + bh * G * gs + (long long)q * D + c * 4;
+    f32x4 v = *reinterpret_cast<const f32x4*>(src);
+    int g = 1;
+    for (; g + 3 < G; g += 4) {                   // four independent loads in flight, fixed summation order
+        const f32x4 x0 = *reinterpret_cast<const f32x4*>(src + g * gs), x1 = *reinterpret_cast<const f32x4*>(src + (g + 1) * gs);
+        const f32x4 x2 = *reinterpret_cast<const f32x4*>(src + (g + 2) * gs), x3 = *reinterpret_cast<const f32x4*>(src + (g + 3) * gs);
+        v += x0; v += x1; v += x2; v += x3;
+    }
+    for (; g < G; g++) v += *reinterpret_cast<const f32x4*>(src + g * gs);
+    const bf16x4 o = {f2bf(v[0] * alpha), f2bf(v[1] * alpha), f2bf(v[2] * alpha), f2bf(v[3] * alpha)};
+    *reinterpret_cast<bf16x4*>(dQ + b * bsq + (long long)q * ldq + (long long)h * D + c * 4) = o;
+}
+
 // Explicit instantiations of every kernel specialisation the dispatcher can launch: hipcc 7.2 has left individual host stubs
 // (__device_stub__...) of implicitly instantiated kernel templates out of the object in some builds of this file (undefined
 // symbol at dlopen); a definition request pins them all.
@@ -876,6 +1138,77 @@ static int attn_fwd_impl(bool ps, const void* Q, const void* K, const void* V, v
     p.scale = 1.0f / sqrtf((float)D); p.scale2 = p.scale * 1.4426950408889634f;
     return ps ? dispatch_attn<true>(p, 0, (hipStream_t)stream) : dispatch_attn<false>(p, 0, (hipStream_t)stream);
 }
+// Which backward calls take attn_bwd_fused_kernel (A/B switch: SIDLSG_ATTN_BWD_FUSED, read once; sidlsg_debug_set_attn_bwd_fused):
+// 0 never, 1 by rule, 2 every call the kernel can run (the rule without its length threshold: the tests reach it at small N).
+// The kernel's own conditions: DP == 48, dK and dV requested, Nq == Nk (self-attention), whole key groups, and room for at least one
+// batch element's slabs [H][G][Nq][D] fp32 in the stream's workspace (the batch is walked in chunks of what fits).
+// Length threshold of the rule: the measured shape only (profiles/attn_bwd_fused_ab.txt has N = 4096; SD's shorter self-attentions
+// have d = 80 / 160 and never get here).
+constexpr int AF_DEFAULT_MODE = 1;
+constexpr int AF_MIN_N = 4096;
+static int g_attn_fused_mode = -1;      // -1: not read yet
+static int attn_fused_mode() {
+    if (g_attn_fused_mode < 0) {
+        const char* e = getenv("SIDLSG_ATTN_BWD_FUSED");
+        const int v = e ? atoi(e) : AF_DEFAULT_MODE;
+        g_attn_fused_mode = v < 0 ? 0 : (v > 2 ? 2 : v);
+    }
+    return g_attn_fused_mode;
+}
+static bool attn_fused_rule(int mode, int H, int Nq, int Nk, int D, bool have_dkdv, long long ws_bytes) {
+    if (mode <= 0 || !have_dkdv || D <= 32 || D > 48 || D % 8 || Nq != Nk || Nk <= 0 || Nk % AF_KEYS) return false;
+    if (mode == 1 && Nk < AF_MIN_N) return false;
+    return (long long)H * (Nk / AF_KEYS) * Nq * D * 4 <= ws_bytes;
+}
+static int attn_bwd_fused(bool ps, const AttnParams& p_in, float* ws, long long ws_bytes, hipStream_t s) {
+    AttnParams p = p_in;
+    p.xcd = attn_xcd_on(2, p);
+    p.rot = attn_rot_on(2, p);
+    p.G = p.Nk / AF_KEYS;
+    p.slab = ws;
+    const int B = p.B;
+    {
+        const long long rows = (long long)B * p.Nq * p.H;
+        SIDLSG_LAUNCH(attn_delta_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, p.O, p.dO, p.delta_out, B, p.H, p.Nq, p.D, p.ldo, p.bso);
+    }
+    constexpr int lds = attn_fused_lds_bytes<48>();
+    static bool attr_done = false;
+    if (!attr_done) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_fused_kernel<48, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
+            hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_fused_kernel<48, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
+            return SIDLSG_EINVAL;
+        attr_done = true;
+    }
+    const long long per_b = (long long)p.H * p.G * p.Nq * p.D * 4;
+    int bc = (int)(ws_bytes / per_b < B ? ws_bytes / per_b : B);       // >= 1 (attn_fused_rule)
+    // One workgroup per CU is resident and all of them run equally long, so a chunk whose workgroups do not fill the CUs a whole number
+    // of times pays for the empty places: measured at N 4096, 8 heads, B 16 (MI355X, 256 CUs; 64 workgroups per batch element): chunks of
+    // 4 / 16 batch elements 1451 / 1454 us, of 6 (1.5 rounds) 1747 us, of 2 (half a round) 2712 us.  -> the largest chunk <= what fits
+    // that fills whole rounds, when there is one.
+    static int ncu = 0;
+    if (!ncu) {
+        int dev_ = 0;
+        if (hipGetDevice(&dev_) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev_) != hipSuccess || ncu <= 0) ncu = 256;
+    }
+    if (bc < B)
+        for (int c = bc; c >= 1; c--)
+            if ((long long)c * p.H * p.G % ncu == 0) { bc = c; break; }
+    const bf16 *Q0 = p.Q, *K0 = p.K, *V0 = p.V, *dO0 = p.dO;
+    bf16 *dQ0 = p.dQ, *dK0 = p.dK, *dV0 = p.dV;
+    float* LSE0 = p.LSE;
+    const float* DL0 = p.delta;
+    for (int b0 = 0; b0 < B; b0 += bc) {
+        p.B = B - b0 < bc ? B - b0 : bc;
+        p.Q = Q0 + b0 * p.bsq; p.K = K0 + b0 * p.bsk; p.V = V0 + b0 * p.bsv; p.dO = dO0 + b0 * p.bso;
+        p.dQ = dQ0 + b0 * p.bsq; p.dK = dK0 + b0 * p.bsk; p.dV = dV0 + b0 * p.bsv;
+        p.LSE = LSE0 + (long long)b0 * p.H * p.Nq; p.delta = DL0 + (long long)b0 * p.H * p.Nq;
+        if (ps) SIDLSG_LAUNCH((attn_bwd_fused_kernel<48, true>), dim3(p.G, p.H, p.B), dim3(512), lds, s, p);
+        else SIDLSG_LAUNCH((attn_bwd_fused_kernel<48, false>), dim3(p.G, p.H, p.B), dim3(512), lds, s, p);
+        const long long n4 = (long long)p.B * p.H * p.Nq * (p.D / 4);
+        SIDLSG_LAUNCH(attn_dq_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, ws, p.dQ, p.B, p.H, p.G, p.Nq, p.D, p.ldq, p.bsq, p.scale);
+    }
+    return sidlsg_last_error();
+}
 static int attn_bwd_impl(bool ps, const void* Q, const void* K, const void* V, const void* O, const void* dO, const float* LSE, void* dQ,
                          void* dK, void* dV, float* delta, int B, int H, int Nq, int Nk, int D, int ldq, int ldk, int ldv, int ldo,
                          long long bsq, long long bsk, long long bsv, long long bso, void* stream) {
@@ -888,6 +1221,11 @@ static int attn_bwd_impl(bool ps, const void* Q, const void* K, const void* V, c
     p.bsq = bsq; p.bsk = bsk; p.bsv = bsv; p.bso = bso;
     p.scale = 1.0f / sqrtf((float)D); p.scale2 = p.scale * 1.4426950408889634f;
     p.O = const_cast<bf16*>((const bf16*)O); p.delta_out = delta;
+    {
+        long long wsb = 0;
+        float* ws = sidlsg_ws_for_stream(s, &wsb);
+        if (attn_fused_rule(attn_fused_mode(), H, Nq, Nk, D, dK && dV, ws ? wsb : 0)) return attn_bwd_fused(ps, p, ws, wsb, s);
+    }
     if (int e = ps ? dispatch_attn<true>(p, 1, s) : dispatch_attn<false>(p, 1, s)) return e;
     // dK == dV == null: the caller needs the query gradient only (cross-attention of a FROZEN network: K / V come from the
     // text states through frozen weights, nothing upstream wants their gradient) -- the dK/dV pass over 77 keys has only
@@ -931,6 +1269,21 @@ int sidlsg_attn_bwd_ps(const void* Q, const void* K, const void* V, const void* 
                        long long bsq, long long bsk, long long bsv, long long bso, void* stream) {
     SidlsgTraceScope ts(SIDLSG_FAM_ATTN_BWD, ((dK && dV) ? 10.0 : 6.0) * B * H * Nq * (double)Nk * D, 2.0 * B * H * D * (4.0 * Nq + ((dK && dV) ? 4.0 : 2.0) * Nk));
     return attn_bwd_impl(true, Q, K, V, O, dO, LSE, dQ, dK, dV, delta, B, H, Nq, Nk, D, ldq, ldk, ldv, ldo, bsq, bsk, bsv, bso, stream);
+}
+
+// A/B switch of the fused d = 40 backward (attn_fused_mode): 0 never, 1 by rule, 2 every call the kernel can run; a negative value only
+// queries.  Returns the previous setting.
+int sidlsg_debug_set_attn_bwd_fused(int mode) {
+    const int old = attn_fused_mode();
+    if (mode >= 0) g_attn_fused_mode = mode > 2 ? 2 : mode;
+    return old;
+}
+// 1 when a backward call of this shape on the default stream's workspace takes the fused kernel under the current setting
+int sidlsg_attn_bwd_fused_takes(int B, int H, int Nq, int Nk, int D, int have_dkdv) {
+    (void)B;
+    long long wsb = 0;
+    float* ws = sidlsg_ws_for_stream(nullptr, &wsb);
+    return attn_fused_rule(attn_fused_mode(), H, Nq, Nk, D, have_dkdv != 0, ws ? wsb : 0) ? 1 : 0;
 }
 
 }  // extern "C"

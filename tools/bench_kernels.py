@@ -108,6 +108,7 @@ def bench_wgrad(B):
 
 def bench_attn(B):
     print('--- attention (N, heads, D): TFLOP/s fwd / bwd')
+    ops.ensure_workspace(dev)        # the fused d = 40 backward keeps its partial-dQ slabs there (a network's GEMMs have set it up by then)
     for N, heads, D in ((4096, 8, 40), (1024, 8, 80), (256, 8, 160), (4096, 5, 64)):
         C = heads * D
         qkv = r(B, N, 3 * C).requires_grad_()
@@ -120,6 +121,11 @@ def bench_attn(B):
         tb = timeit(bwd, iters=5)
         fl = 4.0 * B * heads * N * N * D
         print(f'  self N{N} h{heads} d{D}: fwd {tf * 1e6:8.1f} us {fl / tf / 1e12:6.1f} TF/s | bwd {tb * 1e6:8.1f} us {2.5 * fl / tb / 1e12:6.1f} TF/s')
+        if lib.sidlsg_attn_bwd_fused_takes.raw(B, heads, N, N, D, 1):       # the row above ran the fused backward: the two-kernel path beside it
+            old = lib.sidlsg_debug_set_attn_bwd_fused.raw(0)
+            t2 = timeit(bwd, iters=5)
+            lib.sidlsg_debug_set_attn_bwd_fused.raw(old)
+            print(f'       N{N} h{heads} d{D}: bwd on the two-kernel path (SIDLSG_ATTN_BWD_FUSED=0) {t2 * 1e6:8.1f} us {2.5 * fl / t2 / 1e12:6.1f} TF/s')
     for N, heads, D in ((4096, 8, 40), (1024, 8, 80)):
         C = heads * D
         q, kv = r(B, N, C), r(B, 77, 2 * C)
