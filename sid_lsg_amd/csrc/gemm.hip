@@ -758,6 +758,29 @@ bool sidlsg_det() {
     return g_det_mode == 1;
 }
 
+// Second launch of a split-K GEMM: the `splits` slabs of p.ws -> C through the epilogue (gemm_finish_kernel, four outputs per thread).
+static void launch_gemm_finish(const GemmParams& p, int splits, hipStream_t s) {
+    const size_t n4 = ((size_t)p.M * p.N + 3) / 4;
+    SIDLSG_LAUNCH(gemm_finish_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, p, splits);
+}
+
+// The split-K rule of every GEMM launcher: a launch of few tiles with a long contraction splits K so that ~TARGET blocks exist.
+// tiles: output tiles of the unsplit launch; nk: its k-tiles; mn = M * N (one fp32 slab per split in the workspace `w`, at least two must
+// fit); min_nk: k-tiles from which a contraction is split at all; min_kt: k-tiles every split keeps.  Returns the split count, 1 = none.
+static int splitk_splits(long long tiles, int nk, long long mn, const Ws& w, int min_nk, int min_kt) {
+    static const int MIN_TILES = getenv("SIDLSG_GEMM_MIN_TILES") ? atoi(getenv("SIDLSG_GEMM_MIN_TILES")) : 384;     // A/B knobs (defaults = the measured best)
+    static const int TARGET = getenv("SIDLSG_SPLITK_TARGET") ? atoi(getenv("SIDLSG_SPLITK_TARGET")) : 512;          // blocks a split launch aims at (2 per CU)
+    if (tiles >= MIN_TILES || nk < min_nk || !w.ptr || mn * 8 > w.bytes) return 1;
+    const long long splits = std::min(std::min<long long>((TARGET + tiles - 1) / tiles, w.bytes / (mn * 4)), (long long)std::min(nk / min_kt, 16));
+    return splits >= 2 ? (int)splits : 1;
+}
+// The bf16 kernels (64-element k-tiles): split from MIN_NK k-tiles on, keeping at least MIN_KT per split (A/B knobs)
+static int splitk_splits_bf16(long long tiles, int nk, long long mn, const Ws& w) {
+    static const int MIN_NK = getenv("SIDLSG_SPLITK_MIN_NK") ? atoi(getenv("SIDLSG_SPLITK_MIN_NK")) : 32;
+    static const int MIN_KT = getenv("SIDLSG_SPLITK_MIN_KT") ? atoi(getenv("SIDLSG_SPLITK_MIN_KT")) : 8;
+    return splitk_splits(tiles, nk, mn, w, MIN_NK, MIN_KT);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Direct-to-LDS (buffer_load ... lds) kernels.  (A 256 x 160 / 8-wave / 3-stage-ring variant "v2" and a
 // 256 x 160 / one-wave-per-SIMD / 32x32x16-MFMA variant "v5" were built and measured -- both correct, both slower
@@ -1228,10 +1251,7 @@ static int launch_gemm_v3(const GemmParams& p, hipStream_t s) {
     static const int group_env = getenv("SIDLSG_GEMM_GROUP_M") ? atoi(getenv("SIDLSG_GEMM_GROUP_M")) : 4;   // A/B switch (measured: 4 and 8 equivalent, 1 = row-major strips)
     q.group_m = group_env < 1 ? 1 : group_env;
     SIDLSG_LAUNCH((gemm_v3_kernel<MODE>), dim3(tiles * splits), dim3(NTHREADS), lds, s, q);
-    if (p.kt_per_split) {
-        const size_t n4 = ((size_t)p.M * p.N + 3) / 4;
-        SIDLSG_LAUNCH(gemm_finish_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, p, splits);
-    }
+    if (p.kt_per_split) launch_gemm_finish(p, splits, s);
     return sidlsg_last_error();
 }
 
@@ -1509,28 +1529,18 @@ static int launch_gemm_mx8(const GemmParams& p, hipStream_t s) {
     GemmParams q = p;
     q.group_m = 4;
     q.Mtot = p.M;            // row count of a split-K slab (a block of a grouped launch narrows its own M)
-    // few tiles (8x8 / 16x16 stages) and a long contraction: split K so that ~512 blocks exist (as gemm_v3_kernel does)
+    // few tiles (8x8 / 16x16 stages) and a long contraction: split K so that ~512 blocks exist (as gemm_v3_kernel does); the k-tiles
+    // are 128 elements here, so half as many are required: 16 to split at all, 4 per split
     const int nk = MODE == 1 ? 9 * ((p.Cin + 127) / 128) : (p.K + 127) / 128;
-    int splits = 1;
     const Ws w = ws_for(s);
-    if (tiles < 384 && nk >= 16 && w.ptr && (long long)p.M * p.N * 8 <= w.bytes) {
-        splits = (512 + tiles - 1) / tiles;
-        const long long cap = w.bytes / ((long long)p.M * p.N * 4);
-        if (splits > cap) splits = (int)cap;
-        if (splits > nk / 4) splits = nk / 4;
-        if (splits > 16) splits = 16;
-        if (splits < 2) splits = 1;
-    }
+    int splits = splitk_splits(tiles, nk, (long long)p.M * p.N, w, 16, 4);
     if (splits > 1) {
         q.kt_per_split = (nk + splits - 1) / splits;
         q.ws = w.ptr;
         splits = (nk + q.kt_per_split - 1) / q.kt_per_split;
     }
     SIDLSG_LAUNCH((gemm_mx8_kernel<MODE>), dim3(tiles * splits), dim3(NTHREADS), lds, s, q);
-    if (splits > 1) {
-        const size_t n4 = ((size_t)p.M * p.N + 3) / 4;
-        SIDLSG_LAUNCH(gemm_finish_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, q, splits);
-    }
+    if (splits > 1) launch_gemm_finish(q, splits, s);
     return sidlsg_last_error();
 }
 
@@ -1817,10 +1827,7 @@ static int launch_gemm(const GemmParams& p, hipStream_t s) {
     const int nk = (p.K + BK - 1) / BK;
     const int splits = p.kt_per_split ? (nk + p.kt_per_split - 1) / p.kt_per_split : 1;
     SIDLSG_LAUNCH((gemm_bf16_kernel<BM, BN, MODE, PAD>), dim3(tiles, splits), dim3(NTHREADS), lds, s, p);
-    if (p.kt_per_split) {
-        const size_t n4 = ((size_t)p.M * p.N + 3) / 4;
-        SIDLSG_LAUNCH(gemm_finish_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, p, splits);
-    }
+    if (p.kt_per_split) launch_gemm_finish(p, splits, s);
     return sidlsg_last_error();
 }
 
@@ -1843,7 +1850,7 @@ static int p8_mode() {
 // profiles/r06_p8_step_ab.txt): the rule offers it to dense calls only and only with SIDLSG_P8_S=1.
 struct P8Choice { int cfg, splits; };
 template <int MODE>
-static P8Choice p8_rule(const GemmParams& p, long long ws_bytes) {
+static P8Choice p8_rule(const GemmParams& p, const Ws& w) {
     static const int margin_pct = getenv("SIDLSG_P8_MARGIN") ? atoi(getenv("SIDLSG_P8_MARGIN")) : 3;
     static const bool dense_too = !(getenv("SIDLSG_P8_DENSE") && atoi(getenv("SIDLSG_P8_DENSE")) == 0);      // A/B switch: dense GEMMs by the same model
     static const bool s_too = getenv("SIDLSG_P8_S") && atoi(getenv("SIDLSG_P8_S")) != 0;                     // A/B switch: the 256 x 160 configuration for dense GEMMs (off: neutral in the step)
@@ -1851,14 +1858,10 @@ static P8Choice p8_rule(const GemmParams& p, long long ws_bytes) {
     const int nk = p.K / BK;
     const double mn = (double)p.M * p.N;
     auto fin = [&](int s) { return s > 1 ? (8.0 * s + 4.0) * mn / 10e6 : 0.0; };
-    const long long cap = ws_bytes > 0 ? ws_bytes / (long long)(mn * 4) : 1;
-    // v3 as dispatch_gemm would launch it
+    const long long cap = w.ptr && w.bytes > 0 ? w.bytes / (long long)(mn * 4) : 1;
+    // v3 as dispatch_gemm would launch it: the same split-K rule with the same knobs
     const long long t3 = (long long)m_tiles_rt(p, 128) * (p.N / 160);
-    int s3 = 1;
-    if (t3 < 384 && nk >= 32 && cap >= 2) {
-        s3 = (int)std::min<long long>(std::min<long long>((512 + t3 - 1) / t3, cap), std::min(nk / 8, 16));
-        if (s3 < 2) s3 = 1;
-    }
+    const int s3 = splitk_splits_bf16(t3, nk, (long long)p.M * p.N, w);
     const double v3_us = (double)((t3 * s3 + 511) / 512) * (11.0 + 1.03 * ((nk + s3 - 1) / s3)) + fin(s3);
     P8Choice best{-1, 1};
     double best_us = v3_us * 100.0 / (100 + margin_pct);
@@ -1909,7 +1912,7 @@ static int dispatch_gemm(const GemmParams& pin, hipStream_t s) {
             if (ch.cfg >= 0 && t < 192 && w.ptr && (long long)p.M * p.N * 8 <= w.bytes)
                 ch.splits = std::max(1, (int)std::min<long long>(std::min<long long>((256 + t - 1) / t, w.bytes / ((long long)p.M * p.N * 4)), std::min(nk / 12, 16)));
         } else if (mode < 0) {
-            ch = p8_rule<MODE>(p, w.ptr ? w.bytes : 0);
+            ch = p8_rule<MODE>(p, w);
         }
         if (ch.cfg >= 0) {
             GemmParams q = p;
@@ -1920,32 +1923,17 @@ static int dispatch_gemm(const GemmParams& pin, hipStream_t s) {
     const bool n160 = p.N % 160 == 0;
     static const bool v3_on = !(getenv("SIDLSG_GEMM_V3") && atoi(getenv("SIDLSG_GEMM_V3")) == 0);   // A/B switch
     const bool v3 = n160 && v3_on && MODE != 2;
-    // A/B knobs (defaults = the measured best): launches with fewer than MIN_TILES 128-row tiles split K when the
-    // contraction has at least MIN_NK k-tiles, keeping at least MIN_KT k-tiles per split
-    static const int MIN_TILES = getenv("SIDLSG_GEMM_MIN_TILES") ? atoi(getenv("SIDLSG_GEMM_MIN_TILES")) : 384;
-    static const int MIN_NK = getenv("SIDLSG_SPLITK_MIN_NK") ? atoi(getenv("SIDLSG_SPLITK_MIN_NK")) : 32;
-    static const int MIN_KT = getenv("SIDLSG_SPLITK_MIN_KT") ? atoi(getenv("SIDLSG_SPLITK_MIN_KT")) : 8;
     static const int V3_DIRECT_TILES = getenv("SIDLSG_V3_DIRECT_TILES") ? atoi(getenv("SIDLSG_V3_DIRECT_TILES")) : 256;   // 256 since the compact epilogue: 4096x1280x1280 28.1 -> 23.9 us
-    {
-        const long long t = tiles(128, n160 ? 160 : 128);
+    if ((p.N & 3) == 0) {              // (gemm_finish_kernel handles four columns per thread)
         const int nk = (p.K + BK - 1) / BK;
         const Ws w = ws_for(s);
-        float* const g_ws = w.ptr;
-        const long long g_ws_bytes = w.bytes;
-        if (t < MIN_TILES && nk >= MIN_NK && (p.N & 3) == 0 && g_ws && (long long)p.M * p.N * 8 <= g_ws_bytes) {
-            static const int TARGET = getenv("SIDLSG_SPLITK_TARGET") ? atoi(getenv("SIDLSG_SPLITK_TARGET")) : 512;   // blocks a split launch aims at (2 per CU)
-            int splits = (int)((TARGET + t - 1) / t);
-            const long long cap = g_ws_bytes / ((long long)p.M * p.N * 4);
-            if (splits > cap) splits = (int)cap;
-            if (splits > nk / MIN_KT) splits = nk / MIN_KT;
-            if (splits > 16) splits = 16;
-            if (splits >= 2) {
-                GemmParams q = p;
-                q.kt_per_split = (nk + splits - 1) / splits;
-                q.ws = g_ws;
-                if (v3) return launch_gemm_v3<MODE == 2 ? 0 : MODE>(q, s);
-                return n160 ? launch_gemm<128, 160, MODE>(q, s) : launch_gemm<128, 128, MODE>(q, s);
-            }
+        const int splits = splitk_splits_bf16(tiles(128, n160 ? 160 : 128), nk, (long long)p.M * p.N, w);
+        if (splits >= 2) {
+            GemmParams q = p;
+            q.kt_per_split = (nk + splits - 1) / splits;
+            q.ws = w.ptr;
+            if (v3) return launch_gemm_v3<MODE == 2 ? 0 : MODE>(q, s);
+            return n160 ? launch_gemm<128, 160, MODE>(q, s) : launch_gemm<128, 128, MODE>(q, s);
         }
     }
     if (tiles(128, n160 ? 160 : 128) >= (v3 ? V3_DIRECT_TILES : 384)) {
@@ -1963,6 +1951,51 @@ static int check_common(const GemmParams& p) {
     if (p.rowvec && p.rows_per_batch <= 0) return SIDLSG_EINVAL;
     if ((p.flags & F_ACCUM) && !(p.flags & F_OUT_F32)) return SIDLSG_EINVAL;
     return SIDLSG_OK;
+}
+
+// ---- host side of the entry points: filling GemmParams, operand ranges, the second set of a grouped call
+static bool fits31(unsigned long long bytes) { return bytes < 0x7FFFFFFFull; }
+
+// Byte range of an operand for its 31-bit buffer descriptor: `rows` rows of `ld` elements of `esize` bytes, `cols` of them used (a weight
+// matrix: N rows with ld = cols = K, or 9 Cout rows of Cin; e4m3 operands: esize 1).  The check counts `halo` more elements, which `range` does not include.  False: the operand is too large.
+static bool range31(unsigned& range, unsigned long long rows, int ld, int cols, int esize, unsigned long long halo = 0) {
+    const unsigned long long bytes = ((rows - 1) * ld + cols) * esize;
+    if (!fits31(bytes + halo * esize)) return false;
+    range = (unsigned)bytes;
+    return true;
+}
+// pixels of the image a 3x3 conv reads: `ups` reads a half-size source through a nearest x2 upsample
+static unsigned long long conv_src_pixels(int B, int H, int Wd, int ups) { return (unsigned long long)B * (ups ? H / 2 : H) * (ups ? Wd / 2 : Wd); }
+
+// Operands, epilogue and shape of a dense contraction.  The caller adds what its format needs (wscale, the GEGLU fields, the second set).
+static GemmParams dense_params(const void* A, int lda, const void* W, void* C, int ldc, const float* bias, const void* res, int ldres,
+                               const float* rowvec, int ld_rowvec, int rows_per_batch, int M, int N, int K, float alpha, int flags) {
+    GemmParams p{};
+    p.A = (const bf16*)A; p.W = (const bf16*)W; p.C = C; p.bias = bias; p.res = (const bf16*)res; p.rowvec = rowvec;
+    p.ldrv = ld_rowvec > 0 ? ld_rowvec : N;
+    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldc = ldc; p.ldres = ldres; p.rows_per_batch = rows_per_batch;
+    p.alpha = alpha; p.flags = flags;
+    return p;
+}
+// The same for a 3x3 conv (pad 1) as an implicit GEMM: M = output pixels, K = 9 taps x Cin, one row-vector row per image.  stride: 1 or 2.
+static GemmParams conv_params(const void* X, int ldx, const void* W, void* Y, int ldc, const float* bias, const void* res, int ldres,
+                              const float* rowvec, int ld_rowvec, int B, int H, int Wd, int Cin, int Cout, int stride, int ups, float alpha,
+                              int flags) {
+    const int Ho = (H + 2 - 3) / stride + 1, Wo = (Wd + 2 - 3) / stride + 1;
+    GemmParams p = dense_params(X, ldx, W, Y, ldc, bias, res, ldres, rowvec, ld_rowvec, Ho * Wo, B * Ho * Wo, Cout, 9 * Cin, alpha, flags);
+    p.H = H; p.Wd = Wd; p.Cin = Cin; p.stride = stride; p.ups = ups; p.Ho = Ho; p.Wo = Wo;
+    return p;
+}
+
+// The grouped forms (sidlsg_*_g2, include/sidlsg_hip.h "grouped launches"): a second set (W1, wscale1, bias1) for the rows / samples of the
+// second half; g2 = false: the ordinary launch (Mg = 0), exactly as before the grouped forms existed.  bf16 weights have no wscale1; the
+// e4m3 entry points check theirs.
+static void set_group2(GemmParams& p, bool g2, const void* W1, const float* wscale1, const float* bias1) {
+    if (!g2) return;
+    p.W1 = (const bf16*)W1; p.wscale1 = wscale1; p.bias1 = bias1; p.Mg = p.M / 2;
+}
+static bool group2_args_ok(int rows, const void* W1, const float* bias, const float* bias1) {
+    return W1 && !(rows & 1) && (bias != nullptr) == (bias1 != nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2578,6 +2611,17 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ ws, float* __restr
 extern "C" int sidlsg_colsum(const void* g, int ldg, float* per_batch, float* total, float* ws, int B, int rows_per_batch, int N,
                              void* stream);
 
+// Dynamic LDS of the wgrad_v2* kernels: two stages of WG_MB contraction rows of a tn-wide dY tile and a tk-wide A tile
+constexpr int wgrad_v2_lds(int tn, int tk) { return 2 * WG_MB * (tn + tk) * (int)sizeof(bf16); }
+
+// A pixel split: M contraction rows over `splits` blocks -> rows per split in whole LDS stages (WG_MB rows) and the number of splits
+// that many rows per split need (<= `splits`)
+struct PixelSplit { int mps, splits; };
+static PixelSplit pixel_split(int M, int splits) {
+    const int mps = ((M + splits - 1) / splits + WG_MB - 1) / WG_MB * WG_MB;
+    return {mps, (M + mps - 1) / mps};
+}
+
 // Deterministic mode, weight gradients: the pixel splits never meet in fp32 atomics.  dW: slabs + wgrad_reduce_kernel (split order) or
 // one split when no two slabs fit; the bias: the k-tile-0 blocks of every split added into dB, so with several splits the kernel
 // gets no dB and the bias gradient is an order-fixed column sum of dY (sidlsg_colsum, B = 1) after it.
@@ -2605,7 +2649,7 @@ static int launch_wgrad(WgradParams p, hipStream_t s) {
     // Split the pixel contraction so the grid fills the chip in whole rounds of 512 resident blocks (256 CUs x 2).
     // Small cost model (us): rounds * (rows per block * 24 ns + 3 us block overhead) + slab reduction at ~4 TB/s;
     // e.g. 69 tiles: ceil(768/69) = 12 splits ran 1.6 rounds, the model picks a whole number of rounds.
-    int splits = 1;
+    int want = 1;
     {
         const int cap = std::min(64, (p.M + 4 * WG_MB - 1) / (4 * WG_MB));
         static const int slots = getenv("SIDLSG_WGRAD_SLOTS") ? atoi(getenv("SIDLSG_WGRAD_SLOTS")) : 512;   // A/B knob: resident blocks a launch may count on
@@ -2615,54 +2659,46 @@ static int launch_wgrad(WgradParams p, hipStream_t s) {
             const int rounds = (sp * tiles + slots - 1) / slots;
             const double rows = (double)((p.M + sp - 1) / sp);
             const double est = rounds * (rows * 0.024 + 3.0) + (sp > 1 ? sp * slab_us : 0.0);
-            if (est < best) { best = est; splits = sp; }
+            if (est < best) { best = est; want = sp; }
         }
     }
     const int max_splits = (p.M + 4 * WG_MB - 1) / (4 * WG_MB);
-    if (splits > max_splits) splits = max_splits;
-    if (splits < 1) splits = 1;
-    int mps = (p.M + splits - 1) / splits;
-    mps = (mps + WG_MB - 1) / WG_MB * WG_MB;
-    splits = (p.M + mps - 1) / mps;
+    if (want > max_splits) want = max_splits;
+    if (want < 1) want = 1;
+    PixelSplit ps = pixel_split(p.M, want);
     const long long nk = (long long)p.N * p.K;
     const Ws wsl = ws_for(s);
-    float* const g_ws = wsl.ptr;
-    const long long g_ws_bytes = wsl.bytes;
-    if (splits > 1 && g_ws) {                       // cap the split count by the slab space
-        const long long cap = g_ws_bytes / (nk * 4);
+    if (ps.splits > 1 && wsl.ptr) {                 // cap the split count by the slab space
+        const long long cap = wsl.bytes / (nk * 4);
         if (cap < 2) { p.ws = nullptr; }
         else {
-            if (splits > cap) {
-                splits = (int)cap;
-                mps = (p.M + splits - 1) / splits;
-                mps = (mps + WG_MB - 1) / WG_MB * WG_MB;
-                splits = (p.M + mps - 1) / mps;
-            }
-            p.ws = g_ws;
+            if (ps.splits > cap) ps = pixel_split(p.M, (int)cap);
+            p.ws = wsl.ptr;
         }
     }
     float* det_dB = nullptr;
-    if (sidlsg_det() && splits > 1) {
+    if (sidlsg_det() && ps.splits > 1) {
         if (!p.ws || (p.dB && (p.N & 7))) {
-            splits = 1; mps = (p.M + WG_MB - 1) / WG_MB * WG_MB; p.ws = nullptr;
+            ps = pixel_split(p.M, 1); p.ws = nullptr;
         } else {
             det_dB = p.dB; p.dB = nullptr;
         }
     }
-    p.m_per_split = mps;
+    const int splits = ps.splits;
+    p.m_per_split = ps.mps;
     p.nsplits = splits;
-    if (p.assign && splits > 1 && !p.ws) {          // fp32-atomic fallback (no slab space): the atomics need a zeroed target
+    if (p.assign && splits > 1 && !p.ws) {         // fp32-atomic fallback (no slab space): the atomics need a zeroed target
         if (hipMemsetAsync(p.dW, 0, (size_t)nk * sizeof(float), s) != hipSuccess) return sidlsg_last_error();
     }
     if (v2) {
-        const size_t lds = (size_t)2 * WG_MB * (tn + tk) * sizeof(bf16);
+        const size_t lds = (size_t)wgrad_v2_lds(tn, tk);
         static bool attr_done = false;
         if (!attr_done) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_v2_kernel<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * WG_MB * (128 + WG_T) * 2);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_v2w_kernel<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * WG_MB * (160 + WG_T) * 2);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_v2s_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * WG_MB * (160 + 160) * 2);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_v2f_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * WG_MB * (128 + WG_T) * 2);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_v2wf_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * WG_MB * (160 + WG_T) * 2);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_v2_kernel<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, wgrad_v2_lds(128, WG_T));
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_v2w_kernel<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, wgrad_v2_lds(160, WG_T));
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_v2s_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, wgrad_v2_lds(160, 160));
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_v2f_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, wgrad_v2_lds(128, WG_T));
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_v2wf_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, wgrad_v2_lds(160, WG_T));
             attr_done = true;
         }
         bool cf = false;
@@ -2684,8 +2720,6 @@ static int launch_wgrad(WgradParams p, hipStream_t s) {
     if (det_dB) return sidlsg_colsum(p.dY, p.ldy, nullptr, det_dB, nullptr, 1, p.M, p.N, s);      // after the reduction: it reuses the workspace
     return sidlsg_last_error();
 }
-
-static bool fits31(unsigned long long bytes) { return bytes < 0x7FFFFFFFull; }
 
 // Host side of the grouped dense weight gradient.  Every job must be one the 128 x 128 direct-to-LDS kernel takes (aligned operands);
 // the split count is chosen for the GROUP: all jobs together should put ~512 blocks on the chip (whole rounds, like launch_wgrad's
@@ -2714,24 +2748,18 @@ static int launch_wgrad_group(WgradParams* jobs, int njobs, hipStream_t s, bool 
     for (int i = 0; i < njobs; i++) {
         WgradParams p = jobs[i];
         const int max_splits = (p.M + 4 * WG_MB - 1) / (4 * WG_MB);
-        int splits = std::min(std::min(want, 64), std::max(1, max_splits));
-        int mps = (p.M + splits - 1) / splits;
-        mps = (mps + WG_MB - 1) / WG_MB * WG_MB;
-        splits = (p.M + mps - 1) / mps;
+        PixelSplit ps = pixel_split(p.M, std::min(std::min(want, 64), std::max(1, max_splits)));
         const long long nk = (long long)p.N * p.K;
         p.ws = nullptr;
-        if (splits > 1) {
+        if (ps.splits > 1) {
             // slabs that do not fit what is left of the workspace: as many splits as do fit (launch_wgrad does the same), one only when not even two fit
             const long long fit = (wsl.ptr && !(nk & 3)) ? (wsl.bytes - ws_used) / (nk * 4) : 0;
-            if (fit < splits) {
-                splits = fit >= 2 ? (int)fit : 1;
-                mps = ((p.M + splits - 1) / splits + WG_MB - 1) / WG_MB * WG_MB;
-                splits = (p.M + mps - 1) / mps;
-            }
-            if (splits > 1) { p.ws = reinterpret_cast<float*>(reinterpret_cast<char*>(wsl.ptr) + ws_used); ws_used += ((long long)splits * nk * 4 + 255) / 256 * 256; }
+            if (fit < ps.splits) ps = pixel_split(p.M, fit >= 2 ? (int)fit : 1);
         }
+        const int splits = ps.splits;
+        if (splits > 1) { p.ws = reinterpret_cast<float*>(reinterpret_cast<char*>(wsl.ptr) + ws_used); ws_used += ((long long)splits * nk * 4 + 255) / 256 * 256; }
         if (sidlsg_det() && splits > 1 && p.dB) { det_dB[i] = p.dB; p.dB = nullptr; }      // (see launch_wgrad)
-        p.m_per_split = mps;
+        p.m_per_split = ps.mps;
         p.nsplits = splits;
         g.blk0[i] = blocks;
         p.bid0 = blocks;
@@ -2746,11 +2774,11 @@ static int launch_wgrad_group(WgradParams* jobs, int njobs, hipStream_t s, bool 
     }
     g.blk0[njobs] = blocks;
     rg.njobs = rjobs; rg.blk0[rjobs] = rblocks;
-    const size_t lds = (size_t)2 * WG_MB * (t160 ? 320 : 128 + WG_T) * sizeof(bf16);
+    const size_t lds = (size_t)(t160 ? wgrad_v2_lds(160, 160) : wgrad_v2_lds(128, WG_T));
     static bool attr_done = false;
     if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_v2g_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * WG_MB * (128 + WG_T) * 2);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_v2sg_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * WG_MB * 320 * 2);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_v2g_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, wgrad_v2_lds(128, WG_T));
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_v2sg_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, wgrad_v2_lds(160, 160));
         attr_done = true;
     }
     if (t160) SIDLSG_LAUNCH(wgrad_v2sg_kernel, dim3(blocks), dim3(NTHREADS), lds, s, g);
@@ -2767,7 +2795,7 @@ extern "C" {
 // (diagnostic) resident blocks per CU of the weight-gradient kernels with their dynamic LDS: 0 = 128x128, 1 = 160x128, 2 = 160x160
 int sidlsg_debug_wgrad_blocks_per_cu(int which) {
     int n = -1;
-    const size_t lds = (size_t)2 * WG_MB * ((which ? 160 : 128) + (which == 2 ? 160 : 128)) * 2;
+    const size_t lds = (size_t)wgrad_v2_lds(which ? 160 : 128, which == 2 ? 160 : WG_T);
     const void* f = which == 2 ? reinterpret_cast<const void*>(&wgrad_v2s_kernel)
                                : which ? reinterpret_cast<const void*>(&wgrad_v2w_kernel<0>) : reinterpret_cast<const void*>(&wgrad_v2_kernel<0>);
     (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -2814,19 +2842,20 @@ int sidlsg_set_stream_workspace(void* stream, void* ptr, long long bytes) {
 }
 
 // Dense GEMM: C[M,N] = act(alpha * A[M,K] W[N,K]^T + bias[N] + rowvec[m/rpb,N] + res[M,N])
+static int gemm_bf16_impl(bool g2, const void* A, int lda, const void* W, const void* W1, void* C, int ldc, const float* bias, const float* bias1,
+                          const void* res, int ldres, const float* rowvec, int ld_rowvec, int rows_per_batch, int M, int N, int K, float alpha,
+                          int flags, void* stream) {
+    if (g2 && !group2_args_ok(M, W1, bias, bias1)) return SIDLSG_EINVAL;
+    GemmParams p = dense_params(A, lda, W, C, ldc, bias, res, ldres, rowvec, ld_rowvec, rows_per_batch, M, N, K, alpha, flags);
+    if (int e = check_common(p)) return e;
+    if (!range31(p.a_bytes, M, lda, K, 2) || !range31(p.w_bytes, N, K, K, 2)) return SIDLSG_EINVAL;
+    set_group2(p, g2, W1, nullptr, bias1);
+    return dispatch_gemm<0>(p, (hipStream_t)stream);
+}
 int sidlsg_gemm_bf16(const void* A, int lda, const void* W, void* C, int ldc, const float* bias, const void* res,
                      int ldres, const float* rowvec, int ld_rowvec, int rows_per_batch, int M, int N, int K, float alpha,
                      int flags, void* stream) {
-    GemmParams p{};
-    p.A = (const bf16*)A; p.W = (const bf16*)W; p.C = C; p.bias = bias; p.res = (const bf16*)res; p.rowvec = rowvec;
-    p.ldrv = ld_rowvec > 0 ? ld_rowvec : N;
-    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldc = ldc; p.ldres = ldres; p.rows_per_batch = rows_per_batch;
-    p.alpha = alpha; p.flags = flags;
-    if (int e = check_common(p)) return e;
-    const unsigned long long ab = ((unsigned long long)(M - 1) * lda + K) * 2ull, wb = (unsigned long long)N * K * 2ull;
-    if (!fits31(ab) || !fits31(wb)) return SIDLSG_EINVAL;
-    p.a_bytes = (unsigned)ab; p.w_bytes = (unsigned)wb;
-    return dispatch_gemm<0>(p, (hipStream_t)stream);
+    return gemm_bf16_impl(false, A, lda, W, nullptr, C, ldc, bias, nullptr, res, ldres, rowvec, ld_rowvec, rows_per_batch, M, N, K, alpha, flags, stream);
 }
 
 // Grouped dense GEMM: two weight sets on one stacked activation matrix (M even): rows [0, M/2) use (W, bias), rows [M/2, M)
@@ -2835,18 +2864,7 @@ int sidlsg_gemm_bf16(const void* A, int lda, const void* W, void* C, int ldc, co
 int sidlsg_gemm_bf16_g2(const void* A, int lda, const void* W, const void* W1, void* C, int ldc, const float* bias, const float* bias1,
                         const void* res, int ldres, const float* rowvec, int ld_rowvec, int rows_per_batch, int M, int N, int K,
                         float alpha, int flags, void* stream) {
-    if (!W1 || (M & 1) || (bias != nullptr) != (bias1 != nullptr)) return SIDLSG_EINVAL;
-    GemmParams p{};
-    p.A = (const bf16*)A; p.W = (const bf16*)W; p.C = C; p.bias = bias; p.res = (const bf16*)res; p.rowvec = rowvec;
-    p.W1 = (const bf16*)W1; p.bias1 = bias1; p.Mg = M / 2;
-    p.ldrv = ld_rowvec > 0 ? ld_rowvec : N;
-    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldc = ldc; p.ldres = ldres; p.rows_per_batch = rows_per_batch;
-    p.alpha = alpha; p.flags = flags;
-    if (int e = check_common(p)) return e;
-    const unsigned long long ab = ((unsigned long long)(M - 1) * lda + K) * 2ull, wb = (unsigned long long)N * K * 2ull;
-    if (!fits31(ab) || !fits31(wb)) return SIDLSG_EINVAL;
-    p.a_bytes = (unsigned)ab; p.w_bytes = (unsigned)wb;
-    return dispatch_gemm<0>(p, (hipStream_t)stream);
+    return gemm_bf16_impl(true, A, lda, W, W1, C, ldc, bias, bias1, res, ldres, rowvec, ld_rowvec, rows_per_batch, M, N, K, alpha, flags, stream);
 }
 
 // FF-in projection + GEGLU in one kernel: h[M][N2] = A W^T + bias (N2 = 2 F; H may be NULL: not stored),
@@ -2857,19 +2875,23 @@ int sidlsg_gemm_geglu_ok(int M, int N2, int K) {
     if (!on || M <= 0 || N2 <= 0 || K <= 0 || (N2 % 160) || (K & 7)) return 0;
     return (long long)((M + 127) / 128) * (N2 / 160) >= 256 ? 1 : 0;
 }
-int sidlsg_gemm_geglu_bf16(const void* A, int lda, const void* W, void* H, int ldh, void* Y, int ldy, const float* bias, int M, int N2,
-                           int K, void* stream) {
-    if (!sidlsg_gemm_geglu_ok(M, N2, K) || !Y || (ldy & 7) || (ldh & 7) || (lda & 7)) return SIDLSG_EINVAL;
-    GemmParams p{};
-    p.A = (const bf16*)A; p.W = (const bf16*)W; p.C = H; p.bias = bias; p.Y = (bf16*)Y; p.ldy = ldy; p.geglu = N2 / 2;
-    p.ldrv = N2; p.M = M; p.N = N2; p.K = K; p.lda = lda; p.ldc = ldh; p.rows_per_batch = 1; p.alpha = 1.f; p.Mtot = M;
-    if (!A || !W) return SIDLSG_EINVAL;
-    const unsigned long long ab = ((unsigned long long)(M - 1) * lda + K) * 2ull, wb = (unsigned long long)N2 * K * 2ull;
-    if (!fits31(ab) || !fits31(wb)) return SIDLSG_EINVAL;
-    p.a_bytes = (unsigned)ab; p.w_bytes = (unsigned)wb;
-    SidlsgTraceScope ts(SIDLSG_FAM_GEMM, 2.0 * M * (double)N2 * K, 2.0 * ((double)M * K + (double)N2 * K + (double)M * N2 * (H ? 1.5 : 0.5)));
+// (the two fusions go straight to their kernels: no dispatch_gemm, no check_common; g2: the grouped forms below)
+static int gemm_geglu_impl(bool g2, const void* A, int lda, const void* W, const void* W1, void* H, int ldh, void* Y, int ldy, const float* bias,
+                           const float* bias1, int M, int N2, int K, void* stream) {
+    if (!sidlsg_gemm_geglu_ok(M, N2, K) || !A || !W || !Y || (ldy & 7) || (ldh & 7) || (lda & 7)) return SIDLSG_EINVAL;
+    if (g2 && !group2_args_ok(M, W1, bias, bias1)) return SIDLSG_EINVAL;
+    GemmParams p = dense_params(A, lda, W, H, ldh, bias, nullptr, 0, nullptr, N2, 1, M, N2, K, 1.f, 0);
+    p.Y = (bf16*)Y; p.ldy = ldy; p.geglu = N2 / 2; p.Mtot = M;
+    if (!range31(p.a_bytes, M, lda, K, 2) || !range31(p.w_bytes, N2, K, K, 2)) return SIDLSG_EINVAL;
+    set_group2(p, g2, W1, nullptr, bias1);
+    SidlsgTraceScope ts(SIDLSG_FAM_GEMM, 2.0 * M * (double)N2 * K,
+                        2.0 * ((double)M * K + (g2 ? 2.0 : 1.0) * (double)N2 * K + (double)M * N2 * (H ? 1.5 : 0.5)));
     if (p8_geglu_takes(p)) return launch_gemm_p8_geglu<1>(p, (hipStream_t)stream);
     return launch_gemm_v3<0>(p, (hipStream_t)stream);
+}
+int sidlsg_gemm_geglu_bf16(const void* A, int lda, const void* W, void* H, int ldh, void* Y, int ldy, const float* bias, int M, int N2,
+                           int K, void* stream) {
+    return gemm_geglu_impl(false, A, lda, W, nullptr, H, ldh, Y, ldy, bias, nullptr, M, N2, K, stream);
 }
 
 // Data gradient of the FF-out projection + GEGLU derivative in one kernel: dy = dOut Wt^T (Wt = the [F][K] backward-data operand of
@@ -2883,18 +2905,21 @@ int sidlsg_gemm_geglu_bwd_ok(int M, int F, int K) {
     if (!on || M <= 0 || F <= 0 || K <= 0 || (F % 160) || (K & 7)) return 0;
     return (long long)((M + 127) / 128) * (F / 160) >= 256 ? 1 : 0;
 }
-int sidlsg_gemm_geglu_bwd_bf16(const void* dOut, int lda, const void* Wt, const void* H, void* dH, int ldh, int M, int F, int K,
-                               void* stream) {
+static int gemm_geglu_bwd_impl(bool g2, const void* dOut, int lda, const void* Wt, const void* Wt1, const void* H, void* dH, int ldh, int M, int F,
+                               int K, void* stream) {
     if (!sidlsg_gemm_geglu_bwd_ok(M, F, K) || !dOut || !Wt || !H || !dH || (ldh & 7) || (lda & 7) || ldh < 2 * F) return SIDLSG_EINVAL;
-    GemmParams p{};
-    p.A = (const bf16*)dOut; p.W = (const bf16*)Wt; p.C = nullptr; p.Y = (bf16*)dH; p.Hin = (const bf16*)H; p.ldy = ldh; p.geglu_bwd = F;
-    p.ldrv = F; p.M = M; p.N = F; p.K = K; p.lda = lda; p.ldc = F; p.rows_per_batch = 1; p.alpha = 1.f; p.Mtot = M;
-    const unsigned long long ab = ((unsigned long long)(M - 1) * lda + K) * 2ull, wb = (unsigned long long)F * K * 2ull;
-    if (!fits31(ab) || !fits31(wb)) return SIDLSG_EINVAL;
-    p.a_bytes = (unsigned)ab; p.w_bytes = (unsigned)wb;
-    SidlsgTraceScope ts(SIDLSG_FAM_GEMM, 2.0 * M * (double)F * K, 2.0 * ((double)M * K + (double)F * K + 4.0 * (double)M * F));
+    if (g2 && !group2_args_ok(M, Wt1, nullptr, nullptr)) return SIDLSG_EINVAL;
+    GemmParams p = dense_params(dOut, lda, Wt, nullptr, F, nullptr, nullptr, 0, nullptr, F, 1, M, F, K, 1.f, 0);      // dy is never stored: no C
+    p.Y = (bf16*)dH; p.Hin = (const bf16*)H; p.ldy = ldh; p.geglu_bwd = F; p.Mtot = M;
+    if (!range31(p.a_bytes, M, lda, K, 2) || !range31(p.w_bytes, F, K, K, 2)) return SIDLSG_EINVAL;
+    set_group2(p, g2, Wt1, nullptr, nullptr);
+    SidlsgTraceScope ts(SIDLSG_FAM_GEMM, 2.0 * M * (double)F * K, 2.0 * ((double)M * K + (g2 ? 2.0 : 1.0) * (double)F * K + 4.0 * (double)M * F));
     if (p8_geglu_takes(p)) return launch_gemm_p8_geglu<2>(p, (hipStream_t)stream);
     return launch_gemm_v3<0>(p, (hipStream_t)stream);
+}
+int sidlsg_gemm_geglu_bwd_bf16(const void* dOut, int lda, const void* Wt, const void* H, void* dH, int ldh, int M, int F, int K,
+                               void* stream) {
+    return gemm_geglu_bwd_impl(false, dOut, lda, Wt, nullptr, H, dH, ldh, M, F, K, stream);
 }
 
 // Grouped variants of the two GEGLU fusions (round 6: the grouped frozen pass of phase B -- 64 of an iteration's 144 sample-passes -- had fallen back
@@ -2903,82 +2928,40 @@ int sidlsg_gemm_geglu_bwd_bf16(const void* dOut, int lda, const void* Wt, const 
 // only see the block's rows).
 int sidlsg_gemm_geglu_bf16_g2(const void* A, int lda, const void* W, const void* W1, void* H, int ldh, void* Y, int ldy, const float* bias,
                               const float* bias1, int M, int N2, int K, void* stream) {
-    if (!sidlsg_gemm_geglu_ok(M, N2, K) || !Y || (ldy & 7) || (ldh & 7) || (lda & 7) || (M & 1) || !W1 || (bias != nullptr) != (bias1 != nullptr)) return SIDLSG_EINVAL;
-    GemmParams p{};
-    p.A = (const bf16*)A; p.W = (const bf16*)W; p.C = H; p.bias = bias; p.Y = (bf16*)Y; p.ldy = ldy; p.geglu = N2 / 2;
-    p.W1 = (const bf16*)W1; p.bias1 = bias1; p.Mg = M / 2;
-    p.ldrv = N2; p.M = M; p.N = N2; p.K = K; p.lda = lda; p.ldc = ldh; p.rows_per_batch = 1; p.alpha = 1.f; p.Mtot = M;
-    if (!A || !W) return SIDLSG_EINVAL;
-    const unsigned long long ab = ((unsigned long long)(M - 1) * lda + K) * 2ull, wb = (unsigned long long)N2 * K * 2ull;
-    if (!fits31(ab) || !fits31(wb)) return SIDLSG_EINVAL;
-    p.a_bytes = (unsigned)ab; p.w_bytes = (unsigned)wb;
-    SidlsgTraceScope ts(SIDLSG_FAM_GEMM, 2.0 * M * (double)N2 * K, 2.0 * ((double)M * K + 2.0 * (double)N2 * K + (double)M * N2 * (H ? 1.5 : 0.5)));
-    if (p8_geglu_takes(p)) return launch_gemm_p8_geglu<1>(p, (hipStream_t)stream);
-    return launch_gemm_v3<0>(p, (hipStream_t)stream);
+    return gemm_geglu_impl(true, A, lda, W, W1, H, ldh, Y, ldy, bias, bias1, M, N2, K, stream);
 }
 int sidlsg_gemm_geglu_bwd_bf16_g2(const void* dOut, int lda, const void* Wt, const void* Wt1, const void* H, void* dH, int ldh, int M, int F, int K,
                                   void* stream) {
-    if (!sidlsg_gemm_geglu_bwd_ok(M, F, K) || !dOut || !Wt || !Wt1 || !H || !dH || (ldh & 7) || (lda & 7) || ldh < 2 * F || (M & 1)) return SIDLSG_EINVAL;
-    GemmParams p{};
-    p.A = (const bf16*)dOut; p.W = (const bf16*)Wt; p.C = nullptr; p.Y = (bf16*)dH; p.Hin = (const bf16*)H; p.ldy = ldh; p.geglu_bwd = F;
-    p.W1 = (const bf16*)Wt1; p.Mg = M / 2;
-    p.ldrv = F; p.M = M; p.N = F; p.K = K; p.lda = lda; p.ldc = F; p.rows_per_batch = 1; p.alpha = 1.f; p.Mtot = M;
-    const unsigned long long ab = ((unsigned long long)(M - 1) * lda + K) * 2ull, wb = (unsigned long long)F * K * 2ull;
-    if (!fits31(ab) || !fits31(wb)) return SIDLSG_EINVAL;
-    p.a_bytes = (unsigned)ab; p.w_bytes = (unsigned)wb;
-    SidlsgTraceScope ts(SIDLSG_FAM_GEMM, 2.0 * M * (double)F * K, 2.0 * ((double)M * K + 2.0 * (double)F * K + 4.0 * (double)M * F));
-    if (p8_geglu_takes(p)) return launch_gemm_p8_geglu<2>(p, (hipStream_t)stream);
-    return launch_gemm_v3<0>(p, (hipStream_t)stream);
-}
-
-// Grouped 3x3 convolution: samples [0, B/2) use (W, bias), samples [B/2, B) use (W1, bias1) (B even).
-int sidlsg_conv3x3_bf16_g2(const void* X, int ldx, const void* W, const void* W1, void* Y, int ldc, const float* bias, const float* bias1,
-                           const void* res, int ldres, const float* rowvec, int ld_rowvec, int B, int H, int Wd, int Cin, int Cout,
-                           int stride, int ups, float alpha, int flags, void* stream) {
-    if (stride != 1 && stride != 2) return SIDLSG_EINVAL;
-    if ((Cin & 7) || !W1 || (B & 1) || (bias != nullptr) != (bias1 != nullptr)) return SIDLSG_EINVAL;
-    if (ups && ((H | Wd) & 1)) return SIDLSG_EINVAL;
-    GemmParams p{};
-    p.A = (const bf16*)X; p.W = (const bf16*)W; p.C = Y; p.bias = bias; p.res = (const bf16*)res; p.rowvec = rowvec;
-    p.W1 = (const bf16*)W1; p.bias1 = bias1;
-    p.ldrv = ld_rowvec > 0 ? ld_rowvec : Cout;
-    p.H = H; p.Wd = Wd; p.Cin = Cin; p.stride = stride; p.ups = ups;
-    p.Ho = (H + 2 - 3) / stride + 1; p.Wo = (Wd + 2 - 3) / stride + 1;
-    p.M = B * p.Ho * p.Wo; p.N = Cout; p.K = 9 * Cin; p.lda = ldx; p.ldc = ldc; p.ldres = ldres;
-    p.Mg = p.M / 2;
-    p.rows_per_batch = p.Ho * p.Wo; p.alpha = alpha; p.flags = flags;
-    if (int e = check_common(p)) return e;
-    const int Hs = ups ? H / 2 : H, Ws = ups ? Wd / 2 : Wd;
-    const unsigned long long ab = (((unsigned long long)B * Hs * Ws - 1) * ldx + Cin) * 2ull, wb = (unsigned long long)Cout * 9 * Cin * 2ull;
-    if (!fits31(ab) || !fits31(wb)) return SIDLSG_EINVAL;
-    p.a_bytes = (unsigned)ab; p.w_bytes = (unsigned)wb;
-    if (Cin % 64 == 0) return dispatch_gemm<1>(p, (hipStream_t)stream);
-    return dispatch_gemm<2>(p, (hipStream_t)stream);
+    return gemm_geglu_bwd_impl(true, dOut, lda, Wt, Wt1, H, dH, ldh, M, F, K, stream);
 }
 
 // Implicit-GEMM 3x3 convolution, pad 1, NHWC.  X: [B][Hs][Ws][ldx] (ldx >= Cin, pixel stride),
 // W: [Cout][3][3][Cin], Y: [B][Ho][Wo][ldc].  `ups`=1 reads X through a nearest x2 upsample
 // (virtual input H x Wd = 2Hs x 2Ws).  stride in {1,2}.
+static int conv3x3_bf16_impl(bool g2, const void* X, int ldx, const void* W, const void* W1, void* Y, int ldc, const float* bias, const float* bias1,
+                             const void* res, int ldres, const float* rowvec, int ld_rowvec, int B, int H, int Wd, int Cin, int Cout, int stride,
+                             int ups, float alpha, int flags, void* stream) {
+    if ((stride != 1 && stride != 2) || (Cin & 7) || (ups && ((H | Wd) & 1))) return SIDLSG_EINVAL;
+    if (g2 && !group2_args_ok(B, W1, bias, bias1)) return SIDLSG_EINVAL;
+    GemmParams p = conv_params(X, ldx, W, Y, ldc, bias, res, ldres, rowvec, ld_rowvec, B, H, Wd, Cin, Cout, stride, ups, alpha, flags);
+    if (int e = check_common(p)) return e;
+    if (!range31(p.a_bytes, conv_src_pixels(B, H, Wd, ups), ldx, Cin, 2) || !range31(p.w_bytes, 9ull * Cout, Cin, Cin, 2)) return SIDLSG_EINVAL;
+    set_group2(p, g2, W1, nullptr, bias1);
+    if (Cin % 64 == 0) return dispatch_gemm<1>(p, (hipStream_t)stream);
+    return dispatch_gemm<2>(p, (hipStream_t)stream);
+}
 int sidlsg_conv3x3_bf16(const void* X, int ldx, const void* W, void* Y, int ldc, const float* bias, const void* res,
                         int ldres, const float* rowvec, int ld_rowvec, int B, int H, int Wd, int Cin, int Cout, int stride,
                         int ups, float alpha, int flags, void* stream) {
-    if (stride != 1 && stride != 2) return SIDLSG_EINVAL;
-    if (Cin & 7) return SIDLSG_EINVAL;
-    if (ups && ((H | Wd) & 1)) return SIDLSG_EINVAL;
-    GemmParams p{};
-    p.A = (const bf16*)X; p.W = (const bf16*)W; p.C = Y; p.bias = bias; p.res = (const bf16*)res; p.rowvec = rowvec;
-    p.ldrv = ld_rowvec > 0 ? ld_rowvec : Cout;
-    p.H = H; p.Wd = Wd; p.Cin = Cin; p.stride = stride; p.ups = ups;
-    p.Ho = (H + 2 - 3) / stride + 1; p.Wo = (Wd + 2 - 3) / stride + 1;
-    p.M = B * p.Ho * p.Wo; p.N = Cout; p.K = 9 * Cin; p.lda = ldx; p.ldc = ldc; p.ldres = ldres;
-    p.rows_per_batch = p.Ho * p.Wo; p.alpha = alpha; p.flags = flags;
-    if (int e = check_common(p)) return e;
-    const int Hs = ups ? H / 2 : H, Ws = ups ? Wd / 2 : Wd;
-    const unsigned long long ab = (((unsigned long long)B * Hs * Ws - 1) * ldx + Cin) * 2ull, wb = (unsigned long long)Cout * 9 * Cin * 2ull;
-    if (!fits31(ab) || !fits31(wb)) return SIDLSG_EINVAL;
-    p.a_bytes = (unsigned)ab; p.w_bytes = (unsigned)wb;
-    if (Cin % 64 == 0) return dispatch_gemm<1>(p, (hipStream_t)stream);
-    return dispatch_gemm<2>(p, (hipStream_t)stream);
+    return conv3x3_bf16_impl(false, X, ldx, W, nullptr, Y, ldc, bias, nullptr, res, ldres, rowvec, ld_rowvec, B, H, Wd, Cin, Cout, stride, ups, alpha,
+                             flags, stream);
+}
+// Grouped 3x3 convolution: samples [0, B/2) use (W, bias), samples [B/2, B) use (W1, bias1) (B even).
+int sidlsg_conv3x3_bf16_g2(const void* X, int ldx, const void* W, const void* W1, void* Y, int ldc, const float* bias, const float* bias1,
+                           const void* res, int ldres, const float* rowvec, int ld_rowvec, int B, int H, int Wd, int Cin, int Cout,
+                           int stride, int ups, float alpha, int flags, void* stream) {
+    return conv3x3_bf16_impl(true, X, ldx, W, W1, Y, ldc, bias, bias1, res, ldres, rowvec, ld_rowvec, B, H, Wd, Cin, Cout, stride, ups, alpha, flags,
+                             stream);
 }
 
 // diffusers Downsample2D(padding = 0) of the AutoencoderKL encoder: F.pad(x, (0, 1, 0, 1)) then conv2d(k = 3, stride 2, no padding), i.e.
@@ -2988,19 +2971,11 @@ int sidlsg_conv3x3_bf16(const void* X, int ldx, const void* W, void* Y, int ldc,
 int sidlsg_conv3x3_br_bf16(const void* X, int ldx, const void* W, void* Y, int ldc, const float* bias, int B, int H, int Wd, int Cin, int Cout,
                            int flags, void* stream) {
     if (B <= 0 || H <= 0 || Wd <= 0 || ((H | Wd) & 1) || (Cin & 7) || (flags & ~(F_OUT_F32 | F_SILU))) return SIDLSG_EINVAL;
-    GemmParams p{};
-    p.A = (const bf16*)X; p.W = (const bf16*)W; p.C = Y; p.bias = bias;
-    p.ldrv = Cout;
-    p.H = H; p.Wd = Wd; p.Cin = Cin; p.stride = 2; p.ups = 0;
-    p.Ho = H / 2; p.Wo = Wd / 2;
-    p.M = B * p.Ho * p.Wo; p.N = Cout; p.K = 9 * Cin; p.lda = ldx; p.ldc = ldc;
+    GemmParams p = conv_params(X, ldx, W, Y, ldc, bias, nullptr, 0, nullptr, 0, B, H, Wd, Cin, Cout, 2, 0, 1.0f, flags);      // Ho = H / 2, Wo = Wd / 2
     p.Mtot = p.M;
-    p.rows_per_batch = p.Ho * p.Wo; p.alpha = 1.0f; p.flags = flags;
     if (int e = check_common(p)) return e;
     if (ldx < Cin || ldc < Cout) return SIDLSG_EINVAL;
-    const unsigned long long ab = (((unsigned long long)B * H * Wd - 1) * ldx + Cin) * 2ull, wb = (unsigned long long)Cout * 9 * Cin * 2ull;
-    if (!fits31(ab) || !fits31(wb)) return SIDLSG_EINVAL;
-    p.a_bytes = (unsigned)ab; p.w_bytes = (unsigned)wb;
+    if (!range31(p.a_bytes, conv_src_pixels(B, H, Wd, 0), ldx, Cin, 2) || !range31(p.w_bytes, 9ull * Cout, Cin, Cin, 2)) return SIDLSG_EINVAL;
     SidlsgTraceScope ts(SIDLSG_FAM_CONV, 2.0 * p.M * (double)p.N * p.K,
                         2.0 * ((double)B * H * Wd * Cin + (double)p.N * p.K + (double)p.M * p.N * ((flags & F_OUT_F32) ? 2 : 1)));
     // 128 x 128 tiles once they cover the chip (>= 384: the rule of dispatch_gemm), 64 x 64 below
@@ -3015,9 +2990,7 @@ static int wgrad_dense_impl(const void* dY, int ldy, const void* A, int lda, flo
     if (M <= 0 || N <= 0 || K <= 0 || (K & 7) || (lda & 7) || !dY || !A || !dW) return SIDLSG_EINVAL;
     WgradParams p{};
     p.dY = (const bf16*)dY; p.A = (const bf16*)A; p.dW = dW; p.dB = dBias; p.M = M; p.N = N; p.K = K; p.ldy = ldy; p.lda = lda; p.assign = assign;
-    const unsigned long long ab = ((unsigned long long)(M - 1) * lda + K) * 2ull, yb = ((unsigned long long)(M - 1) * ldy + N) * 2ull;
-    if (!fits31(ab) || !fits31(yb)) return SIDLSG_EINVAL;
-    p.a_bytes = (unsigned)ab; p.y_bytes = (unsigned)yb;
+    if (!range31(p.a_bytes, M, lda, K, 2) || !range31(p.y_bytes, M, ldy, N, 2)) return SIDLSG_EINVAL;
     SidlsgTraceScope ts(SIDLSG_FAM_WGRAD, 2.0 * M * (double)N * K, 2.0 * ((double)M * N + (double)M * K) + (assign ? 4.0 : 8.0) * N * K);      // dY, A read once; dW (read +) written (fp32)
     return launch_wgrad<0>(p, (hipStream_t)stream);
 }
@@ -3049,9 +3022,7 @@ static int wgrad_group_impl(const void* jobs, int njobs, void* stream, bool t160
         WgradParams p{};
         p.dY = (const bf16*)q.dY; p.A = (const bf16*)q.A; p.dW = q.dW; p.dB = q.dBias; p.M = q.M; p.N = q.N; p.K = q.K; p.ldy = q.ldy; p.lda = q.lda;
         p.assign = q.assign;
-        const unsigned long long ab = ((unsigned long long)(q.M - 1) * q.lda + q.K) * 2ull, yb = ((unsigned long long)(q.M - 1) * q.ldy + q.N) * 2ull;
-        if (!fits31(ab) || !fits31(yb)) return SIDLSG_EINVAL;
-        p.a_bytes = (unsigned)ab; p.y_bytes = (unsigned)yb;
+        if (!range31(p.a_bytes, q.M, q.lda, q.K, 2) || !range31(p.y_bytes, q.M, q.ldy, q.N, 2)) return SIDLSG_EINVAL;
         ps[i] = p;
         flop += 2.0 * q.M * (double)q.N * q.K;
         bytes += 2.0 * ((double)q.M * q.N + (double)q.M * q.K) + (q.assign ? 4.0 : 8.0) * q.N * q.K;
@@ -3075,9 +3046,7 @@ static int wgrad_conv_impl(const void* dY, int ldy, const void* X, int ldx, floa
     p.Ho = (H + 2 - 3) / stride + 1; p.Wo = (Wd + 2 - 3) / stride + 1;
     p.M = B * p.Ho * p.Wo; p.N = Cout; p.K = 9 * Cin;
     const int Hs = ups ? H / 2 : H, Ws = ups ? Wd / 2 : Wd;
-    const unsigned long long ab = (((unsigned long long)B * Hs * Ws - 1) * ldx + Cin) * 2ull, yb = ((unsigned long long)(p.M - 1) * ldy + Cout) * 2ull;
-    if (!fits31(ab) || !fits31(yb)) return SIDLSG_EINVAL;
-    p.a_bytes = (unsigned)ab; p.y_bytes = (unsigned)yb;
+    if (!range31(p.a_bytes, conv_src_pixels(B, H, Wd, ups), ldx, Cin, 2) || !range31(p.y_bytes, p.M, ldy, Cout, 2)) return SIDLSG_EINVAL;
     SidlsgTraceScope ts(SIDLSG_FAM_CONV_WGRAD, 2.0 * p.M * (double)p.N * p.K,
                         2.0 * ((double)p.M * p.N + (double)B * Hs * Ws * Cin) + (assign ? 4.0 : 8.0) * p.N * p.K);
     return launch_wgrad<1>(p, (hipStream_t)stream);
@@ -3099,30 +3068,15 @@ int sidlsg_quantize_fp8_rows(const void* src_bf16, void* dst_fp8, float* scale, 
     return sidlsg_last_error();
 }
 
-// The grouped forms (sidlsg_*_g2, include/sidlsg_hip.h "grouped launches"): a second set (W8_1, wscale1, bias1) for the rows / samples of the
-// second half; g2 = false: the ordinary launch (Mg = 0), exactly as before the grouped forms existed.
-static void set_group2(GemmParams& p, bool g2, const void* W8_1, const float* wscale1, const float* bias1) {
-    if (!g2) return;
-    p.W1 = (const bf16*)W8_1; p.wscale1 = wscale1; p.bias1 = bias1; p.Mg = p.M / 2;
-}
-static bool group2_args_ok(int rows, const void* W8_1, const float* wscale1, const float* bias, const float* bias1) {
-    return W8_1 && wscale1 && !(rows & 1) && (bias != nullptr) == (bias1 != nullptr);
-}
-
 static int gemm_fp8w_impl(bool g2, const void* A, int lda, const void* W8, const float* wscale, const void* W8_1, const float* wscale1, void* C,
                           int ldc, const float* bias, const float* bias1, const void* res, int ldres, const float* rowvec, int ld_rowvec,
                           int rows_per_batch, int M, int N, int K, float alpha, int flags, void* stream) {
-    if (g2 && !group2_args_ok(M, W8_1, wscale1, bias, bias1)) return SIDLSG_EINVAL;
-    GemmParams p{};
-    p.A = (const bf16*)A; p.W = (const bf16*)W8; p.wscale = wscale; p.C = C; p.bias = bias; p.res = (const bf16*)res; p.rowvec = rowvec;
-    p.ldrv = ld_rowvec > 0 ? ld_rowvec : N;
-    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldc = ldc; p.ldres = ldres; p.rows_per_batch = rows_per_batch;
-    p.alpha = alpha; p.flags = flags;
+    if (g2 && (!wscale1 || !group2_args_ok(M, W8_1, bias, bias1))) return SIDLSG_EINVAL;
+    GemmParams p = dense_params(A, lda, W8, C, ldc, bias, res, ldres, rowvec, ld_rowvec, rows_per_batch, M, N, K, alpha, flags);
+    p.wscale = wscale;
     if (int e = check_common(p)) return e;
     if ((K & 15) || !wscale) return SIDLSG_EINVAL;
-    const unsigned long long ab = ((unsigned long long)(M - 1) * lda + K) * 2ull, wb = (unsigned long long)N * K;
-    if (!fits31(ab) || !fits31(wb)) return SIDLSG_EINVAL;
-    p.a_bytes = (unsigned)ab; p.w_bytes = (unsigned)wb;
+    if (!range31(p.a_bytes, M, lda, K, 2) || !range31(p.w_bytes, N, K, K, 1)) return SIDLSG_EINVAL;
     set_group2(p, g2, W8_1, wscale1, bias1);
     const int tiles = m_tiles_rt(p, F8_T) * ((N + F8_T - 1) / F8_T);
     SIDLSG_LAUNCH((gemm_fp8w_kernel<0>), dim3(tiles), dim3(NTHREADS), 0, (hipStream_t)stream, p);
@@ -3144,19 +3098,14 @@ int sidlsg_gemm_fp8w_g2(const void* A, int lda, const void* W8, const float* wsc
 static int gemm_mx8_impl(bool g2, const void* A8, int lda, const void* W8, const float* wscale, const void* W8_1, const float* wscale1, void* C,
                          int ldc, const float* bias, const float* bias1, const void* res, int ldres, const float* rowvec, int ld_rowvec,
                          int rows_per_batch, int M, int N, int K, float alpha, int flags, void* stream) {
-    if (g2 && !group2_args_ok(M, W8_1, wscale1, bias, bias1)) return SIDLSG_EINVAL;
-    GemmParams p{};
-    p.A = (const bf16*)A8; p.W = (const bf16*)W8; p.wscale = wscale; p.C = C; p.bias = bias; p.res = (const bf16*)res; p.rowvec = rowvec;
-    p.ldrv = ld_rowvec > 0 ? ld_rowvec : N;
-    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldc = ldc; p.ldres = ldres; p.rows_per_batch = rows_per_batch;
-    p.alpha = alpha; p.flags = flags;
+    if (g2 && (!wscale1 || !group2_args_ok(M, W8_1, bias, bias1))) return SIDLSG_EINVAL;
     if (M <= 0 || N <= 0 || K <= 0 || !A8 || !W8 || !C || !wscale) return SIDLSG_EINVAL;
     if ((K & 15) || (lda & 15) || (N % 160) || lda < K) return SIDLSG_EINVAL;
     if (rowvec && rows_per_batch <= 0) return SIDLSG_EINVAL;
     if ((flags & F_ACCUM) && !(flags & F_OUT_F32)) return SIDLSG_EINVAL;
-    const unsigned long long ab = (unsigned long long)(M - 1) * lda + K, wb = (unsigned long long)N * K;
-    if (!fits31(ab) || !fits31(wb)) return SIDLSG_EINVAL;
-    p.a_bytes = (unsigned)ab; p.w_bytes = (unsigned)wb;
+    GemmParams p = dense_params(A8, lda, W8, C, ldc, bias, res, ldres, rowvec, ld_rowvec, rows_per_batch, M, N, K, alpha, flags);
+    p.wscale = wscale;
+    if (!range31(p.a_bytes, M, lda, K, 1) || !range31(p.w_bytes, N, K, K, 1)) return SIDLSG_EINVAL;      // extents in bytes of e4m3
     set_group2(p, g2, W8_1, wscale1, bias1);
     SidlsgTraceScope ts(SIDLSG_FAM_GEMM, 2.0 * p.M * (double)p.N * p.K);
     return launch_gemm_mx8<0>(p, (hipStream_t)stream);
@@ -3177,20 +3126,15 @@ int sidlsg_gemm_mx8_g2(const void* A8, int lda, const void* W8, const float* wsc
 static int conv3x3_mx8_impl(bool g2, const void* X8, int ldx, const void* W8, const float* wscale, const void* W8_1, const float* wscale1,
                             void* Y, int ldc, const float* bias, const float* bias1, const void* res, int ldres, const float* rowvec,
                             int ld_rowvec, int B, int H, int Wd, int Cin, int Cout, float alpha, int flags, void* stream) {
-    if (g2 && !group2_args_ok(B, W8_1, wscale1, bias, bias1)) return SIDLSG_EINVAL;
+    if (g2 && (!wscale1 || !group2_args_ok(B, W8_1, bias, bias1))) return SIDLSG_EINVAL;
     if (B <= 0 || H <= 0 || Wd <= 0 || Cin <= 0 || Cout <= 0 || !X8 || !W8 || !Y || !wscale) return SIDLSG_EINVAL;
     if ((Cin & 15) || (ldx & 15) || (Cout % 160) || ldx < Cin) return SIDLSG_EINVAL;
     if ((flags & F_ACCUM) && !(flags & F_OUT_F32)) return SIDLSG_EINVAL;
-    GemmParams p{};
-    p.A = (const bf16*)X8; p.W = (const bf16*)W8; p.wscale = wscale; p.C = Y; p.bias = bias; p.res = (const bf16*)res; p.rowvec = rowvec;
-    p.ldrv = ld_rowvec > 0 ? ld_rowvec : Cout;
-    p.M = B * H * Wd; p.N = Cout; p.K = 9 * Cin; p.lda = ldx; p.ldc = ldc; p.ldres = ldres; p.rows_per_batch = H * Wd;
-    p.H = H; p.Wd = Wd; p.Cin = Cin; p.Ho = H; p.Wo = Wd; p.stride = 1; p.ups = 0;
-    p.alpha = alpha; p.flags = flags;
-    const unsigned long long ab = ((unsigned long long)B * H * Wd - 1) * ldx + Cin + (unsigned long long)(Wd + 1) * ldx;
-    const unsigned long long wb = (unsigned long long)Cout * 9 * Cin;
-    if (!fits31(ab) || !fits31(wb)) return SIDLSG_EINVAL;
-    p.a_bytes = (unsigned)(ab - (unsigned long long)(Wd + 1) * ldx); p.w_bytes = (unsigned)wb;
+    GemmParams p = conv_params(X8, ldx, W8, Y, ldc, bias, res, ldres, rowvec, ld_rowvec, B, H, Wd, Cin, Cout, 1, 0, alpha, flags);
+    p.wscale = wscale;
+    // the tap offsets reach (Wd + 1) pixels past a row's own: the check counts them, the descriptor range does not
+    if (!range31(p.a_bytes, conv_src_pixels(B, H, Wd, 0), ldx, Cin, 1, (unsigned long long)(Wd + 1) * ldx) || !range31(p.w_bytes, 9ull * Cout, Cin, Cin, 1))
+        return SIDLSG_EINVAL;
     set_group2(p, g2, W8_1, wscale1, bias1);
     SidlsgTraceScope ts(SIDLSG_FAM_CONV, 2.0 * p.M * (double)p.N * p.K);
     return launch_gemm_mx8<1>(p, (hipStream_t)stream);
@@ -3229,21 +3173,13 @@ static int conv3x3_fp8w_impl(bool g2, const void* X, int ldx, const void* W8, co
                              void* Y, int ldc, const float* bias, const float* bias1, const void* res, int ldres, const float* rowvec,
                              int ld_rowvec, int B, int H, int Wd, int Cin, int Cout, int stride, int ups, float alpha, int flags,
                              void* stream) {
-    if (g2 && !group2_args_ok(B, W8_1, wscale1, bias, bias1)) return SIDLSG_EINVAL;
+    if (g2 && (!wscale1 || !group2_args_ok(B, W8_1, bias, bias1))) return SIDLSG_EINVAL;
     if ((stride != 1 && stride != 2) || (Cin & 15) || !wscale) return SIDLSG_EINVAL;
     if (ups && ((H | Wd) & 1)) return SIDLSG_EINVAL;
-    GemmParams p{};
-    p.A = (const bf16*)X; p.W = (const bf16*)W8; p.wscale = wscale; p.C = Y; p.bias = bias; p.res = (const bf16*)res; p.rowvec = rowvec;
-    p.ldrv = ld_rowvec > 0 ? ld_rowvec : Cout;
-    p.H = H; p.Wd = Wd; p.Cin = Cin; p.stride = stride; p.ups = ups;
-    p.Ho = (H + 2 - 3) / stride + 1; p.Wo = (Wd + 2 - 3) / stride + 1;
-    p.M = B * p.Ho * p.Wo; p.N = Cout; p.K = 9 * Cin; p.lda = ldx; p.ldc = ldc; p.ldres = ldres;
-    p.rows_per_batch = p.Ho * p.Wo; p.alpha = alpha; p.flags = flags;
+    GemmParams p = conv_params(X, ldx, W8, Y, ldc, bias, res, ldres, rowvec, ld_rowvec, B, H, Wd, Cin, Cout, stride, ups, alpha, flags);
+    p.wscale = wscale;
     if (int e = check_common(p)) return e;
-    const int Hs = ups ? H / 2 : H, Wss = ups ? Wd / 2 : Wd;
-    const unsigned long long ab = (((unsigned long long)B * Hs * Wss - 1) * ldx + Cin) * 2ull, wb = (unsigned long long)Cout * 9 * Cin;
-    if (!fits31(ab) || !fits31(wb)) return SIDLSG_EINVAL;
-    p.a_bytes = (unsigned)ab; p.w_bytes = (unsigned)wb;
+    if (!range31(p.a_bytes, conv_src_pixels(B, H, Wd, ups), ldx, Cin, 2) || !range31(p.w_bytes, 9ull * Cout, Cin, Cin, 1)) return SIDLSG_EINVAL;
     set_group2(p, g2, W8_1, wscale1, bias1);
     const int tiles = m_tiles_rt(p, F8_T) * ((p.N + F8_T - 1) / F8_T);
     SIDLSG_LAUNCH((gemm_fp8w_kernel<2>), dim3(tiles), dim3(NTHREADS), 0, (hipStream_t)stream, p);

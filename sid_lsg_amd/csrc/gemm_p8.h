@@ -671,9 +671,6 @@ static int launch_gemm_p8(const GemmParams& p, hipStream_t s) {
     GemmParams q = p;
     q.group_m = 4;
     SIDLSG_LAUNCH(kern, dim3(tiles * splits), dim3(G::NTH), (size_t)G::LDS_BYTES, s, q);
-    if (p.kt_per_split) {
-        const size_t n4 = ((size_t)p.M * p.N + 3) / 4;
-        SIDLSG_LAUNCH(gemm_finish_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, p, splits);
-    }
+    if (p.kt_per_split) launch_gemm_finish(p, splits, s);
     return sidlsg_last_error();
 }
