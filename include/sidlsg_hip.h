@@ -373,6 +373,26 @@ int sidlsg_pr_distances(const void* rows, int R, const void* cols, int C, int F,
 int sidlsg_pr_kth_radius(const void* manifold, int N, int F, int k, void* radius_out, void* stream);
 int sidlsg_pr_member(const void* probes, int P, const void* manifold, int N, int F, const void* radius, void* inside_out, void* stream);
 
+/* ---- KID / CMMD (kernel two-sample statistics): fp32 Gram tiles on the f32 MFMA, kernel values summed in fp64 ------------------
+ * X, Y: [n][F] fp32 row-major, F a positive multiple of 4 (pad with zero columns on the host), 16-byte aligned.  Subset s uses the
+ * rows X[ix[s][i]], i < mx, and Y[iy[s][j]], j < my (ix: int32 [S][mx], iy: [S][my], indices trusted to be in range); both lists
+ * NULL = the rows 0..n-1 in order, then S = 1, mx = nx, my = ny.  No gathered copy and no N x N matrix is formed.
+ * out[s] = {Sxx, Syy, Sxy, Txx, Tyy} (doubles): S** = the sum of v over ALL ordered pairs of the two row lists, the diagonal
+ * included; T** = the sum over i == j of the symmetric passes.  With g = a . b on v_mfma_f32_16x16x4_f32 (an exact fp32 fma chain
+ * over k, in the same order for every pair and for the norms), in fp32:
+ *   kind 0 (polynomial):  v = t * t * t,  t = fma(p0, g, p1)
+ *   kind 1 (RBF):         d2 = max(fma(-2, g, |a|^2 + |b|^2), 0),  v = -expm1f(-(p0 * d2))  = 1 - exp(-p0 d2), the COMPLEMENT of the
+ *                         kernel value (full relative precision where the kernel is close to 1).  A row against itself or a
+ *                         bit-identical duplicate gives d2 = 0 and v = 0 exactly.
+ * Each v is converted to double; one double per 128 x 128 tile and quantity goes to ws, and a second launch adds the slots of a
+ * subset in a fixed order: no atomics, the same inputs give the same bits on every run.  ws: sidlsg_pair_kernel_sums_ws_doubles(S,
+ * mx, my) doubles (a host query; negative for sizes the entry point rejects).
+ * SIDLSG_EINVAL, and no launch, for null or misaligned pointers, F % 4 != 0, S < 1 or > 65535, mx or my < 1, n, mx or my > 2^24,
+ * F > 2^20, an index list on one side only, no lists with S != 1 or m != n, kind outside {0, 1}, or a workspace of 2^31 doubles or more. */
+int sidlsg_pair_kernel_sums_ws_doubles(int S, int mx, int my);
+int sidlsg_pair_kernel_sums(const float* X, int nx, const float* Y, int ny, int F, const int* ix, const int* iy, int S, int mx, int my,
+                            int kind, float p0, float p1, double* out, double* ws, void* stream);
+
 /* ---- snapshot preview grids (save_image_grid, sid_training_loop.py:99-115, 597-614) -------------------------------------
  * B decoded fp32 images -> their tiles of ONE uint8 grid image [gh*H][gw*W][3] (HWC, what a PNG writer takes): image i goes to
  * tile first + i, row (first + i) / gw, column (first + i) % gw, so the batches of a grid are placed as they leave the decoder and

@@ -48,6 +48,9 @@ CLIP_ARCHS = {
     'vit-l-14': dict(projection_dim=768,            # openai/clip-vit-large-patch14
                      vision_config=dict(_V, hidden_size=1024, intermediate_size=4096, num_hidden_layers=24, num_attention_heads=16),
                      text_config=dict(_T, hidden_size=768, intermediate_size=3072, num_hidden_layers=12, num_attention_heads=12)),
+    'vit-l-14-336': dict(projection_dim=768,        # openai/clip-vit-large-patch14-336, the image tower of the published CMMD
+                         vision_config=dict(_V, hidden_size=1024, intermediate_size=4096, num_hidden_layers=24, num_attention_heads=16, image_size=336),
+                         text_config=dict(_T, hidden_size=768, intermediate_size=3072, num_hidden_layers=12, num_attention_heads=12)),
     'vit-g-14': dict(projection_dim=1024,           # laion/CLIP-ViT-g-14-laion2B-s12B-b42K (what the reference's clip_score.py builds)
                      vision_config=dict(_V, hidden_size=1408, intermediate_size=6144, num_hidden_layers=40, num_attention_heads=16, hidden_act='gelu'),
                      text_config=dict(_T, hidden_size=1024, intermediate_size=4096, num_hidden_layers=24, num_attention_heads=16, hidden_act='gelu')),

@@ -1,4 +1,4 @@
-"""Evaluation metrics of the distilled generator: FID, CLIP scores, precision / recall and HPSv2.
+"""Evaluation metrics of the distilled generator: FID, CLIP scores, precision / recall, HPSv2, KID and CMMD.
 
 Reference: metrics/sid_metric_main.py:25-123 (registry, `calc_metric`, `report_metric`, the `fid30k_full` /
 `fid_clip_30k_full` / `fid_test` / `fid_clip_test` entries), metrics/sid_fid_and_clip.py:32-74 (the Frechet distance between
@@ -25,7 +25,9 @@ What is different here (not a translation):
     reductions inside the fp16 MFMA distance contraction, so no N x N matrix is formed, let alone copied to the host as the
     reference does.  The distance is computed to fp32 accuracy and rounded to fp16 once; the reference's fp16 `cdist` is not
     correctly rounded, so single distances differ by an fp16 ulp (tests/test_gpu_pr.py pins what follows from that).
-Only the precision / recall kernels are hot; the rest is host logic.
+  * KID and CMMD are not in the reference: both are sums of a kernel function over all pairs of feature vectors, formed by
+    `ops.pair_kernel_sums` (fp32 operands on the MFMA, fp64 sums in a fixed order, no N x N matrix); see the section above the registry.
+Only the precision / recall and pair-sum kernels are hot; the rest is host logic.
 """
 import json
 import os
@@ -349,8 +351,9 @@ class MetricOptions:
     def __init__(self, G, prompts=None, resolution=512, init_timestep=625, detector=None, real_stats=None, open_clip_detector=None,
                  clip_score_fn=None, device=None, seed=0, batch_gen=4, detector_size=256, progress=None, dataset_kwargs=None,
                  dataset=None, run_dir=None, metric_clip_path=None, metric_hps_path=None, hps_prompts=None, hps_arch=None, hps_tokenizer=None,
-                 hps_detector=None):
+                 hps_detector=None, metric_cmmd_clip_path=None):
         from .dnnlib_util import construct_class_by_name
+        self.metric_cmmd_clip_path = metric_cmmd_clip_path      # --metric_cmmd_clip_path: the CLIP image tower behind `cmmd*`
         self.run_dir = run_dir
         if dataset is None and dataset_kwargs:
             dataset = construct_class_by_name(**dataset_kwargs)
@@ -452,7 +455,8 @@ def generator_feature_stats(opts, num_gen, compute_clip=False, capture_all=False
         img = (img * 127.5 + 128).clamp(0, 255).to(torch.uint8)
         if img.shape[1] == 1:
             img = img.repeat(1, 3, 1, 1)
-        img = resize_for_detector(img, opts.detector_size)
+        if opts.detector_size is not None:      # None: the detector resamples the images itself (compute_cmmd)
+            img = resize_for_detector(img, opts.detector_size)
         with torch.no_grad():
             stats.append(detector(img, return_features=True))
             if compute_clip:
@@ -536,6 +540,114 @@ def compute_pr(opts, max_real, num_gen, nhood_size):
         radius = ops.pr_kth_radius(manifold, k)
         results[name] = float(ops.pr_member(probes, manifold, radius).to(torch.float64).mean())       # the exact share: count / n
     return results['precision'], results['recall']
+
+
+# ------------------------------------------------------------------------------------------------
+# KID (Binkowski et al., "Demystifying MMD GANs"; `kid50k_full` of the StyleGAN2-ADA / StyleGAN3 metric registry) and CMMD
+# (Jayasumana et al. 2024, "Rethinking FID").  Both are three sums over all pairs of a kernel function of feature dot products,
+# which ops.pair_kernel_sums forms on the f32 MFMA and adds in fp64; the functions below are the arithmetic around those sums.
+# They restate the published formulas and are not pinned against those packages.
+KID_NUM_SUBSETS, KID_MAX_SUBSET_SIZE = 100, 1000
+CMMD_SIGMA, CMMD_SCALE = 10.0, 1000.0
+
+
+def kid_subsets(n_gen, n_real, num_subsets=KID_NUM_SUBSETS, max_subset_size=KID_MAX_SUBSET_SIZE, seed=0):
+    """(ix, iy) int32 [num_subsets, m], m = min(n_gen, n_real, max_subset_size): the rows of the generated and of the real features
+    each subset uses.  StyleGAN's kernel_inception_distance.py draws, per subset, `choice(n_gen, m, replace=False)` and then
+    `choice(n_real, m, replace=False)` from numpy's global generator; here from RandomState(seed), in that order."""
+    m = min(int(n_gen), int(n_real), int(max_subset_size))
+    if m < 1 or num_subsets < 1:
+        raise ValueError(f'kid_subsets: {n_gen} generated and {n_real} real features in {num_subsets} subsets of at most {max_subset_size}')
+    rnd = np.random.RandomState(seed)
+    ix = np.empty((num_subsets, m), dtype=np.int32)
+    iy = np.empty((num_subsets, m), dtype=np.int32)
+    for s in range(num_subsets):
+        ix[s] = rnd.choice(n_gen, m, replace=False)
+        iy[s] = rnd.choice(n_real, m, replace=False)
+    return ix, iy
+
+
+def kid_from_sums(sums, m):
+    """[S, 5] sums (Sxx, Syy, Sxy, Txx, Tyy) of the cubic kernel (x.y / F + 1)^3 over subsets of m rows -> KID, in fp64:
+    t_s = ((Sxx - Txx) + (Syy - Tyy)) / (m - 1) - 2 Sxy / m;  KID = mean_s(t_s) / m   (the unbiased estimator: no i == j pairs).
+    m = 1 leaves no pair i != j: NaN, the 0 / 0 of the published code (the one-sample `kid_test` of a smoke run)."""
+    if m < 2:
+        return float('nan')
+    s = np.asarray(sums, dtype=np.float64).reshape(-1, 5)
+    t = ((s[:, 0] - s[:, 3]) + (s[:, 1] - s[:, 4])) / (m - 1) - 2.0 * s[:, 2] / m
+    return float(t.mean() / m)
+
+
+def cmmd_from_sums(sums, nx, ny, scale=CMMD_SCALE):
+    """[5] (or [1, 5]) sums of 1 - k, k = exp(-|a - b|^2 / (2 sigma^2)), over all pairs, the diagonal included -> scale * MMD^2, in
+    fp64: mean(k_xx) + mean(k_yy) - 2 mean(k_xy) = 2 Sxy / (nx ny) - Sxx / nx^2 - Syy / ny^2  (the biased V-statistic of the
+    published CMMD code; the ones cancel exactly instead of in floating point)."""
+    s = np.asarray(sums, dtype=np.float64).reshape(-1)
+    return float(scale * (2.0 * s[2] / (float(nx) * float(ny)) - s[0] / float(nx) ** 2 - s[1] / float(ny) ** 2))
+
+
+def _features_f32(t, device):
+    return torch.as_tensor(t).to(device, torch.float32).contiguous()
+
+
+def kid_from_features(real, gen, num_subsets=KID_NUM_SUBSETS, max_subset_size=KID_MAX_SUBSET_SIZE, seed=0):
+    """KID between [n_real, F] and [n_gen, F] fp32 features on the device: the subsets are index lists read by one launch."""
+    from . import ops
+    ix, iy = kid_subsets(gen.shape[0], real.shape[0], num_subsets, max_subset_size, seed)
+    sums = ops.pair_kernel_sums(gen, real, ops.PAIR_KERNEL_POLY3, 1.0 / gen.shape[1], 1.0,
+                                torch.from_numpy(ix).to(gen.device), torch.from_numpy(iy).to(gen.device))
+    return kid_from_sums(sums.cpu().numpy(), ix.shape[1])
+
+
+def cmmd_from_features(real, gen, sigma=CMMD_SIGMA, scale=CMMD_SCALE):
+    """CMMD between [n_real, F] and [n_gen, F] fp32 (L2-normalised CLIP) embeddings on the device."""
+    from . import ops
+    sums = ops.pair_kernel_sums(real, gen, ops.PAIR_KERNEL_RBF, 1.0 / (2.0 * sigma * sigma))
+    return cmmd_from_sums(sums.cpu().numpy(), real.shape[0], gen.shape[0], scale)
+
+
+def compute_kid(opts, max_real, num_gen, num_subsets=KID_NUM_SUBSETS, max_subset_size=KID_MAX_SUBSET_SIZE):
+    """KID of `num_gen` generated images against the first `max_real` real ones: the Inception detector and the 256 x 256 resize of
+    FID, fp32 features kept on the device (as compute_pr keeps them).  Every rank holds all features and computes the same number."""
+    real = dataset_feature_stats(opts, max_items=max_real, capture_all=True).get_all_torch()
+    gen = generator_feature_stats(opts, num_gen, capture_all=True)[0].get_all_torch()
+    if min(real.shape[0], gen.shape[0]) < 2:
+        dist.print0(f'WARNING: KID: {real.shape[0]} real and {gen.shape[0]} generated features: subsets of one feature have no pair, the result is NaN')
+    return kid_from_features(_features_f32(real, opts.device), _features_f32(gen, opts.device), num_subsets, max_subset_size)
+
+
+class ClipEmbeddingDetector:
+    """The image tower of a CLIP model with the detector call contract: uint8 images of any size -> F.normalize(image_embeds), fp32.
+    The tower resamples H x W to its own R x R without a crop (preprocess='interpolate'), as the published CMMD code does."""
+
+    def __init__(self, path, device):
+        from .clip import load_clip
+        self.vision = load_clip(path, device, preprocess='interpolate').vision
+
+    def __call__(self, images_u8, return_features=True):
+        with torch.no_grad():
+            return torch.nn.functional.normalize(self.vision(images_u8).float(), dim=-1)
+
+
+def cmmd_options(opts):
+    """`opts` with the CMMD detector in place of the Inception one and no resize in front of it."""
+    import copy
+    if not opts.metric_cmmd_clip_path:
+        raise ValueError('cmmd needs --metric_cmmd_clip_path: a local CLIP directory in the Hugging Face layout (ViT-L/14-336 in the '
+                         'published CMMD) or random:clip-<arch>')
+    o = copy.copy(opts)
+    o.detector = ClipEmbeddingDetector(opts.metric_cmmd_clip_path, opts.device)
+    o.detector_size = None
+    return o
+
+
+def compute_cmmd(opts, max_real, num_gen):
+    """CMMD of `num_gen` generated images against the first `max_real` real ones: both through the same CLIP image tower, straight
+    from their own sizes (no 256 x 256 step).  Every rank holds all embeddings and computes the same number."""
+    o = cmmd_options(opts)
+    real = dataset_feature_stats(o, max_items=max_real, capture_all=True).get_all_torch()
+    gen = generator_feature_stats(o, num_gen, capture_all=True)[0].get_all_torch()
+    return cmmd_from_features(_features_f32(real, opts.device), _features_f32(gen, opts.device))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -638,8 +750,30 @@ def hpsv2_test(opts):
     return compute_hps(opts, 16)
 
 
-NEEDS_IMAGES = ('pr30k3_full', 'pr_test')      # metrics that read the real images themselves: --data_stat cannot stand in
+@register_metric
+def kid30k_full(opts):
+    return dict(kid30k_full=compute_kid(opts, max_real=None, num_gen=30000))
+
+
+@register_metric
+def kid_test(opts):
+    return dict(kid30k_full=compute_kid(opts, max_real=None, num_gen=max(1, getattr(opts, 'num_test', 1))))
+
+
+@register_metric
+def cmmd30k_full(opts):
+    return dict(cmmd30k_full=compute_cmmd(opts, max_real=None, num_gen=30000))
+
+
+@register_metric
+def cmmd_test(opts):
+    return dict(cmmd30k_full=compute_cmmd(opts, max_real=None, num_gen=max(1, getattr(opts, 'num_test', 1))))
+
+
+# metrics that read the real images themselves: --data_stat cannot stand in
+NEEDS_IMAGES = ('pr30k3_full', 'pr_test', 'kid30k_full', 'kid_test', 'cmmd30k_full', 'cmmd_test')
 HPS_METRICS = ('hpsv2', 'hpsv2_test')          # metrics that need neither the Inception detector nor real-set statistics
+CMMD_METRICS = ('cmmd30k_full', 'cmmd_test')   # likewise: the CLIP image tower of --metric_cmmd_clip_path and the real images
 
 
 def calc_metric(metric, **kwargs):

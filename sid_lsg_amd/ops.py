@@ -2196,6 +2196,56 @@ def pr_member(probes, manifold, radius):
     return out.bool()
 
 
+PAIR_KERNEL_POLY3, PAIR_KERNEL_RBF = 0, 1
+
+
+def pair_kernel_sums(x, y, kind, p0, p1=0.0, idx_x=None, idx_y=None):
+    """[S, 5] fp64 = (Sxx, Syy, Sxy, Txx, Tyy) per subset (sidlsg_pair_kernel_sums): the sums over all ordered pairs of rows, the
+    diagonal included (S), and over the pairs i == j of the symmetric passes (T), of
+        kind 0:  (p0 g + p1)^3                      g = a . b as an fp32 fma chain on the f32 MFMA
+        kind 1:  1 - exp(-p0 |a - b|^2)             the complement of the RBF kernel value
+    summed in fp64 in a fixed order.  x [nx, F], y [ny, F] fp32 (x may be y).  idx_x [S, mx], idx_y [S, my] int32: subset s uses the
+    rows x[idx_x[s]] and y[idx_y[s]] (both or neither; neither = every row in order, S = 1).  No [n, n] matrix and no gathered
+    copy is formed.  F is padded with zero columns to a multiple of 4 (zeros change neither a norm nor a dot product)."""
+    for t, name in ((x, 'x'), (y, 'y')):
+        _chk(t, F32)
+        if t.dim() != 2 or t.shape[0] == 0 or t.shape[1] == 0:
+            raise RuntimeError(f'pair_kernel_sums: {name}: expected a non-empty [n, F] feature matrix, got {tuple(t.shape)}')
+    if x.shape[1] != y.shape[1] or x.device != y.device:
+        raise RuntimeError(f'pair_kernel_sums: x {tuple(x.shape)} on {x.device} and y {tuple(y.shape)} on {y.device}: one feature width, one device')
+    if kind not in (PAIR_KERNEL_POLY3, PAIR_KERNEL_RBF):
+        raise RuntimeError(f'pair_kernel_sums: kind {kind!r}: expected 0 (polynomial) or 1 (RBF)')
+    if (idx_x is None) != (idx_y is None):
+        raise RuntimeError('pair_kernel_sums: index lists are given for both sides or for neither')
+    same = y is x
+    pad = -x.shape[1] % 4
+    if pad:
+        x = torch.nn.functional.pad(x, [0, pad])
+        y = x if same else torch.nn.functional.pad(y, [0, pad])
+    x = x.contiguous()
+    y = x if same else y.contiguous()
+    S, mx, my = 1, x.shape[0], y.shape[0]
+    if idx_x is not None:
+        for t, n, name in ((idx_x, x.shape[0], 'idx_x'), (idx_y, y.shape[0], 'idx_y')):
+            _chk(t, torch.int32)
+            if t.dim() != 2 or t.device != x.device:
+                raise RuntimeError(f'pair_kernel_sums: {name}: expected int32 [S, m] on {x.device}, got {tuple(t.shape)} on {t.device}')
+            if t.numel() and not bool(((t >= 0) & (t < n)).all()):
+                raise RuntimeError(f'pair_kernel_sums: {name} addresses rows outside 0 .. {n - 1}')
+        if idx_x.shape[0] != idx_y.shape[0]:
+            raise RuntimeError(f'pair_kernel_sums: {idx_x.shape[0]} subsets of x and {idx_y.shape[0]} of y')
+        idx_x, idx_y = idx_x.contiguous(), idx_y.contiguous()
+        S, mx, my = idx_x.shape[0], idx_x.shape[1], idx_y.shape[1]
+    nws = lib.sidlsg_pair_kernel_sums_ws_doubles.raw(S, mx, my)
+    if nws < 0:
+        raise RuntimeError(f'pair_kernel_sums: {S} subsets of {mx} x {my} rows: need 1 <= S <= 65535, 1 <= m <= 2^24 and a workspace below 2^31 doubles')
+    ws = torch.empty(nws, device=x.device, dtype=torch.float64)
+    out = torch.empty((S, 5), device=x.device, dtype=torch.float64)
+    lib.sidlsg_pair_kernel_sums(_p(x), x.shape[0], _p(y), y.shape[0], x.shape[1], _p(idx_x), _p(idx_y), S, mx, my, int(kind), float(p0), float(p1),
+                                _p(out), _p(ws), _s())
+    return out
+
+
 def _det_synced(backward):
     @functools.wraps(backward)
     def wrapper(*args):

@@ -102,6 +102,7 @@ OPTIONS = [
     (('--metric_clip_path',), dict(type=str, default=None, help='CLIP model behind clipscore30k: a local directory in the Hugging Face layout (config.json, model.safetensors, vocab.json, merges.txt)')),
     (('--metric_open_clip_path',), dict(type=str, default=None, help='CLIP model behind open_clipscore_30k: such a directory, or a pickled open_clip wrapper of the reference')),
     (('--metric_hps_path',), dict(type=str, default=None, metavar='FILE', help='Scorer behind hpsv2: HPS_v2_compressed.pt, or any checkpoint in open_clip\'s layout (.pt / .bin / .safetensors) (not a reference option)')),
+    (('--metric_cmmd_clip_path',), dict(type=str, default=None, metavar='DIR', help='CLIP model behind cmmd30k_full / cmmd_test (ViT-L/14-336 in the published CMMD): a local directory in the Hugging Face layout, or random:clip-<arch> (not a reference option)')),
     (('--hps_prompts',), dict(type=str, default=None, metavar='DIR', help='HPSv2 benchmark prompts: a directory with anime.json, concept-art.json, paintings.json, photo.json (not a reference option)')),
     (('--hps_arch',), dict(type=str, default=None, help='open_clip architecture of --metric_hps_path  [default: ViT-H-14] (not a reference option)')),
     (('--hps_tokenizer',), dict(type=str, default=None, metavar='DIR', help='vocab.json / merges.txt of the scorer  [default: <sd_model>/tokenizer] (not a reference option)')),
@@ -138,8 +139,9 @@ def build_config(o):
         needs_images = [m for m in o.metrics if m in _metrics.NEEDS_IMAGES]
         # --data_stat may be left out when the statistics can be computed from the images of --data
         hps = [m for m in o.metrics if m in _metrics.HPS_METRICS]      # scored by --metric_hps_path alone: no Inception file, no statistics
+        cmmd = [m for m in o.metrics if m in _metrics.CMMD_METRICS]    # scored by --metric_cmmd_clip_path and the real images: likewise
         need_stat = o.data_stat is not None or (len(needs_images) + len(hps) < len(o.metrics) and not has_images)
-        need_pt = len(hps) < len(o.metrics)
+        need_pt = len(hps) + len(cmmd) < len(o.metrics)
         for flag, path in ((('--metric_pt_path', o.metric_pt_path),) if need_pt else ()) + ((('--data_stat', o.data_stat),) if need_stat else ()):
             if not path or not os.path.isfile(path):
                 raise click.ClickException(f'--metrics needs {flag} to be a local file (got {path!r})')
@@ -148,6 +150,9 @@ def build_config(o):
                 raise click.ClickException(f'--metrics {",".join(hps)} needs --metric_hps_path to be a local file (got {o.get("metric_hps_path")!r})')
             if not o.get('hps_prompts') or not os.path.isdir(o.hps_prompts):
                 raise click.ClickException(f'--metrics {",".join(hps)} needs --hps_prompts to be a local directory (got {o.get("hps_prompts")!r})')
+        if cmmd and not _metrics.is_clip_spec(o.get('metric_cmmd_clip_path')):
+            raise click.ClickException(f'--metrics {",".join(cmmd)} needs --metric_cmmd_clip_path to be a local CLIP directory in the Hugging Face '
+                                       f'layout or random:clip-<arch> (got {o.get("metric_cmmd_clip_path")!r})')
         if needs_images and not has_images:
             raise click.ClickException(f'--metrics {",".join(needs_images)} read the real images: --data must be a directory of images '
                                        f'with .txt captions (got {o.data!r})')
@@ -200,7 +205,7 @@ def build_config(o):
              metric_open_clip_path=o.metric_open_clip_path, metric_clip_path=o.metric_clip_path)
     if o.get('text_encoder') is not None:      # (absent when not given: load_sd15 then decides, and the printed options stay as they were)
         c.text_encoder = o.text_encoder
-    for k in ('metric_hps_path', 'hps_prompts', 'hps_arch', 'hps_tokenizer'):      # (absent when not given, likewise)
+    for k in ('metric_hps_path', 'hps_prompts', 'hps_arch', 'hps_tokenizer', 'metric_cmmd_clip_path'):      # (absent when not given, likewise)
         if o.get(k) is not None:
             c[k] = o[k]
     if teacher:      # (absent otherwise: the printed options of every other run stay as they were)

@@ -2,7 +2,7 @@
 """Per-shape kernel micro-benchmarks on the SD1.5 work list -- the optimisation harness.
 Prints achieved TFLOP/s (contractions) or GB/s (HBM-bound kernels) per shape.  GPU only.
 
-    python tools/bench_kernels.py [conv] [gemm] [wgrad] [attn] [norm] [geglu] [fp8] [pr] [--batch 16]
+    python tools/bench_kernels.py [conv] [gemm] [wgrad] [attn] [norm] [geglu] [fp8] [pr] [mmd] [--batch 16]
 """
 import os
 import sys
@@ -232,6 +232,57 @@ def bench_pr(_B, N=30000, F=2048, k=3, rounds=5):
         h, t = med['hip_' + what], med['torch_' + what]
         print(f'  {what}: the fused kernel is {t / h:.2f}x the speed of torch' + (' (FASTER)' if h < t else ' (SLOWER)'))
     print(f'  peak memory of the process: {torch.cuda.max_memory_allocated() / 2 ** 20:.0f} MiB (the torch blocks: 10 000 x 10 000 fp32 + fp16)')
+
+
+def bench_mmd(_B, rounds=5):
+    """The KID / CMMD reduction (ops.pair_kernel_sums) at the sizes of cmmd30k_full (RBF, n = 30 000, F = 768) and kid30k_full
+    (cubic, 100 subsets of 1000 rows, F = 2048) against the dense torch chain of the same arithmetic on the device (`x @ y.T`, the
+    element function, `.double().sum()`: three n x n fp32 matrices, or per subset a gathered copy and three m x m ones),
+    alternating in one session."""
+    g = torch.Generator(device=dev).manual_seed(2)
+
+    def report(name, hip, ref, flops):
+        a, b = hip().cpu(), ref().cpu()
+        print(f'  results: max relative difference of the sums {float(((a - b).abs() / b.abs().clamp_min(1e-300)).max()):.2e}')
+        times = dict(hip=[], torch=[])
+        for _ in range(rounds):
+            times['hip'].append(timeit(hip, iters=2, warm=1))
+            times['torch'].append(timeit(ref, iters=2, warm=1))
+        med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+        for k, ts in times.items():
+            print(f'  {k:6s}: ' + ' '.join(f'{t * 1e3:8.2f}' for t in ts) + f'   median {med[k] * 1e3:8.2f} ms  {flops / med[k] / 1e12:6.1f} TFLOP/s of the dense 3-pass count')
+        print(f'  {name}: the fused kernel is {med["torch"] / med["hip"]:.2f}x the speed of torch' + (' (FASTER)' if med['hip'] < med['torch'] else ' (SLOWER)'))
+
+    n, F, p0 = 30000, 768, 1.0 / 200.0
+    print(f'--- RBF sums (CMMD), n = {n} against {n}, F = {F}: ms per call, {rounds} alternating rounds')
+    x = torch.nn.functional.normalize(torch.randn(n, F, device=dev, generator=g))
+    y = torch.nn.functional.normalize(torch.randn(n, F, device=dev, generator=g) + 0.05)
+
+    def rbf_ref():
+        out = []
+        for a, b in ((x, x), (y, y), (x, y)):
+            d2 = (a.square().sum(1)[:, None] + b.square().sum(1)[None, :] - 2.0 * (a @ b.t())).clamp_min_(0)
+            out.append((-torch.expm1(-p0 * d2)).double().sum())
+        return torch.stack(out)
+    torch.cuda.reset_peak_memory_stats()
+    report('rbf', lambda: ops.pair_kernel_sums(x, y, ops.PAIR_KERNEL_RBF, p0)[0, :3], rbf_ref, 3 * 2.0 * n * n * F)
+    print(f'  peak memory of the process: {torch.cuda.max_memory_allocated() / 2 ** 20:.0f} MiB (the features are {2 * n * F * 4 / 2 ** 20:.0f} MiB)')
+    del x, y
+
+    S, m, F, n = 100, 1000, 2048, 30000
+    print(f'--- cubic sums (KID), {S} subsets of {m} of {n} rows, F = {F}: ms per call, {rounds} alternating rounds')
+    x = torch.randn(n, F, device=dev, generator=g).abs()
+    y = torch.randn(n, F, device=dev, generator=g).abs() * 1.1
+    ix = torch.stack([torch.randperm(n, device=dev, generator=g)[:m] for _ in range(S)]).int()
+    iy = torch.stack([torch.randperm(n, device=dev, generator=g)[:m] for _ in range(S)]).int()
+
+    def poly_ref():
+        out = []
+        for s in range(S):
+            a, b = x[ix[s].long()], y[iy[s].long()]
+            out.append(torch.stack([((p @ q.t() / F + 1.0) ** 3).double().sum() for p, q in ((a, a), (b, b), (a, b))]))
+        return torch.stack(out)
+    report('poly3', lambda: ops.pair_kernel_sums(x, y, ops.PAIR_KERNEL_POLY3, 1.0 / F, 1.0, ix, iy)[:, :3], poly_ref, S * 3 * 2.0 * m * m * F)
 
 
 if __name__ == '__main__':
