@@ -21,6 +21,7 @@ import os
 import torch
 
 from ._lib import lib
+from .backward_state import PassLedger
 from .scheduler import prediction_mode
 
 BF16 = torch.bfloat16
@@ -196,7 +197,6 @@ _WGRAD_SIDE = os.environ.get('SIDLSG_WGRAD_STREAM', '1') != '0'
 _WGRAD_NSTREAMS = max(1, int(os.environ.get('SIDLSG_WGRAD_STREAMS', '1')))
 _wgrad_streams = {}
 _wgrad_rr = {}
-_wgrad_join_armed = set()
 
 
 # SIDLSG_WGRAD_PRIO=low: the weight-gradient streams are created with the LOWEST HIP stream priority (hipStreamCreateWithPriority; torch
@@ -235,7 +235,7 @@ def wgrad_stream(device):
     """The stream of the next weight-gradient launch (round robin when several are configured)."""
     lst = _wgrad_stream_list(device)
     if len(lst) > 1 and is_deterministic():
-        return lst[0]             # one stream: launches that share a dW stay ordered
+        return lst[0]             # one stream: every gradient is accumulated in one fixed order, across passes too
     key = _dev_key(device)
     i = _wgrad_rr.get(key, 0)
     _wgrad_rr[key] = (i + 1) % len(lst)
@@ -243,8 +243,11 @@ def wgrad_stream(device):
 
 
 def wgrad_stream_count():
-    """How many streams the weight-gradient launches of a backward pass are spread over (two launches on one dW are ordered
-    only when this is 1)."""
+    """How many streams the weight-gradient launches of a backward pass are spread over.  Two launches on one dW WITHIN a backward pass
+    are ordered for any count (_OnWgradStream: the later stream waits for the one that wrote the dW last).  Across passes they are
+    ordered through the main stream only: the record of who wrote which dW is dropped at the join that ends a pass, and each launch
+    waits for the main stream.  sd_util.hip_generate_steps still refuses the multi-step generator with a count above 1: that
+    combination (N uses of every layer in one pass) predates the ordering above and has not been tested with it."""
     return 1 if (not _WGRAD_SIDE or is_deterministic()) else _WGRAD_NSTREAMS
 
 
@@ -253,11 +256,20 @@ def grad_streams(device):
     return list(_wgrad_streams.get(_dev_key(device), ()))
 
 
-class _OnWgradStream:
-    """with _OnWgradStream(dy, x): <wgrad launches> -- inside a torch.autograd.Function.backward only."""
+_wgrad_dw_stream = {}        # several weight-gradient streams only: data_ptr of a dW -> the side stream that wrote it last
+wgrad_order_log = None       # a list here records ('launch', dW, stream handle) / ('wait', dW, later handle, earlier handle) (tests)
 
-    def __init__(self, *tensors):
+
+class _OnWgradStream:
+    """with _OnWgradStream(dy, x, dws=(dW, ...)): <wgrad launches> -- inside a torch.autograd.Function.backward only.
+    dws: the gradient tensors the launches write.  With one weight-gradient stream two launches on one dW are ordered by the stream.
+    With several (SIDLSG_WGRAD_STREAMS > 1) the stream chosen here first waits for the stream that wrote any of `dws` last, so a
+    parameter that reaches its weight gradient twice (a shared layer; one use queued and flushed, the other launched directly) is
+    accumulated in launch order by construction, whichever streams the round robin hands out."""
+
+    def __init__(self, *tensors, dws=()):
         self.tensors = tensors
+        self.dws = dws
         self.on = _WGRAD_SIDE and tensors[0].dtype == BF16
 
     def __enter__(self):
@@ -266,6 +278,17 @@ class _OnWgradStream:
         dev = self.tensors[0].device
         self.side = wgrad_stream(dev)
         self.side.wait_stream(torch.cuda.current_stream(dev))
+        if len(_wgrad_stream_list(dev)) > 1:
+            for dw in self.dws:
+                p = dw.data_ptr()
+                prev = _wgrad_dw_stream.get(p)
+                if prev is not None and prev.cuda_stream != self.side.cuda_stream:
+                    self.side.wait_stream(prev)
+                    if wgrad_order_log is not None:
+                        wgrad_order_log.append(('wait', p, self.side.cuda_stream, prev.cuda_stream))
+                _wgrad_dw_stream[p] = self.side
+                if wgrad_order_log is not None:
+                    wgrad_order_log.append(('launch', p, self.side.cuda_stream))
         self.cm = torch.cuda.stream(self.side)
         self.cm.__enter__()
         return self
@@ -276,23 +299,19 @@ class _OnWgradStream:
         self.cm.__exit__(*exc)
         for t in self.tensors:
             t.record_stream(self.side)
-        # one join per backward pass and device, keyed by the autograd graph-task id (a pass that died with an exception
-        # must not leave the next one un-joined)
-        key = (_dev_key(self.tensors[0].device), torch._C._current_graph_task_id())
-        if key not in _wgrad_join_armed:
-            dev = self.tensors[0].device
-
+        # one join per backward pass and device: the mark lives with the pass in the ledger and goes when the pass ends or dies, so a
+        # pass that raised cannot leave the next one un-joined and a nested pass does not take the outer one's join away
+        dev = self.tensors[0].device
+        if _passes.once(('wgrad join', _dev_key(dev))):
+            if _wgrad_dw_stream:
+                _passes.on_death(_wgrad_dw_stream.clear)     # a pass that dies never joins: its record goes with it
             def join():
-                _wgrad_join_armed.discard(key)
                 for side in grad_streams(dev):
                     torch.cuda.current_stream(dev).wait_stream(side)
-            if key[1] < 0:                       # not inside a backward pass: join right away
+                _wgrad_dw_stream.clear()         # every side stream has been joined: later launches are ordered behind them anyway
+            if _passes.current() < 0:            # not inside a backward pass: join right away
                 join()
             else:
-                # ids never repeat: anything left for THIS device is from a pass that did not finish
-                for stale in [k for k in _wgrad_join_armed if k[0] == key[0]]:
-                    _wgrad_join_armed.discard(stale)
-                _wgrad_join_armed.add(key)
                 torch.autograd.Variable._execution_engine.queue_callback(join)
         return False
 
@@ -304,18 +323,23 @@ class _OnWgradStream:
 # read gradients (flush_deferred(): the fused optimizer and the reducer call it).  The partial-sum workspaces are kept alive here
 # until then.  SIDLSG_DEFER_REDUCE=0: one reduction launch per layer as before (A/B, tests).
 _DEFER = os.environ.get('SIDLSG_DEFER_REDUCE', '1') != '0'
-_defer_streams = {}          # stream handle -> [torch stream, [workspaces]]
-_defer_armed = set()
+_defer_streams = {}          # stream handle -> [torch stream, the ledger's queue of (graph-task id, workspace)]
 
 
 def _defer_begin(device):
-    """Before a norm-backward launch that reduces parameter gradients: deferral on for the current stream."""
+    """Before a norm-backward launch that reduces parameter gradients: deferral on for the current stream.
+    The library's queue of a stream carries no pass tags, so it holds the reductions of ONE backward pass at a time: what another
+    live pass (the outer one of a re-entrant pass) left queued on this stream is launched first -- its partial sums are complete,
+    launching them early is harmless -- and a pass that dies can then have exactly its own reductions forgotten."""
     if not _DEFER:
         return None
     st = torch.cuda.current_stream(device)
     h = st.cuda_stream
+    key = ('reduce', h)
     if h not in _defer_streams:
-        _defer_streams[h] = [st, []]
+        _defer_streams[h] = [st, _passes.queue(key)]
+    if _passes.owners(key) - {_passes.current()}:
+        _passes.flush(key)
     lib.sidlsg_defer_reductions.raw(h, 1)
     return h
 
@@ -325,25 +349,14 @@ def _defer_end(h, ws):
     if h is None:
         return
     lib.sidlsg_defer_reductions.raw(h, 2)        # only the call in between was deferred (direct users of the C ABI never are)
-    _defer_streams[h][1].append(ws)
-    if torch._C._current_graph_task_id() < 0:
+    if _passes.add(('reduce', h), ws) < 0:
         flush_deferred()
-    else:
-        _arm_end_of_backward_flush()
 
 
 def flush_deferred():
     """Launch every queued reduction (one kernel per stream that has any) and order the current stream after them."""
     flush_wgrad_queues()
-    for h, (st, keep) in _defer_streams.items():
-        if not keep:
-            continue
-        if lib.sidlsg_flush_reductions.raw(h) < 0:
-            raise RuntimeError('sidlsg_flush_reductions failed')
-        keep.clear()
-        cur = torch.cuda.current_stream(st.device)
-        if cur.cuda_stream != h:
-            cur.wait_stream(st)
+    _passes.flush()
 
 
 # ---- grouped dense weight gradients (csrc/gemm.hip "grouped dense weight gradients") -----------------------------------------------
@@ -367,11 +380,15 @@ class _WgJob(ctypes.Structure):
                 ('assign', ctypes.c_int), ('pad', ctypes.c_int * 2)]
 
 
-def _queue_dense_wgrad(dy, x, dw, dbias, M, N, K, assign):
+def _queue_dense_wgrad(dy, x, dw, dbias, M, N, K, assign, weight=None):
     """True: queued for a grouped launch (the caller must not launch it).
     The jobs of one grouped launch must have DISTINCT dW (include/sidlsg_hip.h): a parameter that reaches its weight gradient twice in
-    one backward pass (a shared / re-applied layer; one use queued and another one launched directly) first flushes what is queued,
-    so the two gradients stay ordered on the weight-gradient stream (the `assign` mark was taken by the earlier one)."""
+    one backward pass (a shared / re-applied layer; one use queued and another one launched directly) first flushes what is queued
+    (the `assign` mark was taken by the earlier one).  The two launches then stay ordered: on the one weight-gradient stream, or --
+    several streams -- because the later launch's stream waits for the earlier one's (_OnWgradStream, `dws`).
+    A queued job belongs to the backward pass that queued it (the ledger `_passes`): it is launched when its queue is full, at a
+    marker, when any live pass ends or before gradients are read; if ITS pass raises it is dropped, never launched, and `weight` gets
+    the `assign` mark back that the job had taken (_drop_entries)."""
     if dw.data_ptr() in _wg_queued_dw:
         flush_wgrad_queues()
     if not _WG_GROUP or dy.dtype != BF16 or x.dtype != BF16 or not dy.is_cuda:
@@ -383,66 +400,71 @@ def _queue_dense_wgrad(dy, x, dw, dbias, M, N, K, assign):
     t160 = N % 160 == 0 and K % 160 == 0 and N != K and (M >= 4096 or N * K >= (8 << 20))
     if t160 and not _WG_GROUP160:
         return False
-    if torch._C._current_graph_task_id() < 0:
+    if _passes.current() < 0:
         return False          # outside a backward pass nobody would flush
     st = torch.cuda.current_stream(dy.device)
-    q = _wg_queues.setdefault((st.cuda_stream, t160), [st, [], t160])
-    q[1].append((dy, x, dw, dbias, M, N, K, 1 if assign else 0))
+    key = ('wgrad', st.cuda_stream, t160)
+    q = _wg_queues.setdefault(key[1:], [st, _passes.queue(key), t160])
     _wg_queued_dw.add(dw.data_ptr())
+    _passes.add(key, (dy, x, dw, dbias, M, N, K, 1 if assign else 0, weight))
     if len(q[1]) >= (_WG_MAX160 if t160 else _WG_MAX):
-        _flush_wgrad_queue(q)
-    _arm_end_of_backward_flush()
+        _passes.flush(key)
     return True
 
 
-def _flush_wgrad_queue(q):
-    st, jobs, t160 = q
-    if not jobs:
-        return
+def _launch_wgrad_group(st, t160, jobs):
     arr = (_WgJob * len(jobs))()
-    for i, (dy, x, dw, dbias, M, N, K, assign) in enumerate(jobs):
+    for i, (dy, x, dw, dbias, M, N, K, assign, _) in enumerate(jobs):
         arr[i].dY, arr[i].A, arr[i].dW, arr[i].dBias = dy.data_ptr(), x.data_ptr(), dw.data_ptr(), (dbias.data_ptr() if dbias is not None else None)
         arr[i].ldy, arr[i].lda, arr[i].M, arr[i].N, arr[i].K, arr[i].assign = dy.stride(0), x.stride(0), M, N, K, assign
+    for j in jobs:                       # launched or not, the jobs have left the queue
+        _wg_queued_dw.discard(j[2].data_ptr())
     tensors = [t for j in jobs for t in j[:2]]
     with torch.cuda.stream(st):          # the stream the operands were produced on: the weight-gradient stream waits for IT
-        with _OnWgradStream(*tensors):
+        with _OnWgradStream(*tensors, dws=[j[2] for j in jobs]):
             (lib.sidlsg_wgrad_group160_bf16 if t160 else lib.sidlsg_wgrad_group_bf16)(ctypes.addressof(arr), len(jobs), _s())
-    for j in jobs:
-        _wg_queued_dw.discard(j[2].data_ptr())
-    jobs.clear()
 
 
 def flush_wgrad_queues():
-    for q in _wg_queues.values():
-        _flush_wgrad_queue(q)
+    for h, t160 in list(_wg_queues):
+        _passes.flush(('wgrad', h, t160))
 
 
-def _discard_stale_backward_state():
-    """A backward pass that raised left its queues behind (weight-gradient jobs, dgamma / dbeta reductions on the C side, partial-sum
-    workspaces, the shared column-gradient buffer): launching them into .grad during the NEXT pass -- possibly after an optimizer step
-    re-marked the gradients -- would apply stale gradients silently.  Drop them."""
-    for q in _wg_queues.values():
-        q[1].clear()
-    _wg_queued_dw.clear()
-    for h, (st, keep) in _defer_streams.items():
-        lib.sidlsg_defer_reductions.raw(h, 3)
-        keep.clear()
-    for holder in list(_ColumnGrads.live):
-        holder.buf = None
+def _launch_entries(key, entries):
+    """Ledger hook: launch what one queue holds.  Every entry is complete work of a LIVE pass (of several, when passes nest)."""
+    if key[0] == 'wgrad':
+        _launch_wgrad_group(_wg_queues[key[1:]][0], key[2], entries)
+    else:
+        h = key[1]
+        st = _defer_streams[h][0]
+        if lib.sidlsg_flush_reductions.raw(h) < 0:
+            raise RuntimeError('sidlsg_flush_reductions failed')
+        cur = torch.cuda.current_stream(st.device)
+        if cur.cuda_stream != h:
+            cur.wait_stream(st)
 
 
-def _arm_end_of_backward_flush():
-    tid = torch._C._current_graph_task_id()
-    if tid >= 0 and tid not in _defer_armed:
-        if _defer_armed:                 # ids never repeat: anything left is from a pass that did not finish
-            _defer_armed.clear()
-            _discard_stale_backward_state()
-        _defer_armed.add(tid)
+def _drop_entries(key, entries):
+    """Ledger hook: the pass that queued `entries` raised.  Launching them into .grad during a later pass -- possibly after an optimizer
+    step re-marked the gradients -- would apply stale gradients silently, so they are forgotten: weight-gradient jobs give the `assign`
+    mark they took back to their parameter (the next pass must still overwrite what the optimizer left in .grad), and the library
+    forgets the dgamma / dbeta reductions queued on the stream (they are this pass's alone, see _defer_begin).  The entries of other
+    passes stay.  Gradients the dead pass had already WRITTEN (launches that were not queued, groups that were full) are the caller's
+    to zero, as in plain PyTorch."""
+    if key[0] == 'wgrad':
+        for job in entries:
+            _wg_queued_dw.discard(job[2].data_ptr())
+            if job[7] and job[8] is not None:
+                job[8]._grad_assign = True
+    else:
+        lib.sidlsg_defer_reductions.raw(key[1], 3)
 
-        def done():
-            _defer_armed.discard(tid)
-            flush_deferred()
-        torch.autograd.Variable._execution_engine.queue_callback(done)
+
+# The end-of-backward flush: the first entry of a backward pass makes the pass known to the ledger, which queues ONE engine callback
+# for it; when it runs -- the pass has ended -- whatever is queued is launched (the entries of every live pass).  A pass is told dead by
+# that callback being freed without having run (backward_state.PassLedger); only then, and only for that pass, are entries dropped.
+# A nested pass -- a new graph-task id while the outer pass is live -- drops nothing.
+_passes = PassLedger(_launch_entries, _drop_entries)
 
 
 def ensure_stream_workspace(stream, nbytes=256 << 20):
@@ -673,6 +695,10 @@ def _conv_dgrad(dy, w16t, x_shape, stride, ups, dtype):
 # One autograd node per weight-bearing op.  A node is in its GROUPED form when its parameters arrive as Pairs (the pass of two
 # FROZEN networks over a stacked batch, dual_networks): the backward is then the data gradient only and nothing of the forward
 # input is kept alive for a weight gradient -- the Pairs live on ctx (they are not tensors).
+# ctx.masters: a weight-bearing node keeps its parameter OBJECTS next to the saved tensors.  The gradient buffer (.grad, `_flat_grad`) and
+# the `_grad_assign` mark hang on the object, and ctx.saved_tensors does not always give it back: under saved-tensor hooks -- the
+# recomputation of torch.utils.checkpoint(use_reentrant=False) -- a saved parameter returns as a detached alias that has neither.  The
+# saved tensors are still unpacked (values, and autograd's check that nothing was modified in place); only the identity comes from ctx.
 class _Linear(torch.autograd.Function):
     """y = x W^T + b (+ res) (+ rowvec broadcast over rows_per_batch rows).  x: [M,K] bf16.  Grouped: bias / w16 / w16t are Pairs and
     weight is None."""
@@ -686,6 +712,7 @@ class _Linear(torch.autograd.Function):
             ctx.w16t = w16t
         else:
             ctx.save_for_backward(x, weight, bias, w16t)
+            ctx.masters = (weight, bias)
         ctx.dtype = x.dtype
         ctx.rpb = rows_per_batch
         ctx.has_res = res is not None
@@ -701,7 +728,8 @@ class _Linear(torch.autograd.Function):
             dx = gemm(dy, ctx.w16t) if ctx.needs_input_grad[0] else None
             drv = colsum(dy, ctx.rpb, per_batch=True) if need_rv else None
             return dx, None, None, None, None, dres, drv, None, None
-        x, weight, bias, w16t = ctx.saved_tensors
+        x, _, _, w16t = ctx.saved_tensors
+        weight, bias = ctx.masters
         dx = gemm(dy, w16t) if ctx.needs_input_grad[0] else None
         need_b = _wants_grad(bias)
         # bias gradient comes out of the bf16 wgrad kernel (the fp32 family computes it with a column sum)
@@ -709,9 +737,9 @@ class _Linear(torch.autograd.Function):
         if _wants_grad(weight):
             M, K = x.shape
             assign = _take_assign(weight, x.dtype)
-            if not _queue_dense_wgrad(dy, x, weight.grad, bias.grad if fused_b else None, M, weight.shape[0], K, assign):
+            if not _queue_dense_wgrad(dy, x, weight.grad, bias.grad if fused_b else None, M, weight.shape[0], K, assign, weight):
                 wg = _fn('wgrad_assign', x.dtype, '_bf16') if assign else _fn('wgrad', x.dtype, '_bf16')
-                with _OnWgradStream(dy, x):
+                with _OnWgradStream(dy, x, dws=(weight.grad,)):
                     wg(_p(dy), dy.stride(0), _p(x), x.stride(0), _p(weight.grad), _p(bias.grad) if fused_b else None, M, weight.shape[0], K, _s())
         drv = None
         if need_rv:
@@ -752,6 +780,7 @@ class _Conv3x3(torch.autograd.Function):
             ctx.w16t = w16t
         else:
             ctx.save_for_backward(x, weight, bias, w16t)
+            ctx.masters = (weight, bias)
         ctx.cfg = (stride, ups, res is not None, rowvec is not None, x.shape, x.dtype)
         ctx.rv_slot = getattr(rowvec, '_col_slot', None)
         return y
@@ -768,7 +797,8 @@ class _Conv3x3(torch.autograd.Function):
             dx = _conv_dgrad(dy, ctx.w16t, xs, stride, ups, dtype) if ctx.needs_input_grad[0] else None
             drv = colsum(dy2, Ho * Wo, per_batch=True, slot=ctx.rv_slot) if need_rv else None
             return dx, None, None, None, None, dres, drv, None, None, None, None
-        x, weight, bias, w16t = ctx.saved_tensors
+        x, _, _, w16t = ctx.saved_tensors
+        weight, bias = ctx.masters
         Cin = xs[3]
         dx = _conv_dgrad(dy, w16t, xs, stride, ups, dtype) if ctx.needs_input_grad[0] else None
         co_w, ci_w = weight.shape[0], weight.shape[1]     # logical (unpadded) sizes of the master
@@ -782,7 +812,7 @@ class _Conv3x3(torch.autograd.Function):
             if not padded and _take_assign(weight, x.dtype):
                 wgrad = lib.sidlsg_conv3x3_wgrad_assign_bf16
             if not padded:
-                with _OnWgradStream(dy, x):
+                with _OnWgradStream(dy, x, dws=(weight.grad,)):
                     wgrad(_p(dy), Cout, _p(x), Cin, _p(weight.grad), _p(bias.grad) if fused_b else None,
                           B, H, W, Cin, Cout, stride, ups, _s())
             else:
@@ -921,19 +951,19 @@ def layernorm_fp8_g2(x, gamma, beta, eps):
 
 def _keep(ctx, x, stats, *params):
     """What a norm node keeps for its backward: x and stats as saved tensors, and its parameters -- saved tensors too in the single
-    form, Pairs on ctx in the grouped one."""
+    form (and as `ctx.masters`, see there), Pairs on ctx in the grouped one."""
     if isinstance(params[0], Pair):
         ctx.save_for_backward(x, stats)
         ctx.params = params
     else:
         ctx.save_for_backward(x, stats, *params)
-        ctx.params = None
+        ctx.params, ctx.masters = None, params
 
 
 def _kept(ctx):
     """-> x, stats, parameters as _keep() got them."""
-    x, stats, *params = ctx.saved_tensors
-    return x, stats, ctx.params or params
+    x, stats, *_ = ctx.saved_tensors
+    return x, stats, ctx.params or ctx.masters
 
 
 class _GroupNorm(torch.autograd.Function):
@@ -1274,6 +1304,7 @@ class _LinearGEGLU(torch.autograd.Function):
         lib.sidlsg_gemm_geglu_bf16(_p(x), x.stride(0), _p(w16), _p(h), N2, _p(y), N2 // 2, _p(bias), M, N2, K, _s())
         if keep_h:
             ctx.save_for_backward(x, weight, bias, w16t, h)
+            ctx.masters = (weight, bias)
         if with_h:
             # h as a second output: the consumer (_GegluLinear) returns the gradient with respect to h itself -- its data-gradient
             # GEMM applies the GEGLU derivative in the epilogue -- and no gradient for y
@@ -1283,7 +1314,8 @@ class _LinearGEGLU(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy, dh=None):
-        x, weight, bias, w16t, h = ctx.saved_tensors
+        x, _, _, w16t, h = ctx.saved_tensors
+        weight, bias = ctx.masters
         F2 = h.shape[-1]
         if dy is not None:
             dh_y = torch.empty_like(h)
@@ -1298,9 +1330,9 @@ class _LinearGEGLU(torch.autograd.Function):
             M, K = x.shape
             need_b = _wants_grad(bias)
             assign = _take_assign(weight, BF16)
-            if not _queue_dense_wgrad(dh, x, weight.grad, bias.grad if need_b else None, M, weight.shape[0], K, assign):
+            if not _queue_dense_wgrad(dh, x, weight.grad, bias.grad if need_b else None, M, weight.shape[0], K, assign, weight):
                 wg = lib.sidlsg_wgrad_assign_bf16 if assign else lib.sidlsg_wgrad_bf16
-                with _OnWgradStream(dh, x):
+                with _OnWgradStream(dh, x, dws=(weight.grad,)):
                     wg(_p(dh), dh.stride(0), _p(x), x.stride(0), _p(weight.grad), _p(bias.grad) if need_b else None, M, weight.shape[0], K, _s())
         elif _wants_grad(bias):
             colsum(dh, dh.shape[0], total=bias.grad)
@@ -1343,12 +1375,14 @@ class _GegluLinear(torch.autograd.Function):
         out = gemm(y, w16, bias=bias, res=res)
         wg = weight.requires_grad
         ctx.save_for_backward(h, y if wg else None, weight, bias, w16t)
+        ctx.masters = (weight, bias)
         ctx.has_res = res is not None
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        h, y, weight, bias, w16t = ctx.saved_tensors
+        h, y, _, _, w16t = ctx.saved_tensors
+        weight, bias = ctx.masters
         dout = _gradc(dout)
         M, F2 = h.shape
         K = dout.shape[1]
@@ -1359,9 +1393,9 @@ class _GegluLinear(torch.autograd.Function):
         need_b = _wants_grad(bias)
         if _wants_grad(weight):
             assign = _take_assign(weight, BF16)
-            if not _queue_dense_wgrad(dout, y, weight.grad, bias.grad if need_b else None, M, weight.shape[0], F2 // 2, assign):
+            if not _queue_dense_wgrad(dout, y, weight.grad, bias.grad if need_b else None, M, weight.shape[0], F2 // 2, assign, weight):
                 wgk = lib.sidlsg_wgrad_assign_bf16 if assign else lib.sidlsg_wgrad_bf16
-                with _OnWgradStream(dout, y):
+                with _OnWgradStream(dout, y, dws=(weight.grad,)):
                     wgk(_p(dout), dout.stride(0), _p(y), y.stride(0), _p(weight.grad), _p(bias.grad) if need_b else None, M, weight.shape[0],
                         F2 // 2, _s())
         elif need_b:
@@ -1819,18 +1853,27 @@ def transpose_w(src_f32, n, k, taps=1, dtype=BF16):
 class _ColumnGrads:
     """The gradient of a split_columns() source, built in place: one [n, sum C] fp32 buffer per backward pass (zeroed ONCE, on
     first use) into whose column slices the consumers' backward kernels accumulate (ops.colsum(slot=...)); _SplitColumns.backward
-    hands it on as it is.  22 fills + a concat kernel per pass become one fill."""
+    hands it on as it is.  22 fills + a concat kernel per pass become one fill.
 
-    live = weakref.WeakSet()         # every holder, so that a pass that raised can be cleaned up after (_discard_stale_backward_state)
+    Consumers of several live passes may accumulate into one buffer (a re-entrant pass in the middle of the outer one: a checkpointed
+    consumer).  If any pass that accumulated into it raises, the buffer is dropped with that pass (the ledger `_passes`): the partial
+    sums of a pass that died must not reach the next one."""
 
     def __init__(self, sizes):
         self.total, self.buf = sum(sizes), None
-        _ColumnGrads.live.add(self)
 
     def buffer(self, n, device):
+        if _passes.once(('column grads', id(self))) and _passes.current() >= 0:
+            _passes.on_death(functools.partial(_ColumnGrads._forget, weakref.ref(self)))
         if self.buf is None:
             self.buf = torch.zeros((n, self.total), device=device, dtype=F32)
         return self.buf if self.buf.shape[0] == n else None
+
+    @staticmethod
+    def _forget(ref):
+        holder = ref()
+        if holder is not None:
+            holder.buf = None
 
     def take(self):
         b, self.buf = self.buf, None
