@@ -393,6 +393,29 @@ int sidlsg_pair_kernel_sums_ws_doubles(int S, int mx, int my);
 int sidlsg_pair_kernel_sums(const float* X, int nx, const float* Y, int ny, int F, const int* ix, const int* iy, int S, int mx, int my,
                             int kind, float p0, float p1, double* out, double* ws, void* stream);
 
+/* ---- FID Inception-v3 detector (sid_lsg_amd/inception.py, csrc/inception.hip): fp32 only ------------------------------------------
+ * sidlsg_conv2d_relu_f32: Y[b][ho][wo][n] = act(bias[n] + sum over (dh, dw, c) of X[b][ho * stride - pad_h + dh][wo * stride - pad_w + dw][c]
+ * * W[n][dh][dw][c]) on v_mfma_f32_16x16x4_f32: an exact fp32 fma chain in increasing k = (dh * KW + dw) * Cin + c, then one add of the
+ * bias (the folded BatchNorm shift; never NULL), then max(., 0) when relu != 0.  X: [B][H][Wd][ldx] NHWC, W: [Cout][KH][KW][Cin],
+ * Y: [B][Ho][Wo][ldc] with Ho = (H + 2 pad_h - KH) / stride + 1 (floor), Wo likewise.  ldc is independent of Cout: Y may point at a
+ * channel slice of a wider buffer, the columns outside [0, Cout) of a row are not touched.  Taps outside the image read as zero (a
+ * bounds test in the gather, no padded copy).  (KH, KW) in {(1,1), (3,3), (5,5), (1,7), (7,1), (1,3), (3,1)}, stride 1 or 2,
+ * 0 <= pad < kernel side, Cin, ldx, ldc multiples of 4 (a 3-channel image is fed as 4 channels with a zero plane and zero weights),
+ * any Cout and any B * Ho * Wo.  All four pointers 16-byte aligned.
+ * sidlsg_pool2d_f32: k x k window (k <= 8, 2 pad <= k) over X [B][H][W][ldx] -> Y [B][Ho][Wo][ldy], C channels (C, ldx, ldy multiples
+ * of 4).  mode 0: max over the taps inside the image (padding never wins: the bits of max_pool2d).  mode 1: mean over the taps inside
+ * the image only (count_include_pad = False): summed in row-major order, divided once by their count.
+ * sidlsg_inception_input_u8: uint8 NCHW [B][3][H][W] -> out [B][299][299][4] fp32, TF's legacy bilinear resize and the detector's
+ * normalisation in one launch.  Output column i reads q = (i * W) div 299 and min(q + 1, W - 1) with the weight
+ * float((i * W) mod 299) / 299.0f on the second (rows likewise); t = a + l * (b - a) horizontally, then vertically, then
+ * (t - 128) / 128, each operation rounded once; channel 3 is zero.  H, W <= 16384.
+ * SIDLSG_EINVAL, and no launch, for anything outside this and for an operand of 2^31 bytes or more. */
+int sidlsg_conv2d_relu_f32(const float* X, int ldx, const float* W, float* Y, int ldc, const float* bias, int B, int H, int Wd, int Cin,
+                           int Cout, int KH, int KW, int stride, int pad_h, int pad_w, int relu, void* stream);
+int sidlsg_pool2d_f32(const float* X, int ldx, float* Y, int ldy, int B, int H, int W, int C, int k, int stride, int pad, int mode,
+                      void* stream);
+int sidlsg_inception_input_u8(const void* images, float* out, int B, int H, int W, void* stream);
+
 /* ---- snapshot preview grids (save_image_grid, sid_training_loop.py:99-115, 597-614) -------------------------------------
  * B decoded fp32 images -> their tiles of ONE uint8 grid image [gh*H][gw*W][3] (HWC, what a PNG writer takes): image i goes to
  * tile first + i, row (first + i) / gw, column (first + i) % gw, so the batches of a grid are placed as they leave the decoder and

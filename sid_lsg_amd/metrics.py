@@ -1,4 +1,4 @@
-"""Evaluation metrics of the distilled generator: FID, CLIP scores, precision / recall, HPSv2, KID and CMMD.
+"""Evaluation metrics of the distilled generator: FID, CLIP scores, precision / recall, HPSv2, KID, CMMD and the Inception Score.
 
 Reference: metrics/sid_metric_main.py:25-123 (registry, `calc_metric`, `report_metric`, the `fid30k_full` /
 `fid_clip_30k_full` / `fid_test` / `fid_clip_test` entries), metrics/sid_fid_and_clip.py:32-74 (the Frechet distance between
@@ -27,6 +27,8 @@ What is different here (not a translation):
     correctly rounded, so single distances differ by an fp16 ulp (tests/test_gpu_pr.py pins what follows from that).
   * KID and CMMD are not in the reference: both are sums of a kernel function over all pairs of feature vectors, formed by
     `ops.pair_kernel_sums` (fp32 operands on the MFMA, fp64 sums in a fixed order, no N x N matrix); see the section above the registry.
+  * the Inception-v3 itself runs on this package's kernels when its weights come as a state dict (sid_lsg_amd.inception; or the seeded
+    'random:inception-v3'), and the Inception Score (`compute_is`, not in the reference either) reads its class probabilities.
 Only the precision / recall and pair-sum kernels are hot; the rest is host logic.
 """
 import json
@@ -154,19 +156,33 @@ def is_clip_spec(path):
     return isinstance(path, (str, os.PathLike)) and (str(path).lower().startswith('random:clip-') or os.path.isfile(os.path.join(str(path), 'config.json')))
 
 
+def is_inception_spec(path):
+    """'random:inception-v3[:seed]': the seeded Inception-v3 this package builds itself (sid_lsg_amd.inception)."""
+    return isinstance(path, str) and (path.lower() == 'random:inception-v3' or path.lower().startswith('random:inception-v3:'))
+
+
 def load_detector(path, device):
     """A feature detector file of the reference's kinds: TorchScript (`inception-2015-12-05.pt`, called as
     `detector(uint8 NCHW images, return_features=True)`) or a pickled module (open_clip / CLIP wrappers, called with
     `texts=..., div255=True`).  Offline there are none: callers may pass any callable instead.  A CLIP directory (is_clip_spec) gives
-    a `clip.HipCLIPDetector` with the wrappers' call contract: the image tower on the HIP kernels."""
+    a `clip.HipCLIPDetector` with the wrappers' call contract: the image tower on the HIP kernels.  The Inception-v3 as a
+    torch.save'd state dict in torchvision / pytorch-fid key names, or 'random:inception-v3[:seed]', gives an
+    `inception.HipInceptionV3` with the TorchScript detector's call contract: the whole network on the HIP kernels."""
     if callable(path):
         return path
     if is_clip_spec(path):
         from .clip import load_clip
         return load_clip(path, device)
+    if is_inception_spec(path):
+        from .inception import load_inception
+        return load_inception(path, device)
     if not path or not os.path.isfile(path):
         raise FileNotFoundError(f'feature detector {path!r} not found: FID / CLIP metrics need the Inception / CLIP files the reference '
                                 'downloads (metrics/sid_fid_and_clip.py:36, sid_metric_utils.py:456); pass a local file or a callable')
+    from . import inception
+    state_dict = inception.load_state_dict_file(path)       # None for a TorchScript archive or a pickled module
+    if state_dict is not None:
+        return inception.HipInceptionV3(state_dict, device)
     try:
         return torch.jit.load(path, map_location=device).eval()
     except Exception:
@@ -616,6 +632,50 @@ def compute_kid(opts, max_real, num_gen, num_subsets=KID_NUM_SUBSETS, max_subset
     return kid_from_features(_features_f32(real, opts.device), _features_f32(gen, opts.device), num_subsets, max_subset_size)
 
 
+# Inception Score (Salimans et al. 2016; `is50k` of the StyleGAN3 metric registry, metrics/inception_score.py there): restated from
+# the published source, not pinned against that package.
+def is_from_probabilities(probs, num_splits=10):
+    """[N, C] class probabilities -> (mean, population std) over `num_splits` contiguous splits of
+    exp(mean_i sum_c p_ic (log p_ic - log mean_i p_ic)), in fp64 (0 log 0 = 0).  Split s holds the rows
+    s * N // num_splits .. (s + 1) * N // num_splits - 1.  Evaluated in base 2 (2^(.. log2 ..), the same number): one-hot rows spread
+    evenly over K = 2^j classes then score K exactly, where exp(log K) is an ulp off."""
+    p = np.asarray(probs, dtype=np.float64)
+    if p.ndim != 2 or num_splits < 1 or p.shape[0] < num_splits:
+        raise ValueError(f'inception score: {p.shape} probabilities in {num_splits} splits')
+    scores = []
+    for s in range(num_splits):
+        part = p[s * p.shape[0] // num_splits:(s + 1) * p.shape[0] // num_splits]
+        with np.errstate(divide='ignore', invalid='ignore'):
+            kl = part * (np.log2(part) - np.log2(part.mean(axis=0, keepdims=True)))
+        scores.append(np.exp2(np.where(part > 0, kl, 0.0).sum(axis=1).mean()))
+    return float(np.mean(scores)), float(np.std(scores))
+
+
+class _ProbabilityDetector:
+    """The detector as compute_is reads it: class probabilities without fc's bias, through the `return_features` call of the loops."""
+
+    def __init__(self, detector):
+        self.detector = detector
+
+    def __call__(self, images, return_features=True):
+        return self.detector(images, no_output_bias=True)
+
+
+def is_options(opts):
+    """`opts` with the detector's probabilities in place of its features."""
+    import copy
+    o = copy.copy(opts)
+    o.detector = _ProbabilityDetector(load_detector(opts.detector, opts.device))
+    return o
+
+
+def compute_is(opts, num_gen, num_splits=10):
+    """Inception Score of `num_gen` generated images: the probabilities det(images, no_output_bias=True) after the 256 x 256 detector
+    resize of FID, captured on the device, reduced in fp64.  Needs neither real images nor their statistics.  -> (mean, std)."""
+    probs = generator_feature_stats(is_options(opts), num_gen, capture_all=True)[0].get_all_torch()
+    return is_from_probabilities(probs.cpu().numpy(), num_splits)
+
+
 class ClipEmbeddingDetector:
     """The image tower of a CLIP model with the detector call contract: uint8 images of any size -> F.normalize(image_embeds), fp32.
     The tower resamples H x W to its own R x R without a crop (preprocess='interpolate'), as the published CMMD code does."""
@@ -701,6 +761,19 @@ def pr_test(opts):
     return dict(pr30k3_full_precision=precision, pr30k3_full_recall=recall)
 
 
+# registered here, behind the other metrics of the Inception detector: later entries keep their place at the end of the list
+@register_metric
+def is30k_full(opts):
+    mean, std = compute_is(opts, num_gen=30000, num_splits=10)
+    return dict(is30k_full_mean=mean, is30k_full_std=std)
+
+
+@register_metric
+def is_test(opts):
+    mean, std = compute_is(opts, num_gen=max(1, getattr(opts, 'num_test', opts.batch_gen)), num_splits=1)
+    return dict(is30k_full_mean=mean, is30k_full_std=std)
+
+
 def compute_hps(opts, per_style):
     """HPSv2 benchmark score (the reference's generate_hpsv2.py + hpsv2.evaluate, sid_lsg_amd.hps): for each of the four styles,
     image i < per_style from prompt i of the style and the latent of torch.Generator(i) -- the same latents for every style --
@@ -774,6 +847,7 @@ def cmmd_test(opts):
 NEEDS_IMAGES = ('pr30k3_full', 'pr_test', 'kid30k_full', 'kid_test', 'cmmd30k_full', 'cmmd_test')
 HPS_METRICS = ('hpsv2', 'hpsv2_test')          # metrics that need neither the Inception detector nor real-set statistics
 CMMD_METRICS = ('cmmd30k_full', 'cmmd_test')   # likewise: the CLIP image tower of --metric_cmmd_clip_path and the real images
+IS_METRICS = ('is30k_full', 'is_test')         # the Inception detector alone: neither real images nor their statistics
 
 
 def calc_metric(metric, **kwargs):

@@ -2289,6 +2289,71 @@ def pair_kernel_sums(x, y, kind, p0, p1=0.0, idx_x=None, idx_y=None):
     return out
 
 
+# ---- FID Inception-v3 detector (csrc/inception.hip): fp32 NHWC, forward only ----
+POOL_MAX, POOL_MEAN = 0, 1
+
+
+def _slice_out(name, out, shape, col, width, device):
+    """The [B, Ho, Wo, ld] fp32 buffer a launch writes columns col .. col + width - 1 of (a fresh [.., width] one when out is None)."""
+    if out is None:
+        if col:
+            raise RuntimeError(f'{name}: a column offset needs the buffer it counts in')
+        return torch.empty(shape + (width,), device=device, dtype=F32)
+    _chk(out, F32)
+    if out.dim() != 4 or tuple(out.shape[:3]) != shape or col < 0 or col % 4 or col + width > out.shape[3]:
+        raise RuntimeError(f'{name}: output {tuple(out.shape)} does not hold columns {col} .. {col + width - 1} of a {shape} image')
+    return out
+
+
+def conv2d_relu_f32(x, w, bias, stride=1, padding=(0, 0), relu=True, out=None, col=0):
+    """act(conv2d(x, w) + bias) (sidlsg_conv2d_relu_f32).  x [B, H, W, ldx] fp32 NHWC, of which the first Cin channels are read;
+    w [Cout, KH, KW, Cin]; bias [Cout] (the folded BatchNorm shift).  -> [B, Ho, Wo, Cout], or columns col .. col + Cout - 1 of
+    `out` [B, Ho, Wo, ldc]: a branch writes its slice of the block's output and the other columns keep their bits."""
+    _chk(x, F32), _chk(w, F32), _chk(bias, F32)
+    if x.dim() != 4 or w.dim() != 4 or x.shape[3] < w.shape[3] or bias.shape != (w.shape[0],):
+        raise RuntimeError(f'conv2d_relu_f32: x {tuple(x.shape)}, w {tuple(w.shape)}, bias {tuple(bias.shape)}')
+    B, H, W, ldx = x.shape
+    Cout, KH, KW, Cin = w.shape
+    ph, pw = padding
+    Ho, Wo = (H + 2 * ph - KH) // stride + 1, (W + 2 * pw - KW) // stride + 1
+    if Ho < 1 or Wo < 1:
+        raise RuntimeError(f'conv2d_relu_f32: a {KH} x {KW} kernel does not fit a {H} x {W} image with padding {padding}')
+    out = _slice_out('conv2d_relu_f32', out, (B, Ho, Wo), col, Cout, x.device)
+    lib.sidlsg_conv2d_relu_f32(_p(x), ldx, _p(w), out.data_ptr() + 4 * col, out.shape[3], _p(bias), B, H, W, Cin, Cout, KH, KW, stride, ph, pw,
+                               1 if relu else 0, _s())
+    return out
+
+
+def pool2d_f32(x, k, stride, pad=0, mode=POOL_MAX, out=None, col=0):
+    """k x k pooling of x [B, H, W, C] fp32 NHWC (sidlsg_pool2d_f32): POOL_MAX (the bits of F.max_pool2d) or POOL_MEAN over the taps
+    inside the image (count_include_pad=False).  -> [B, Ho, Wo, C], or columns col .. col + C - 1 of `out` [B, Ho, Wo, ldy]."""
+    _chk(x, F32)
+    if x.dim() != 4:
+        raise RuntimeError(f'pool2d_f32: x {tuple(x.shape)}: expected [B, H, W, C]')
+    B, H, W, C = x.shape
+    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    if Ho < 1 or Wo < 1:
+        raise RuntimeError(f'pool2d_f32: a {k} x {k} window does not fit a {H} x {W} image with padding {pad}')
+    out = _slice_out('pool2d_f32', out, (B, Ho, Wo), col, C, x.device)
+    lib.sidlsg_pool2d_f32(_p(x), C, out.data_ptr() + 4 * col, out.shape[3], B, H, W, C, k, stride, pad, int(mode), _s())
+    return out
+
+
+def inception_input_u8(images, out=None):
+    """uint8 NCHW [B, 3, H, W] -> [B, 299, 299, 4] fp32 NHWC (sidlsg_inception_input_u8): the detector's legacy-TF bilinear resize and
+    (v - 128) / 128 in one launch; channel 3 is zero (the stem convolution has zero weights there)."""
+    _chk(images, torch.uint8)
+    if images.dim() != 4 or images.shape[1] != 3:
+        raise RuntimeError(f'inception_input_u8: expected uint8 [B, 3, H, W], got {tuple(images.shape)}')
+    B, _, H, W = images.shape
+    if out is None:
+        out = torch.empty((B, 299, 299, 4), device=images.device, dtype=F32)
+    elif _chk(out, F32).shape != (B, 299, 299, 4):
+        raise RuntimeError(f'inception_input_u8: output {tuple(out.shape)} for {B} images')
+    lib.sidlsg_inception_input_u8(_p(images), _p(out), B, H, W, _s())
+    return out
+
+
 def _det_synced(backward):
     @functools.wraps(backward)
     def wrapper(*args):

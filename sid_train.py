@@ -140,9 +140,12 @@ def build_config(o):
         # --data_stat may be left out when the statistics can be computed from the images of --data
         hps = [m for m in o.metrics if m in _metrics.HPS_METRICS]      # scored by --metric_hps_path alone: no Inception file, no statistics
         cmmd = [m for m in o.metrics if m in _metrics.CMMD_METRICS]    # scored by --metric_cmmd_clip_path and the real images: likewise
-        need_stat = o.data_stat is not None or (len(needs_images) + len(hps) < len(o.metrics) and not has_images)
+        inception_score = [m for m in o.metrics if m in _metrics.IS_METRICS]      # the detector's class probabilities of the generated images: no statistics
+        need_stat = o.data_stat is not None or (len(needs_images) + len(hps) + len(inception_score) < len(o.metrics) and not has_images)
         need_pt = len(hps) + len(cmmd) < len(o.metrics)
         for flag, path in ((('--metric_pt_path', o.metric_pt_path),) if need_pt else ()) + ((('--data_stat', o.data_stat),) if need_stat else ()):
+            if flag == '--metric_pt_path' and _metrics.is_inception_spec(path):      # random:inception-v3[:seed], built by sid_lsg_amd.inception
+                continue
             if not path or not os.path.isfile(path):
                 raise click.ClickException(f'--metrics needs {flag} to be a local file (got {path!r})')
         if hps:

@@ -2,7 +2,7 @@
 """Per-shape kernel micro-benchmarks on the SD1.5 work list -- the optimisation harness.
 Prints achieved TFLOP/s (contractions) or GB/s (HBM-bound kernels) per shape.  GPU only.
 
-    python tools/bench_kernels.py [conv] [gemm] [wgrad] [attn] [norm] [geglu] [fp8] [pr] [mmd] [--batch 16]
+    python tools/bench_kernels.py [conv] [gemm] [wgrad] [attn] [norm] [geglu] [fp8] [pr] [mmd] [inception] [--batch 16]
 """
 import os
 import sys
@@ -283,6 +283,55 @@ def bench_mmd(_B, rounds=5):
             out.append(torch.stack([((p @ q.t() / F + 1.0) ** 3).double().sum() for p, q in ((a, a), (b, b), (a, b))]))
         return torch.stack(out)
     report('poly3', lambda: ops.pair_kernel_sums(x, y, ops.PAIR_KERNEL_POLY3, 1.0 / F, 1.0, ix, iy)[:, :3], poly_ref, S * 3 * 2.0 * m * m * F)
+
+
+def bench_inception(_B, batch=64, rounds=3):
+    """The FID Inception-v3 (sid_lsg_amd.inception.HipInceptionV3, seeded weights) at batch 64 from 256 x 256 uint8 images: images / s,
+    the same for the torch.nn restatement of tests/inception_ref.py on this device (fp32, MIOpen; for information only), and the
+    five convolutions that cost the most per launch."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests'))
+    import inception_ref
+    from sid_lsg_amd import inception
+    net = inception_ref.seeded_net(0)
+    det = inception.HipInceptionV3(net.state_dict(), dev)
+    net = net.to(dev)
+    img = inception_ref.structured_images(batch, 256, 256, seed=1).to(dev)
+    print(f'--- Inception-v3 features, batch {batch} from 256 x 256 uint8: images / s, {rounds} alternating rounds')
+    with torch.no_grad():
+        a, b = det(img, return_features=True), net(img, return_features=True)
+        print(f'  results: relative l2 between the two paths, worst image {float(((a - b).norm(dim=1) / b.norm(dim=1)).max()):.2e}')
+        times = dict(hip=[], torch=[])
+        for _ in range(rounds):
+            times['hip'].append(timeit(lambda: det(img, return_features=True), iters=3, warm=1))
+            times['torch'].append(timeit(lambda: net(img, return_features=True), iters=3, warm=1))
+    for k, ts in times.items():
+        med = sorted(ts)[len(ts) // 2]
+        print(f'  {k:6s}: ' + ' '.join(f'{t * 1e3:8.2f}' for t in ts) + f' ms   median {batch / med:8.0f} images / s')
+    print(f'  peak memory of the process: {torch.cuda.max_memory_allocated() / 2 ** 20:.0f} MiB')
+    # every convolution launch of one pass, timed on its own
+    launches, conv = [], ops.conv2d_relu_f32
+
+    def timed(x, w, bias, **kw):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = conv(x, w, bias, **kw)
+        e1.record()
+        launches.append((e0, e1, tuple(x.shape), tuple(w.shape), kw.get('stride', 1), out.shape[1] * out.shape[2]))
+        return out
+    ops.conv2d_relu_f32 = timed
+    try:
+        det(img, return_features=True)
+    finally:
+        ops.conv2d_relu_f32 = conv
+    torch.cuda.synchronize()
+    rows = []
+    for e0, e1, xs, ws, stride, pixels in launches:
+        t = e0.elapsed_time(e1) * 1e-3
+        rows.append((t, xs, ws, stride, 2.0 * xs[0] * pixels * ws[0] * ws[1] * ws[2] * ws[3]))
+    total_t, total_f = sum(r[0] for r in rows), sum(r[4] for r in rows)
+    print(f'  {len(rows)} convolution launches: {total_t * 1e3:.2f} ms, {total_f / total_t / 1e12:.1f} TFLOP/s over all of them; the five costliest:')
+    for t, xs, ws, stride, fl in sorted(rows, reverse=True)[:5]:
+        print(f'    x {xs} w {ws} stride {stride}: {t * 1e6:8.1f} us  {fl / t / 1e12:6.1f} TFLOP/s')
 
 
 if __name__ == '__main__':

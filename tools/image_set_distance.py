@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """KID and / or CMMD between two folders of PNG / JPEG images, e.g. a real set and a generate_onestep.py run scored after the fact.
     python tools/image_set_distance.py --real DIR --fake DIR [--kid --detector FILE] [--cmmd --clip DIR] [--batch 64]
---kid: the Inception detector file of FID (TorchScript, metrics.load_detector); the real images as stored, the generated ones resized
+--kid: the Inception detector of FID (a TorchScript file, a state-dict .pth or random:inception-v3; metrics.load_detector); the real images as stored, the generated ones resized
 to 256 x 256 with Pillow's LANCZOS arithmetic, as the metrics treat them; 100 subsets of at most 1000 -- what `kid30k_full` reports.  --cmmd: the image tower of a local CLIP directory in
 the Hugging Face layout (ViT-L/14-336 in the published CMMD; or 'random:clip-<arch>'), images straight from their own sizes --
 what `cmmd30k_full` reports.  Both sums run on sidlsg_pair_kernel_sums (fp32 MFMA, fp64 accumulation)."""
@@ -54,7 +54,7 @@ def main(argv=None):
     ap.add_argument('--real', required=True)
     ap.add_argument('--fake', required=True)
     ap.add_argument('--kid', action='store_true')
-    ap.add_argument('--detector', help='--kid: the TorchScript Inception file of FID')
+    ap.add_argument('--detector', help='--kid: the Inception detector of FID: a TorchScript file, a state-dict .pth, or random:inception-v3')
     ap.add_argument('--cmmd', action='store_true')
     ap.add_argument('--clip', help="--cmmd: a CLIP directory in the Hugging Face layout, or 'random:clip-<arch>'")
     ap.add_argument('--batch', type=int, default=64)
