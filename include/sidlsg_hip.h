@@ -203,7 +203,10 @@ int sidlsg_trace_read(int family, double* out);
 /* ---- attention (diffusers Attention + AttnProcessor2_0 / xformers; sid_sd_util.py:102-113) --
  * O = softmax(Q K^T D^-1/2) V per head; Q/K/V/O are strided views ([b][token][h*D + d], token
  * stride ld*, batch stride bs*, in elements) so the fused QKV projection is consumed in place.
- * D multiple of 8, <= 160.  LSE [B][H][Nq] fp32 (log2 domain) is saved for backward. */
+ * Admitted head widths: D a multiple of 8 whose round-up to a multiple of 16 is one of 16, 32, 48, 64, 80, 96, 128 or 160, the
+ * widths the kernels are tiled for -- D = 8, 16, ..., 96, 120, 128, 152, 160.  Every other D (104, 112, 136 and 144 among them)
+ * returns SIDLSG_EINVAL from the forward and the backward, plain and _ps, before anything is launched or written.
+ * LSE [B][H][Nq] fp32 (log2 domain) is saved for backward. */
 int sidlsg_attn_fwd(const void* Q, const void* K, const void* V, void* O, float* LSE, int B, int H, int Nq, int Nk, int D,
                     int ldq, int ldk, int ldv, int ldo, long long bsq, long long bsk, long long bsv, long long bso,
                     void* stream);
@@ -581,7 +584,8 @@ int sidlsg_layernorm_fwd_fp8_g2(const void* x, const float* gamma, const float* 
  * HipUNet2DCondition(compute_dtype=torch.float32); used by the parity suite to assert north_star's 1e-3 bound.
  * Differences: K, lda, ldx, ldy multiples of 4; flags: only SIDLSG_SILU / SIDLSG_ACCUM (C is always fp32); the
  * weight-gradient entry points take dBias = NULL (the bias gradient is a sidlsg_colsum_f32 call); no workspace is used;
- * sidlsg_transpose_w(_batched)_f32 write fp32 destinations. */
+ * sidlsg_transpose_w(_batched)_f32 write fp32 destinations; sidlsg_attn_fwd_f32 / _bwd_f32 take D a multiple of 4 with the
+ * same round-up rule as the bf16 attention (16, 32, 48, 64, 80, 96, 128 or 160), SIDLSG_EINVAL otherwise. */
 int sidlsg_gemm_f32(const void* A, int lda, const void* W, void* C, int ldc, const float* bias, const void* res, int ldres,
                     const float* rowvec, int ld_rowvec, int rows_per_batch, int M, int N, int K, float alpha, int flags,
                     void* stream);

@@ -1180,6 +1180,17 @@ def norm_linear_mx8(x, gamma, beta, eps, w8, bias, w16t, weight, groups=0, silu=
 _ATTN_ALWAYS_KV = os.environ.get('SIDLSG_ATTN_SKIP_KV', '1') == '0'      # A/B switch: compute dK / dV even when nobody wants them
 
 
+ATTN_HEAD_WIDTHS = (16, 32, 48, 64, 80, 96, 128, 160)      # the head widths csrc/attention.hip and csrc/fp32.hip are tiled for
+
+
+def _attn_head_width(D, dtype):
+    """The widths sidlsg_attn_fwd / _bwd (and _ps, _f32) admit, include/sidlsg_hip.h: said here in words, not as code -22."""
+    step = 4 if dtype == F32 else 8
+    if D <= 0 or D % step or (D + 15) // 16 * 16 not in ATTN_HEAD_WIDTHS:
+        raise RuntimeError(f'attention: head width {D} is not admitted: it must be a multiple of {step} whose round-up to a multiple of 16 '
+                           f'is one of {", ".join(map(str, ATTN_HEAD_WIDTHS))} (there are no kernels for 112 and 144)')
+
+
 class _Attention(torch.autograd.Function):
     """q: [B,Nq,*] view with heads*D channels starting at column qoff of a row of width ldq; same for k, v."""
 
@@ -1192,6 +1203,7 @@ class _Attention(torch.autograd.Function):
         sfx = '_ps' if (prescaled and qbuf.dtype == BF16) else ''
         if prescaled and not sfx:
             raise RuntimeError('pre-scaled queries exist in the bf16 compute mode only')
+        _attn_head_width(D, qbuf.dtype)
         B, Nq, ldq = qbuf.shape
         Nk, ldk = kvbuf.shape[1], kvbuf.shape[2]
         C = heads * D
