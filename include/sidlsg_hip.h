@@ -30,7 +30,13 @@ extern "C" {
  * torch.nn.functional.linear / conv2d(k=1) inside diffusers Attention / FeedForward /
  * Transformer2DModel / ResnetBlock2D.time_emb_proj / conv_shortcut (call site sid_sd_util.py:184).
  * C[M][ldc] = act(alpha * A[M][K] W[N][K]^T + bias[N] + rowvec[m/rows_per_batch][ld_rowvec] + res[M][ldres])
- * K, lda multiples of 8.  bias/res/rowvec may be NULL; ld_rowvec <= 0 means N (a slice of a wider matrix otherwise). */
+ * K, lda multiples of 8.  bias/res/rowvec may be NULL; ld_rowvec <= 0 means N (a slice of a wider matrix otherwise).
+ * Operand contract (this entry point, sidlsg_conv3x3_bf16, their _g2 / _fp8w / _mx8 forms; SIDLSG_EINVAL otherwise): row strides in
+ * elements of the operand's type; lda >= K (conv: ldx >= Cin), ldc >= N, ldres >= N, ld_rowvec >= N when given.  C, res and the operands
+ * may be views into wider buffers: only columns [0, N) of rows [0, M) are written, nothing else of C is touched, and only columns
+ * [0, K) / [0, N) of A / res are read.  N % 8 == 0 selects the vector epilogue, which moves 16 bytes per access (8 bf16 or 4 fp32, at
+ * column offsets that are multiples of 8 resp. 4): then C, res, rowvec, bias (and bias1) must be 16-byte aligned, ldc and ldres
+ * multiples of 8 (ldc of 4 for an fp32 C) and ld_rowvec a multiple of 4.  Any other N takes an element-wise epilogue without these. */
 int sidlsg_gemm_bf16(const void* A, int lda, const void* W, void* C, int ldc, const float* bias, const void* res, int ldres,
                      const float* rowvec, int ld_rowvec, int rows_per_batch, int M, int N, int K, float alpha, int flags,
                      void* stream);
@@ -108,6 +114,53 @@ int sidlsg_debug_wgrad_blocks_per_cu(int which); /* host diagnostic: resident bl
 int sidlsg_debug_set_p8(int mode); /* A/B switch: which GEMM / conv calls take the 256-row-tile kernels (csrc/gemm_p8.h): -1 by rule (default), 0 never, 1 / 2 always the 256x160 / 256x320 configuration when admissible; returns the previous setting */
 int sidlsg_conv3x3_wgrad_bf16(const void* dY, int ldy, const void* X, int ldx, float* dW, float* dBias, int B, int H, int Wd,
                               int Cin, int Cout, int stride, int ups, void* stream);
+
+/* ---- dispatch record (host diagnostic; tests/gemm_cases.py) ----------------------------------
+ * Which kernel a GEMM / conv / weight-gradient entry point chose.  Every host launcher of csrc/gemm.hip and csrc/gemm_p8.h writes a
+ * thread-local record of SIDLSG_REC_INTS ints just before it launches: a handful of plain stores, no HIP call, nothing about the
+ * launch changes.  The record is written BEFORE the launch, so it is there also when the launch itself fails (no device).
+ * sidlsg_debug_last_launch copies the record of the calling thread's last such call: out[SIDLSG_REC_*], at most n ints; returns
+ * the number of ints copied, or SIDLSG_EINVAL for a NULL out or n < 1.  A call that was rejected with SIDLSG_EINVAL before its
+ * launcher leaves the record of the call before it; SIDLSG_REC_SEQ counts the records written by the thread, so a caller can tell.
+ * The numbers below are part of the ABI (tests parse them from this header): add at the end, never renumber. */
+enum sidlsg_kernel_id {
+    SIDLSG_K_NONE = 0,                /* no launcher has run on this thread yet */
+    SIDLSG_K_GEMM_BF16 = 1,           /* gemm_bf16_kernel<BM, BN, MODE, PAD>: register-staged tiles */
+    SIDLSG_K_GEMM_V3 = 2,             /* gemm_v3_kernel<MODE>: 128 x 160, direct-to-LDS (also under the GEGLU fusions) */
+    SIDLSG_K_GEMM_P8S = 3,            /* gemm_p8s_kernel<MODE>: 256 x 160 */
+    SIDLSG_K_GEMM_P8W = 4,            /* gemm_p8w_kernel<MODE>: 256 x 320 */
+    SIDLSG_K_GEMM_P8W_GEGLU = 5,      /* gemm_p8w_geglu_kernel */
+    SIDLSG_K_GEMM_P8W_GEGLU_BWD = 6,  /* gemm_p8w_geglu_bwd_kernel */
+    SIDLSG_K_GEMM_AS = 7,             /* gemm_as_kernel<5, RES>: A-stationary, K = 320 */
+    SIDLSG_K_GEMM_MX8 = 8,            /* gemm_mx8_kernel<MODE>: e4m3 x e4m3 */
+    SIDLSG_K_GEMM_FP8W = 9,           /* gemm_fp8w_kernel<MODE>: bf16 x e4m3 weights */
+    SIDLSG_K_WGRAD_BF16 = 10,         /* wgrad_bf16_kernel<MODE>: unaligned operands */
+    SIDLSG_K_WGRAD_V2 = 11,           /* wgrad_v2_kernel<MODE>: 128 x 128 */
+    SIDLSG_K_WGRAD_V2W = 12,          /* wgrad_v2w_kernel<MODE>: 160 x 128 */
+    SIDLSG_K_WGRAD_V2F = 13,          /* wgrad_v2f_kernel: conv, 128 x 128, constant-advance gather */
+    SIDLSG_K_WGRAD_V2WF = 14,         /* wgrad_v2wf_kernel: conv, 160 x 128, constant-advance gather */
+    SIDLSG_K_WGRAD_V2S = 15,          /* wgrad_v2s_kernel: dense, 160 x 160 */
+    SIDLSG_K_WGRAD_V2G = 16,          /* wgrad_v2g_kernel: grouped dense, 128 x 128 */
+    SIDLSG_K_WGRAD_V2SG = 17          /* wgrad_v2sg_kernel: grouped dense, 160 x 160 */
+};
+enum sidlsg_launch_record {
+    SIDLSG_REC_KERNEL = 0,  /* enum sidlsg_kernel_id */
+    SIDLSG_REC_BM = 1,      /* tile rows (weight gradients: tile extent along N) */
+    SIDLSG_REC_BN = 2,      /* tile columns (weight gradients: tile extent along K) */
+    SIDLSG_REC_MODE = 3,    /* the kernel's MODE: GEMM family 0 dense, 1 conv with Cin % 64 == 0, 2 any conv; weight gradients 0 dense, 1 conv */
+    SIDLSG_REC_PAD = 4,     /* gemm_bf16_kernel's PAD (1: pad 1 on all sides, 0: bottom / right only); -1 for every other kernel */
+    SIDLSG_REC_P8 = 5,      /* p8 configuration: 0 = 256 x 160, 1 = 256 x 320; -1: not a p8 kernel */
+    SIDLSG_REC_SPLITS = 6,  /* K splits (GEMM / conv) or pixel splits (weight gradients; a grouped launch: the largest of its jobs); 1 = none */
+    SIDLSG_REC_PARTIAL = 7, /* where partial sums went: SIDLSG_PART_* */
+    SIDLSG_REC_FINISH = 8,  /* kernels that followed: bit mask of SIDLSG_FIN_* */
+    SIDLSG_REC_SEQ = 9,     /* records written by this thread so far, this one included */
+    SIDLSG_REC_INTS = 10
+};
+enum sidlsg_launch_partial { SIDLSG_PART_ONE = 0 /* one split: the kernel finishes its output */, SIDLSG_PART_SLABS = 1 /* fp32 slabs in the workspace */,
+                             SIDLSG_PART_ATOMICS = 2 /* fp32 atomics onto the output */ };
+enum sidlsg_launch_finish { SIDLSG_FIN_GEMM = 1 /* gemm_finish_kernel */, SIDLSG_FIN_WGRAD_REDUCE = 2 /* wgrad_reduce(_g)_kernel */,
+                            SIDLSG_FIN_COLSUM = 4 /* deterministic mode: the bias gradient as a column sum of dY */ };
+int sidlsg_debug_last_launch(int* out, int n);
 
 /* ---- deterministic mode --------------------------------------------------------------------
  * Process-wide switch (like sidlsg_debug_set_p8); initial value from the environment variable SIDLSG_DETERMINISTIC (unset or 0: off).

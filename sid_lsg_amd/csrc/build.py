@@ -28,6 +28,8 @@ def digest():
     for f in SOURCES + ['common.h', 'gemm_p8.h', 'bias_act_kernel.h']:
         with open(os.path.join(HERE, f), 'rb') as fh:
             h.update(fh.read())
+    with open(os.path.join(os.path.dirname(PKG), 'include', 'sidlsg_hip.h'), 'rb') as fh:      # gemm.hip includes the C ABI header
+        h.update(fh.read())
     h.update((' '.join(FLAGS) + repr(sorted(EXTRA.items()))).encode())
     return h.hexdigest()
 

@@ -24,6 +24,7 @@
 // pixel) and W-tile rows are permuted per tile pair so that each lane ends up with 8 consecutive output channels of one
 // pixel: the epilogue stores 16 bytes per lane.
 #include "common.h"
+#include "../../include/sidlsg_hip.h"      // the kernel ids of the dispatch record (and a compile-time check of the C ABI against its definitions)
 #include <stdlib.h>
 #include <algorithm>
 #include <type_traits>
@@ -758,9 +759,24 @@ bool sidlsg_det() {
     return g_det_mode == 1;
 }
 
+// Dispatch record (include/sidlsg_hip.h sidlsg_debug_last_launch): every host launcher below and in gemm_p8.h says which kernel it is
+// about to launch, just before its SIDLSG_LAUNCH -- plain stores to a thread-local struct, so the record is complete also when the launch
+// fails.  A launcher of a second kernel (gemm_finish_kernel, the slab reductions) adds its bit to `finish`.
+struct LaunchRecord { int v[SIDLSG_REC_INTS]; };
+static thread_local LaunchRecord g_last_launch = {};
+static inline void record_launch(int kernel, int bm, int bn, int mode, int pad, int p8, int splits, int partial) {
+    int* r = g_last_launch.v;
+    r[SIDLSG_REC_KERNEL] = kernel; r[SIDLSG_REC_BM] = bm; r[SIDLSG_REC_BN] = bn; r[SIDLSG_REC_MODE] = mode; r[SIDLSG_REC_PAD] = pad;
+    r[SIDLSG_REC_P8] = p8; r[SIDLSG_REC_SPLITS] = splits; r[SIDLSG_REC_PARTIAL] = partial; r[SIDLSG_REC_FINISH] = 0; r[SIDLSG_REC_SEQ]++;
+}
+static inline void record_followup(int fin) { g_last_launch.v[SIDLSG_REC_FINISH] |= fin; }
+// a split-K GEMM launcher: `splits` slabs when p.kt_per_split is set
+static inline int record_partial(int splits) { return splits > 1 ? SIDLSG_PART_SLABS : SIDLSG_PART_ONE; }
+
 // Second launch of a split-K GEMM: the `splits` slabs of p.ws -> C through the epilogue (gemm_finish_kernel, four outputs per thread).
 static void launch_gemm_finish(const GemmParams& p, int splits, hipStream_t s) {
     const size_t n4 = ((size_t)p.M * p.N + 3) / 4;
+    record_followup(SIDLSG_FIN_GEMM);
     SIDLSG_LAUNCH(gemm_finish_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, p, splits);
 }
 
@@ -1250,6 +1266,7 @@ static int launch_gemm_v3(const GemmParams& p, hipStream_t s) {
     GemmParams q = p;
     static const int group_env = getenv("SIDLSG_GEMM_GROUP_M") ? atoi(getenv("SIDLSG_GEMM_GROUP_M")) : 4;   // A/B switch (measured: 4 and 8 equivalent, 1 = row-major strips)
     q.group_m = group_env < 1 ? 1 : group_env;
+    record_launch(SIDLSG_K_GEMM_V3, 128, 160, MODE, -1, -1, splits, p.kt_per_split ? SIDLSG_PART_SLABS : SIDLSG_PART_ONE);
     SIDLSG_LAUNCH((gemm_v3_kernel<MODE>), dim3(tiles * splits), dim3(NTHREADS), lds, s, q);
     if (p.kt_per_split) launch_gemm_finish(p, splits, s);
     return sidlsg_last_error();
@@ -1539,6 +1556,7 @@ static int launch_gemm_mx8(const GemmParams& p, hipStream_t s) {
         q.ws = w.ptr;
         splits = (nk + q.kt_per_split - 1) / q.kt_per_split;
     }
+    record_launch(SIDLSG_K_GEMM_MX8, 128, 160, MODE, -1, -1, splits, record_partial(splits));
     SIDLSG_LAUNCH((gemm_mx8_kernel<MODE>), dim3(tiles * splits), dim3(NTHREADS), lds, s, q);
     if (splits > 1) launch_gemm_finish(q, splits, s);
     return sidlsg_last_error();
@@ -1803,6 +1821,7 @@ static int launch_gemm_as(const GemmParams& p, hipStream_t s) {
     GemmParams q = p;
     q.group_m = tpi;
     const int items = panels * ((tiles_n + tpi - 1) / tpi);
+    record_launch(SIDLSG_K_GEMM_AS, 128, 160, 0, -1, -1, 1, SIDLSG_PART_ONE);
     if (p.res) SIDLSG_LAUNCH((gemm_as_kernel<NKT, true>), dim3(items), dim3(NTHREADS), lds, s, q);
     else SIDLSG_LAUNCH((gemm_as_kernel<NKT, false>), dim3(items), dim3(NTHREADS), lds, s, q);
     return sidlsg_last_error();
@@ -1826,6 +1845,7 @@ static int launch_gemm(const GemmParams& p, hipStream_t s) {
     }
     const int nk = (p.K + BK - 1) / BK;
     const int splits = p.kt_per_split ? (nk + p.kt_per_split - 1) / p.kt_per_split : 1;
+    record_launch(SIDLSG_K_GEMM_BF16, BM, BN, MODE, PAD, -1, splits, p.kt_per_split ? SIDLSG_PART_SLABS : SIDLSG_PART_ONE);
     SIDLSG_LAUNCH((gemm_bf16_kernel<BM, BN, MODE, PAD>), dim3(tiles, splits), dim3(NTHREADS), lds, s, p);
     if (p.kt_per_split) launch_gemm_finish(p, splits, s);
     return sidlsg_last_error();
@@ -1950,6 +1970,21 @@ static int check_common(const GemmParams& p) {
     if (!p.A || !p.W || !p.C) return SIDLSG_EINVAL;
     if (p.rowvec && p.rows_per_batch <= 0) return SIDLSG_EINVAL;
     if ((p.flags & F_ACCUM) && !(p.flags & F_OUT_F32)) return SIDLSG_EINVAL;
+    return SIDLSG_OK;
+}
+
+// Operand contract of the output and the epilogue operands (include/sidlsg_hip.h "operand contract"): rows no narrower than the N columns
+// the kernel touches, and -- N % 8 == 0: the vector epilogue (epilogue_rows8, gemm_store_rows, the p8 row-major epilogue, gemm_finish_kernel)
+// moves 16 bytes per access at column offsets that are multiples of 8 (4 for fp32 data) -- strides and base addresses that keep those aligned.
+static int check_epilogue(const GemmParams& p) {
+    if (p.lda < (p.Cin ? p.Cin : p.K) || p.ldc < p.N || (p.res && p.ldres < p.N) || (p.rowvec && p.ldrv < p.N)) return SIDLSG_EINVAL;
+    if ((p.N & 7) == 0) {
+        auto misaligned = [](const void* q) { return ((uintptr_t)q & 15) != 0; };
+        if ((p.ldc & ((p.flags & F_OUT_F32) ? 3 : 7)) || misaligned(p.C)) return SIDLSG_EINVAL;
+        if (p.res && ((p.ldres & 7) || misaligned(p.res))) return SIDLSG_EINVAL;
+        if (p.rowvec && ((p.ldrv & 3) || misaligned(p.rowvec))) return SIDLSG_EINVAL;
+        if (misaligned(p.bias) || misaligned(p.bias1)) return SIDLSG_EINVAL;
+    }
     return SIDLSG_OK;
 }
 
@@ -2687,6 +2722,18 @@ static int launch_wgrad(WgradParams p, hipStream_t s) {
     const int splits = ps.splits;
     p.m_per_split = ps.mps;
     p.nsplits = splits;
+    bool cf = false;
+    if (v2 && MODE == 1 && !p.slow_gather && !p.ups && p.H == p.Ho * p.stride) {          // conditions of the constant-advance gather (wgrad_v2_body, fastc)
+        const int hw = p.Ho * p.Wo, d_b = WG_MB / hw, d_rem = WG_MB - d_b * hw;
+        const int d_wo = d_rem - (d_rem / p.Wo) * p.Wo;
+        const unsigned long long rowb = (unsigned long long)p.Wd * p.lda * 2ull;
+        cf = d_wo == 0 && (unsigned long long)p.a_bytes + rowb < 0x7fffffffull;
+    }
+    record_launch(!v2 ? SIDLSG_K_WGRAD_BF16 : sq160 ? SIDLSG_K_WGRAD_V2S : cf ? (tn == 160 ? SIDLSG_K_WGRAD_V2WF : SIDLSG_K_WGRAD_V2F)
+                                            : tn == 160 ? SIDLSG_K_WGRAD_V2W : SIDLSG_K_WGRAD_V2,
+                  tn, tk, MODE, -1, -1, splits, splits <= 1 ? SIDLSG_PART_ONE : p.ws ? SIDLSG_PART_SLABS : SIDLSG_PART_ATOMICS);
+    if (splits > 1 && p.ws) record_followup(SIDLSG_FIN_WGRAD_REDUCE);
+    if (det_dB) record_followup(SIDLSG_FIN_COLSUM);
     if (p.assign && splits > 1 && !p.ws) {         // fp32-atomic fallback (no slab space): the atomics need a zeroed target
         if (hipMemsetAsync(p.dW, 0, (size_t)nk * sizeof(float), s) != hipSuccess) return sidlsg_last_error();
     }
@@ -2700,13 +2747,6 @@ static int launch_wgrad(WgradParams p, hipStream_t s) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_v2f_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, wgrad_v2_lds(128, WG_T));
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_v2wf_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, wgrad_v2_lds(160, WG_T));
             attr_done = true;
-        }
-        bool cf = false;
-        if (MODE == 1 && !p.slow_gather && !p.ups && p.H == p.Ho * p.stride) {          // conditions of the constant-advance gather (wgrad_v2_body, fastc)
-            const int hw = p.Ho * p.Wo, d_b = WG_MB / hw, d_rem = WG_MB - d_b * hw;
-            const int d_wo = d_rem - (d_rem / p.Wo) * p.Wo;
-            const unsigned long long rowb = (unsigned long long)p.Wd * p.lda * 2ull;
-            cf = d_wo == 0 && (unsigned long long)p.a_bytes + rowb < 0x7fffffffull;
         }
         if (sq160) SIDLSG_LAUNCH(wgrad_v2s_kernel, dim3(tiles * splits), dim3(NTHREADS), lds, s, p);
         else if (cf && tn == 160) SIDLSG_LAUNCH(wgrad_v2wf_kernel, dim3(tiles * splits), dim3(NTHREADS), lds, s, p);
@@ -2772,6 +2812,16 @@ static int launch_wgrad_group(WgradParams* jobs, int njobs, hipStream_t s, bool 
             rjobs++;
         }
     }
+    {
+        int max_splits = 1;
+        for (int i = 0; i < njobs; i++) max_splits = std::max(max_splits, g.j[i].nsplits);
+        bool det_bias = false;
+        for (int i = 0; i < njobs; i++) det_bias = det_bias || det_dB[i];
+        record_launch(t160 ? SIDLSG_K_WGRAD_V2SG : SIDLSG_K_WGRAD_V2G, t160 ? 160 : 128, t160 ? 160 : WG_T, 0, -1, -1, max_splits,
+                      rjobs ? SIDLSG_PART_SLABS : SIDLSG_PART_ONE);
+        if (rjobs) record_followup(SIDLSG_FIN_WGRAD_REDUCE);
+        if (det_bias) record_followup(SIDLSG_FIN_COLSUM);
+    }
     g.blk0[njobs] = blocks;
     rg.njobs = rjobs; rg.blk0[rjobs] = rblocks;
     const size_t lds = (size_t)(t160 ? wgrad_v2_lds(160, 160) : wgrad_v2_lds(128, WG_T));
@@ -2818,6 +2868,14 @@ int sidlsg_debug_set_p8(int mode) {
     return old;
 }
 
+// (diagnostic) the dispatch record of the calling thread's last GEMM / conv / weight-gradient call: see include/sidlsg_hip.h
+int sidlsg_debug_last_launch(int* out, int n) {
+    if (!out || n < 1) return SIDLSG_EINVAL;
+    const int m = std::min(n, (int)SIDLSG_REC_INTS);
+    for (int i = 0; i < m; i++) out[i] = g_last_launch.v[i];
+    return m;
+}
+
 // Optional scratch for split-K GEMMs and weight gradients: `ptr` = device memory of `bytes` bytes, owned by the
 // caller, used by every later sidlsg_gemm_bf16 / sidlsg_conv3x3_bf16 call of this process (one stream at a time).
 // Pass NULL/0 to disable split-K.
@@ -2850,6 +2908,7 @@ static int gemm_bf16_impl(bool g2, const void* A, int lda, const void* W, const 
     if (int e = check_common(p)) return e;
     if (!range31(p.a_bytes, M, lda, K, 2) || !range31(p.w_bytes, N, K, K, 2)) return SIDLSG_EINVAL;
     set_group2(p, g2, W1, nullptr, bias1);
+    if (int e = check_epilogue(p)) return e;
     return dispatch_gemm<0>(p, (hipStream_t)stream);
 }
 int sidlsg_gemm_bf16(const void* A, int lda, const void* W, void* C, int ldc, const float* bias, const void* res,
@@ -2947,6 +3006,7 @@ static int conv3x3_bf16_impl(bool g2, const void* X, int ldx, const void* W, con
     if (int e = check_common(p)) return e;
     if (!range31(p.a_bytes, conv_src_pixels(B, H, Wd, ups), ldx, Cin, 2) || !range31(p.w_bytes, 9ull * Cout, Cin, Cin, 2)) return SIDLSG_EINVAL;
     set_group2(p, g2, W1, nullptr, bias1);
+    if (int e = check_epilogue(p)) return e;
     if (Cin % 64 == 0) return dispatch_gemm<1>(p, (hipStream_t)stream);
     return dispatch_gemm<2>(p, (hipStream_t)stream);
 }
@@ -3078,7 +3138,9 @@ static int gemm_fp8w_impl(bool g2, const void* A, int lda, const void* W8, const
     if ((K & 15) || !wscale) return SIDLSG_EINVAL;
     if (!range31(p.a_bytes, M, lda, K, 2) || !range31(p.w_bytes, N, K, K, 1)) return SIDLSG_EINVAL;
     set_group2(p, g2, W8_1, wscale1, bias1);
+    if (int e = check_epilogue(p)) return e;
     const int tiles = m_tiles_rt(p, F8_T) * ((N + F8_T - 1) / F8_T);
+    record_launch(SIDLSG_K_GEMM_FP8W, F8_T, F8_T, 0, -1, -1, 1, SIDLSG_PART_ONE);
     SIDLSG_LAUNCH((gemm_fp8w_kernel<0>), dim3(tiles), dim3(NTHREADS), 0, (hipStream_t)stream, p);
     return sidlsg_last_error();
 }
@@ -3107,6 +3169,7 @@ static int gemm_mx8_impl(bool g2, const void* A8, int lda, const void* W8, const
     p.wscale = wscale;
     if (!range31(p.a_bytes, M, lda, K, 1) || !range31(p.w_bytes, N, K, K, 1)) return SIDLSG_EINVAL;      // extents in bytes of e4m3
     set_group2(p, g2, W8_1, wscale1, bias1);
+    if (int e = check_epilogue(p)) return e;
     SidlsgTraceScope ts(SIDLSG_FAM_GEMM, 2.0 * p.M * (double)p.N * p.K);
     return launch_gemm_mx8<0>(p, (hipStream_t)stream);
 }
@@ -3136,6 +3199,7 @@ static int conv3x3_mx8_impl(bool g2, const void* X8, int ldx, const void* W8, co
     if (!range31(p.a_bytes, conv_src_pixels(B, H, Wd, 0), ldx, Cin, 1, (unsigned long long)(Wd + 1) * ldx) || !range31(p.w_bytes, 9ull * Cout, Cin, Cin, 1))
         return SIDLSG_EINVAL;
     set_group2(p, g2, W8_1, wscale1, bias1);
+    if (int e = check_epilogue(p)) return e;
     SidlsgTraceScope ts(SIDLSG_FAM_CONV, 2.0 * p.M * (double)p.N * p.K);
     return launch_gemm_mx8<1>(p, (hipStream_t)stream);
 }
@@ -3181,7 +3245,9 @@ static int conv3x3_fp8w_impl(bool g2, const void* X, int ldx, const void* W8, co
     if (int e = check_common(p)) return e;
     if (!range31(p.a_bytes, conv_src_pixels(B, H, Wd, ups), ldx, Cin, 2) || !range31(p.w_bytes, 9ull * Cout, Cin, Cin, 1)) return SIDLSG_EINVAL;
     set_group2(p, g2, W8_1, wscale1, bias1);
+    if (int e = check_epilogue(p)) return e;
     const int tiles = m_tiles_rt(p, F8_T) * ((p.N + F8_T - 1) / F8_T);
+    record_launch(SIDLSG_K_GEMM_FP8W, F8_T, F8_T, 2, -1, -1, 1, SIDLSG_PART_ONE);
     SIDLSG_LAUNCH((gemm_fp8w_kernel<2>), dim3(tiles), dim3(NTHREADS), 0, (hipStream_t)stream, p);
     return sidlsg_last_error();
 }

@@ -632,6 +632,7 @@ static int launch_gemm_p8_geglu(const GemmParams& p, hipStream_t s) {
     }
     GemmParams q = p;
     q.group_m = 4;
+    record_launch(EPI == 1 ? SIDLSG_K_GEMM_P8W_GEGLU : SIDLSG_K_GEMM_P8W_GEGLU_BWD, G::BM, G::BN, 0, -1, 1, 1, SIDLSG_PART_ONE);
     SIDLSG_LAUNCH(kern, dim3(tiles), dim3(G::NTH), (size_t)G::LDS_BYTES, s, q);
     return sidlsg_last_error();
 }
@@ -670,6 +671,7 @@ static int launch_gemm_p8(const GemmParams& p, hipStream_t s) {
     const int splits = p.kt_per_split ? (nk + p.kt_per_split - 1) / p.kt_per_split : 1;
     GemmParams q = p;
     q.group_m = 4;
+    record_launch(CFG ? SIDLSG_K_GEMM_P8W : SIDLSG_K_GEMM_P8S, G::BM, G::BN, MODE, -1, CFG, splits, p.kt_per_split ? SIDLSG_PART_SLABS : SIDLSG_PART_ONE);
     SIDLSG_LAUNCH(kern, dim3(tiles * splits), dim3(G::NTH), (size_t)G::LDS_BYTES, s, q);
     if (p.kt_per_split) launch_gemm_finish(p, splits, s);
     return sidlsg_last_error();

@@ -38,6 +38,23 @@ def _cases():
     def nonpos(*names):
         return [(f'{n} = {v}', {n: v}) for n in names for v in (0, -8)]
 
+    def contract(out, n, n_name, ld_in, k):
+        """The operand contract of the output and the epilogue operands (include/sidlsg_hip.h "operand contract") for a family whose base has
+        `n` % 8 == 0 output columns (argument `n_name`) in rows of ldc = n, and `k` input columns in rows of `ld_in`: -> (flips, admitted)."""
+        flips = [(f'ldc < {n_name}', dict(ldc=n - 8)), (f'ldres < {n_name}', dict(res=P, ldres=n - 8)), (f'ld_rowvec < {n_name}', dict(rowvec=P, ld_rowvec=n - 8)),
+                 (f'{ld_in} < its {k} columns', {ld_in: k - 8}),
+                 (f'ldc % 8 with {n_name} % 8 == 0', dict(ldc=n + 4)), (f'fp32 {out} with ldc % 4', dict(ldc=n + 2, flags=OUT_F32)), (f'misaligned {out}', {out: 'ptr+8'}),
+                 ('ldres % 8', dict(res=P, ldres=n + 4)), ('misaligned res', dict(res='ptr+8', ldres=n)),
+                 ('ld_rowvec % 4', dict(rowvec=P, ld_rowvec=n + 2)), ('misaligned rowvec', dict(rowvec='ptr+8', ld_rowvec=n)), ('misaligned bias', dict(bias='ptr+8'))]
+        admitted = [('wider ldc, ldres and ld_rowvec', dict(ldc=n + 8, res=P, ldres=n + 64, rowvec=P, ld_rowvec=n + 4)),
+                    (f'fp32 {out} with ldc % 8 == 4', dict(ldc=n + 4, flags=OUT_F32)), ('ldres = N, ld_rowvec = 0 (= N)', dict(res=P, ldres=n, rowvec=P, ld_rowvec=0))]
+        return flips, admitted
+
+    def ragged(n_name, n):
+        """N % 8 != 0 takes the element-wise epilogue: no alignment demands, the widths still hold."""
+        return ([(f'ragged {n_name}: ldc < {n_name}', {n_name: n - 4, 'ldc': n - 8})],
+                [(f'ragged {n_name}: odd strides, misaligned operands', {n_name: n - 4, 'ldc': n - 3, 'res': 'ptr+8', 'ldres': n - 1, 'rowvec': 'ptr+8', 'ld_rowvec': n - 2, 'bias': 'ptr+8'})])
+
     epi = dict(ldc=64, bias=P, res=None, ldres=0, rowvec=None, ld_rowvec=0, alpha=1.0, flags=0, stream=None)
     epi_flips = [('ACCUM without OUT_F32', dict(flags=ACCUM)), ('ACCUM | SILU without OUT_F32', dict(flags=ACCUM | SILU))]
     epi_ok = [('ACCUM with OUT_F32', dict(flags=ACCUM | OUT_F32))]
@@ -58,8 +75,11 @@ def _cases():
         flips.append(('A extent past 2^31 - 1', dict(M=1026, **a_big)))
         wk = 65536 if f8 else 32768          # one W row = 65536 bytes in both formats
         assert 32767 * 65536 < LIMIT <= 32768 * 65536
-        admitted.append(('W extent just below 2^31 - 1', dict(M=2, N=32767, K=wk, lda=wk)))
-        flips.append(('W extent past 2^31 - 1', dict(M=2, N=32768, K=wk, lda=wk)))
+        admitted.append(('W extent just below 2^31 - 1', dict(M=2, N=32767, ldc=32767, K=wk, lda=wk)))
+        flips.append(('W extent past 2^31 - 1', dict(M=2, N=32768, ldc=32768, K=wk, lda=wk)))
+        for fl, ad in (contract('C', 64, 'N', 'lda', 64), ragged('N', 64)):
+            flips += fl
+            admitted += ad
         if f8:
             base['wscale'] = P
             flips += nulls('wscale')
@@ -89,6 +109,9 @@ def _cases():
         assert k_ok % 16 == 0 and k_bad % 16 == 0 and 160 * k_ok < LIMIT <= 160 * k_bad
         admitted.append(('W extent just below 2^31 - 1', dict(M=2, K=k_ok, lda=k_ok)))
         flips.append(('W extent past 2^31 - 1', dict(M=2, K=k_bad, lda=k_bad)))
+        fl, ad = contract('C', 160, 'N', 'lda', 64)
+        flips += [f for f in fl if not f[0].startswith('lda <')]          # ('lda < K' above: 48 is also lda % 16 == 0)
+        admitted += ad
         if g2:
             base.update(W8_1=P, wscale1=P, bias1=P)
             flips += nulls('W8_1', 'wscale1') + [('odd M', dict(M=63)), ('bias for the first set only', dict(bias1=None)),
@@ -115,15 +138,18 @@ def _cases():
         flips.append(('image extent past 2^31 - 1', dict(H=32, Wd=16, ldx=ldx_bad, **big)))
         admitted.append(('ups: the source image (half size) just below 2^31 - 1', dict(H=64, Wd=32, ups=1, ldx=ldx_ok, **big)))
         flips.append(('ups: the source image past 2^31 - 1', dict(H=64, Wd=32, ups=1, ldx=ldx_bad, **big)))
+        for fl, ad in (contract('Y', 64, 'Cout', 'ldx', 64), ragged('Cout', 64)):
+            flips += fl
+            admitted += ad
         if f8:                               # e4m3 weights: one byte each, so twice the rows fit
             assert 2 * co_ok * 9 * 32768 < LIMIT <= (2 * co_ok + 2) * 9 * 32768
-            admitted.append(('W extent just below 2^31 - 1', dict(B=2, H=2, Wd=2, Cin=32768, ldx=32768, Cout=2 * co_ok)))
-            flips.append(('W extent past 2^31 - 1', dict(B=2, H=2, Wd=2, Cin=32768, ldx=32768, Cout=2 * co_ok + 2)))
+            admitted.append(('W extent just below 2^31 - 1', dict(B=2, H=2, Wd=2, Cin=32768, ldx=32768, Cout=2 * co_ok, ldc=2 * co_ok)))
+            flips.append(('W extent past 2^31 - 1', dict(B=2, H=2, Wd=2, Cin=32768, ldx=32768, Cout=2 * co_ok + 2, ldc=2 * co_ok + 8)))
             base['wscale'] = P
             flips += nulls('wscale')
         else:
-            admitted.append(('W extent just below 2^31 - 1', dict(B=2, H=2, Wd=2, Cin=32768, ldx=32768, Cout=co_ok)))
-            flips.append(('W extent past 2^31 - 1', dict(B=2, H=2, Wd=2, Cin=32768, ldx=32768, Cout=co_bad)))
+            admitted.append(('W extent just below 2^31 - 1', dict(B=2, H=2, Wd=2, Cin=32768, ldx=32768, Cout=co_ok, ldc=co_ok)))
+            flips.append(('W extent past 2^31 - 1', dict(B=2, H=2, Wd=2, Cin=32768, ldx=32768, Cout=co_bad, ldc=co_bad + 7)))
         if g2:
             w1 = 'W8_1' if f8 else 'W1'
             base.update({w1: P, 'bias1': P})
@@ -142,10 +168,13 @@ def _cases():
         flips = nulls('X8', 'W8', 'wscale', 'Y') + nonpos('B', 'H', 'Wd', 'Cin', 'Cout') + epi_flips
         flips += [('Cin % 16', dict(Cin=72, ldx=80)), ('ldx % 16', dict(ldx=72)), ('ldx < Cin', dict(ldx=48)), ('Cout % 160', dict(Cout=128)),
                   ('image extent + halo past 2^31 - 1', dict(H=32, Wd=16, Cin=16, ldx=lh_bad)),
-                  ('W extent past 2^31 - 1', dict(Cin=32768, ldx=32768, H=2, Wd=2, Cout=7360))]
+                  ('W extent past 2^31 - 1', dict(Cin=32768, ldx=32768, H=2, Wd=2, Cout=7360, ldc=7360))]
         assert 7200 * 9 * 32768 < LIMIT <= 7360 * 9 * 32768
         admitted = epi_ok + [('image extent + halo just below 2^31 - 1', dict(H=32, Wd=16, Cin=16, ldx=lh_ok)),
-                             ('W extent just below 2^31 - 1', dict(Cin=32768, ldx=32768, H=2, Wd=2, Cout=7200))]
+                             ('W extent just below 2^31 - 1', dict(Cin=32768, ldx=32768, H=2, Wd=2, Cout=7200, ldc=7200))]
+        fl, ad = contract('Y', 160, 'Cout', 'ldx', 64)
+        flips += [f for f in fl if not f[0].startswith('ldx <')]          # ('ldx < Cin' above)
+        admitted += ad
         if g2:
             base.update(W8_1=P, wscale1=P, bias1=P)
             flips += nulls('W8_1', 'wscale1') + [('odd B', dict(B=3)), ('bias for the first set only', dict(bias1=None)),

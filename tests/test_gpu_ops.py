@@ -45,13 +45,19 @@ def close(got, ref, tol, name=''):
 
 
 # ----------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('M,N,K', [(256, 320, 320), (1000, 136, 72), (4096, 960, 320), (77 * 2, 640, 768), (130, 8, 2880), (64, 2560, 320),
-                                   (1000, 1280, 2560), (300, 136, 4096),     # split-K path (few tiles, long K)
-                                   (49152, 320, 320), (49160, 320, 328),                      # direct-to-LDS kernel (+ ragged M, K tail)
-                                   # the 64 x 64-tile fallback of the small launches: K / V projections of the text states, 8 x 8 stage Linears;
-                                   # ragged M / N / K, very short K
+# Which kernel each shape reaches, as the dispatch record (sidlsg_debug_last_launch) shows with the default 512 MB workspace -- the exact
+# tests of tests/test_gpu_gemm_exact.py assert the record per shape, these comments only describe:
+@pytest.mark.parametrize('M,N,K', [(256, 320, 320), (1000, 136, 72), (77 * 2, 640, 768), (64, 2560, 320),     # gemm_bf16_kernel<64, 64>
+                                   (4096, 960, 320),                         # gemm_bf16_kernel<64, 160>
+                                   (130, 8, 2880),                           # gemm_bf16_kernel<128, 64> (N <= 64)
+                                   (1000, 1280, 2560), (300, 136, 4096),     # split-K (few tiles, long K): gemm_v3_kernel 5 splits, gemm_bf16_kernel<128, 128> 8 splits
+                                   (49152, 320, 320),                        # the 256 x 320 p8 kernel, by the cost model
+                                   (49160, 320, 328),                        # gemm_v3_kernel unsplit (ragged M, K tail: K % 64 != 0 keeps the p8 rule out)
+                                   # gemm_bf16_kernel<64, 64> again, the fallback of the small launches: K / V projections of the text states,
+                                   # 8 x 8 stage Linears; ragged M / N / K, very short K
                                    (1232, 640, 768), (616, 2560, 768), (1024, 1280, 1280), (2048, 1280, 1280), (300, 200, 200), (65, 72, 8),
-                                   (129, 136, 136), (1000, 320, 5120)])
+                                   (129, 136, 136),
+                                   (1000, 320, 5120)])                       # gemm_v3_kernel, 10 K splits
 def test_gemm(dev, M, N, K):
     from sid_lsg_amd import ops
     a, w = rnd(M, K, seed=1), rnd(N, K, seed=2, scale=K ** -0.5)
@@ -81,10 +87,14 @@ def test_gemm_short_k_a_stationary(dev):
     assert res.returncode == 0 and 'all shapes ok' in res.stdout, res.stdout[-2000:] + res.stderr[-3000:]
 
 
-CONV_CASES = [(2, 16, 16, 64, 160, 1, 0), (2, 16, 16, 64, 128, 2, 0), (1, 8, 8, 128, 64, 1, 1), (2, 12, 20, 8, 320, 1, 0),
-              (2, 8, 8, 320, 8, 1, 0), (1, 64, 64, 320, 320, 1, 0), (3, 9, 7, 72, 40, 2, 0),
-              (2, 8, 8, 1280, 320, 1, 0), (1, 16, 16, 640, 160, 1, 1),      # these two: split-K conv (8x8 / 16x16 stages)
-              (1, 16, 16, 320, 640, 1, 1), (2, 16, 16, 640, 640, 2, 0), (3, 9, 7, 160, 160, 1, 0)]   # weight gradient: 160 x 160 tiles
+# By the dispatch record (default workspace): the forward convs of this list run gemm_bf16_kernel<64, 64> or <128, 64> (Cout <= 64), or
+# gemm_v3_kernel<1> with split-K -- none reaches unsplit v3, the wider gemm_bf16_kernel tiles or the p8 kernels (tests/gemm_cases.py has those);
+# the weight gradients run wgrad_v2f / v2wf (constant-advance gather), wgrad_v2w<1> ((2, 12, 20, 8, 320)) and wgrad_v2<1> (upsampled, odd sizes).
+CONV_CASES = [(2, 16, 16, 64, 160, 1, 0), (2, 16, 16, 64, 128, 2, 0), (1, 8, 8, 128, 64, 1, 1), (2, 12, 20, 8, 320, 1, 0),     # <64, 64>, <64, 64>, <128, 64>, <64, 64> MODE 2
+              (2, 8, 8, 320, 8, 1, 0), (1, 64, 64, 320, 320, 1, 0), (3, 9, 7, 72, 40, 2, 0),       # <128, 64>, v3 with 5 K splits, <128, 64> MODE 2
+              (2, 8, 8, 1280, 320, 1, 0), (1, 16, 16, 640, 160, 1, 1),      # split-K conv on gemm_v3_kernel<1> (8x8 / 16x16 stages): 15 and 10 splits
+              (1, 16, 16, 320, 640, 1, 1), (2, 16, 16, 640, 640, 2, 0),     # the same: 5 and 10 splits
+              (3, 9, 7, 160, 160, 1, 0)]                                    # <64, 64> MODE 2 (Cin % 64 != 0); weight gradient: wgrad_v2_kernel<1>, 128 x 128 tiles
 
 
 def conv_ref(x, w, stride, ups):
@@ -110,7 +120,8 @@ def test_conv3x3(dev, B, H, W, Cin, Cout, stride, ups):
     close(got, ref + bias + res.float() + rv[:, None, None, :], 1.2e-2, 'conv+epilogue')
 
 
-# (N and K multiples of 160 take the 160 x 160-tile kernel: wgrad_v2s_kernel; incl. ragged row counts and one-split launches)
+# (by the dispatch record: (8192, 960, 320) takes the 160 x 160-tile kernel, wgrad_v2s_kernel -- N and K multiples of 160, N != K, M >= 4096 --
+# every other shape wgrad_v2_kernel<0> on 128 x 128 tiles, (100, 2560, 320) with one split, the rest with slabs + wgrad_reduce_kernel)
 @pytest.mark.parametrize('M,N,K', [(512, 128, 128), (1000, 320, 72), (4096, 64, 2880), (333, 8, 320), (8192, 960, 320), (65536, 320, 320),
                                    (3000, 320, 1280), (777, 640, 640), (100, 2560, 320), (16384, 1280, 1280)])
 def test_wgrad_dense(dev, M, N, K):

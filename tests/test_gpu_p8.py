@@ -53,9 +53,11 @@ def conv_ref(x, w, stride):
     return y.permute(0, 2, 3, 1).contiguous()
 
 
-# (B, H, Cin, Cout, stride): W takes Cout % 320 == 0, S Cout % 160 == 0; 8 x 8 x B16: four images per tile; B3: ragged tiles
+# (B, H, Cin, Cout, stride): W takes Cout % 320 == 0, S Cout % 160 == 0; 8 x 8 x B16: four images per tile; B3: ragged tiles.
+# The other side (p8 off), by the dispatch record: gemm_bf16_kernel<64, 64, 1> for all but (2, 16, 320, 960) -- gemm_v3_kernel<1> with 5 K splits,
+# against 3 splits of either forced p8 configuration -- and the last two
 CONV = [(4, 32, 64, 320, 1), (3, 32, 128, 320, 1), (16, 8, 128, 640, 1), (4, 32, 64, 320, 2), (2, 16, 320, 960, 1), (5, 8, 64, 160, 1),
-        (16, 32, 128, 320, 1), (17, 32, 64, 640, 1)]          # the last two: >= 256 tiles of 128 x 160 -> the other side IS gemm_v3_kernel
+        (16, 32, 128, 320, 1), (17, 32, 64, 640, 1)]          # the last two: >= 256 tiles of 128 x 160 -> the other side IS gemm_v3_kernel, unsplit
 
 
 def v3_runs_unsplit(M, N, K):
@@ -100,6 +102,9 @@ def test_conv_forced(dev, p8, mode, B, H, Cin, Cout, stride):
         assert torch.equal(ops.conv3x3(xd, wd, bias=bd, res=rd, stride=stride), y0)
 
 
+# The other side (p8 off), by the dispatch record: gemm_bf16_kernel<64, 64> for (4096, 320, 320), (1000, 320, 640), (300, 960, 1280) and
+# (20000, 160, 320); gemm_v3_kernel with 2 / 4 K splits for (8192, 640, 2560) / (2048, 1280, 5120) (forced p8: 2 / 4 splits on S, 3 / 6 on W);
+# unsplit gemm_v3_kernel for the last two
 @pytest.mark.parametrize('M,N,K', [(4096, 320, 320), (1000, 320, 640), (8192, 640, 2560), (300, 960, 1280), (20000, 160, 320), (2048, 1280, 5120),
                                    (16500, 320, 640), (8192, 640, 1280)])
 @pytest.mark.parametrize('mode', [1, 2])
@@ -152,13 +157,29 @@ def test_grouped_conv_forced(dev, p8, mode):
     close(ops.conv3x3(x, ops.Pair(w0, w1), bias=ops.Pair(b0, b1), res=res), y, 1.2e-2, 'grouped conv: p8 vs the default kernels')
 
 
+def _last_kernel():
+    """(kernel, tile rows, tile columns, K splits) of the dispatch record (include/sidlsg_hip.h sidlsg_debug_last_launch)."""
+    import ctypes
+    from sid_lsg_amd._lib import lib
+    r = (ctypes.c_int * 10)()
+    assert lib.sidlsg_debug_last_launch.raw(ctypes.addressof(r), 10) == 10
+    return r[0], r[1], r[2], r[6]
+
+
 def test_rule_takes_the_wide_tile_for_the_big_convs(dev, p8):
     """The dispatch rule (cost model in gemm.hip::p8_rule): B16 64x64 320->320 goes to the 256 x 320 kernel (bit-identical to v3 there),
-    a B2 call of the same layer does not fill 256-row tiles and stays on v3 -- observable through the dispatch trace's kernel names is
-    not available from here, so the observable is speed-neutral equality plus the rule's own admission function."""
+    a B2 call of the same layer does not fill 256-row tiles and stays on v3 (with 4 K splits).  The dispatch record names the kernel of
+    each call: SIDLSG_K_GEMM_V3 = 2, SIDLSG_K_GEMM_P8W = 4."""
     from sid_lsg_amd import ops
+    V3, P8W = 2, 4
     x, w = rnd(16, 64, 64, 320, seed=1).to(dev), rnd(320, 2880, seed=2, scale=0.02).to(dev)
     p8.set(-1)
     y = ops.conv3x3(x, w)
+    assert _last_kernel() == (P8W, 256, 320, 1), _last_kernel()
+    y2 = ops.conv3x3(x[:2].contiguous(), w)
+    assert _last_kernel() == (V3, 128, 160, 4), _last_kernel()
     p8.set(0)
     assert torch.equal(ops.conv3x3(x, w), y)
+    assert _last_kernel() == (V3, 128, 160, 1), _last_kernel()
+    assert torch.equal(ops.conv3x3(x[:2].contiguous(), w), y2)
+    assert _last_kernel() == (V3, 128, 160, 4), _last_kernel()
