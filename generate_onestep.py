@@ -32,6 +32,12 @@ file `idx % len`), white = repaint.  A mask gets the init image's centre crop an
 pixel of its 8 x 8 block is >= 128, so everything marked is repainted (diffusers takes the nearest pixel).  The samplers re-impose the
 kept region at every step boundary (sidlsg_masked_renoise).  `--mask_composite 1` also takes the pixels whose mask value is < 128
 from the init image as loaded, after decoding: the VAE round trip alone changes kept pixels slightly.
+
+`--controlnet SPEC --control_images DIR` conditions every UNet call on a ControlNet (sid_lsg_amd.controlnet.HipControlNet): SPEC is a
+local directory in diffusers' layout or `random:controlnet[:seed]`; sample `idx` takes control image `idx % len(files)` of DIR (PNG /
+JPEG, sorted by name), which must already be `--resolution` square -- an edge map or a pose skeleton is not resampled behind the user's
+back.  `--control_scale` (default 1) scales the thirteen residuals.  It applies to `--network teacher` under every `--teacher_*` option
+and to snapshots with any `--num_steps_eval`, and combines with `--init_images` / `--mask_images`.
 """
 import math
 import os
@@ -44,8 +50,8 @@ import torch
 
 from sid_lsg_amd import distributed as dist
 from sid_lsg_amd.preview import save_png
-from sid_lsg_amd.sd_util import (TEACHER, TEACHER_CFG, TEACHER_STEPS, check_prediction_type, load_sd15, load_vae_encoder, sid_sd_sampler,
-                                 teacher_sample_i2i, teacher_sample_solver_i2i, teacher_start_index)
+from sid_lsg_amd.sd_util import (TEACHER, TEACHER_CFG, TEACHER_STEPS, check_prediction_type, load_controlnet, load_sd15, load_vae_encoder,
+                                 sid_sd_sampler, teacher_sample_i2i, teacher_sample_solver_i2i, teacher_start_index)
 
 
 class StackedRandomGenerator:
@@ -236,6 +242,46 @@ def composite(generated, init_pixels, pixel_mask):
     return np.where((pixel_mask >= 128)[..., None], generated, init_pixels)
 
 
+def list_control_images(path):
+    """The PNG / JPEG files of --control_images, sorted by name."""
+    if not os.path.isdir(path):
+        raise click.UsageError(f'--control_images {path}: not a directory')
+    files = sorted(f for f in os.listdir(path) if f.lower().endswith(IMAGE_EXTENSIONS) and os.path.isfile(os.path.join(path, f)))
+    if not files:
+        raise click.UsageError(f'--control_images {path}: no PNG or JPEG files')
+    return [os.path.join(path, f) for f in files]
+
+
+def control_options(controlnet, control_images, control_scale):
+    """-> None without the ControlNet options, else (spec, control image files, scale); one of --controlnet / --control_images without
+    the other, or --control_scale without them, is a usage error."""
+    if controlnet is None and control_images is None:
+        if control_scale is not None:
+            raise click.UsageError('--control_scale applies to --controlnet / --control_images only')
+        return None
+    if controlnet is None:
+        raise click.UsageError('--control_images needs --controlnet (a ControlNet directory or random:controlnet[:seed])')
+    if control_images is None:
+        raise click.UsageError('--controlnet needs --control_images (the directory of control images)')
+    return controlnet, list_control_images(control_images), 1.0 if control_scale is None else float(control_scale)
+
+
+def load_control_image(path, resolution):
+    """-> uint8 [resolution, resolution, 3] RGB.  The file must already have that size: nothing is cropped or resized."""
+    import PIL.Image
+    with PIL.Image.open(path) as im:
+        w, h = im.size
+        if (w, h) != (resolution, resolution):
+            raise click.UsageError(f'--control_images: {path} is {w} x {h}, expected {resolution} x {resolution} (--resolution); '
+                                   'control images are not resized')
+        return np.ascontiguousarray(np.asarray(im.convert('RGB'), dtype=np.uint8))
+
+
+def load_control_batch(files, indices, resolution):
+    """Sample idx takes file idx % len(files) -> uint8 [B, resolution, resolution, 3]."""
+    return np.stack([load_control_image(files[i % len(files)], resolution) for i in indices])
+
+
 @click.command()
 @click.option('--network', 'network_pkl', type=str, required=True, metavar='PATH', help=f'Network snapshot pickle, or "{TEACHER}": sample the UNet of --repo_id itself')
 @click.option('--outdir', type=str, required=True, metavar='DIR', help='Where to save the output images')
@@ -265,10 +311,14 @@ def composite(generated, init_pixels, pixel_mask):
 @click.option('--sample_posterior', type=bool, default=None, help='With --init_images: sample the VAE posterior (eps from the per-seed generator, after z) instead of its mean  [default: False]')
 @click.option('--mask_images', type=str, default=None, metavar='DIR', help='Inpainting, with --init_images: mask files (sorted by name; one for all, or one per init image), >= 128 = repaint')
 @click.option('--mask_composite', type=bool, default=False, show_default=True, help='With --mask_images: take the pixels whose mask value is < 128 from the init image after decoding')
+@click.option('--controlnet', type=str, default=None, metavar='SPEC', help='ControlNet: a local diffusers-layout directory, or random:controlnet[:seed]; needs --control_images')
+@click.option('--control_images', type=str, default=None, metavar='DIR', help='Control images, already --resolution square: PNG/JPEG files (sorted by name); sample idx uses file idx mod len(files)')
+@click.option('--control_scale', type=click.FloatRange(min=0), default=None, help='Scale of the ControlNet residuals  [default: 1]')
 @click.option('--text_encoder', type=click.Choice(['torch', 'hip']), default=None, help='CLIP text encoder: the PyTorch module, or the same weights on the HIP kernels  [default: $SIDLSG_TEXT_ENCODER, else torch] (not a reference option)')
 def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, init_timestep, text_prompts, repo_id, resolution, use_fp16,
          enable_compress_npz, num_steps_eval, custom_seed, teacher_steps, guidance_scale, init_images, strength, sample_posterior, text_encoder,
-         teacher_sampler, teacher_spacing, teacher_eta, guidance_rescale, negative_prompt, mask_images, mask_composite):
+         teacher_sampler, teacher_spacing, teacher_eta, guidance_rescale, negative_prompt, mask_images, mask_composite, controlnet, control_images,
+         control_scale):
     text_encoder_kind = text_encoder
     if resolution % 8:
         raise click.BadParameter(f'{resolution}: must be a multiple of 8', param_hint='--resolution')
@@ -276,6 +326,7 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
     solver_kw = teacher_solver_options(network_pkl, teacher_sampler, teacher_spacing, teacher_eta, guidance_rescale, negative_prompt)
     img2img = image_to_image_options(network_pkl, init_images, strength, sample_posterior, num_steps_eval, teacher_steps)
     masks = mask_options(init_images, mask_images, mask_composite, 0 if img2img is None else len(img2img[0]))
+    control = control_options(controlnet, control_images, control_scale)
     dist.init()
     device = torch.device('cuda')
     rank, world = dist.get_rank(), dist.get_world_size()
@@ -309,6 +360,9 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
         vae_encoder = load_vae_encoder(repo_id, device)
         dist.print0(f'Image-to-image: {len(img2img[0])} init images from "{init_images}", entering at step {img2img[1]} of '
                     f'{num_steps_eval if teacher is None else teacher[0]}')
+    if control is not None:
+        control_net = load_controlnet(control[0], G_ema, device)
+        dist.print0(f'ControlNet "{control[0]}": scale {control[2]:g}, {len(control[1])} control image(s) from "{control_images}"')
     if masks is not None:
         dist.print0(f'Inpainting: {len(masks[0])} mask image(s) from "{mask_images}"' + (', kept pixels composited from the init images' if masks[1] else ''))
     if world > 1 and rank == 0:
@@ -338,6 +392,9 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
             if masks is not None:
                 pixel_mask = load_mask_batch(masks[0], batch, resolution)
                 i2i['mask'] = torch.from_numpy(latent_mask(pixel_mask)).to(device)
+        if control is not None:        # one conversion launch + the hint embedder, once per batch; the guided teacher batch is [uncond ; cond]
+            hints = torch.from_numpy(load_control_batch(control[1], batch, resolution)).to(device)
+            i2i['control'] = control_net.prepare(hints, scale=control[2], dup=2 if (teacher is not None and teacher[1] != 1) else 1)
         with torch.no_grad():
             if teacher is not None and solver_kw is not None:
                 kw = {k: v for k, v in solver_kw.items() if k != 'negative_prompt'}

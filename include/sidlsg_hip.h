@@ -528,6 +528,12 @@ int sidlsg_image_to_nhwc8_f32(const float* images_nchw, void* out, int B, int H,
 int sidlsg_vae_posterior(const float* moments, const float* qw, const float* qb, const float* eps, float* z, float* mean, float* logvar, int B,
                          int HW, float scaling, void* stream);
 
+/* ---- ControlNet (sid_lsg_amd/controlnet.py HipControlNet; the reference has no structure conditioning: no counterpart there) ----------
+ * sidlsg_control_hint_u8: control images uint8 [B][H][W][3] (RGB) -> the hint embedder's input [B][H][W][8], bf16 (f32_out != 0: fp32),
+ *   float(x) / 255 as one IEEE fp32 division, for bf16 rounded to nearest even; channels 3..7 zero.  out 16-byte aligned and below
+ *   2^31 bytes; SIDLSG_EINVAL and no launch otherwise.  Every contraction of a ControlNet runs on the GEMM / conv entry points above. */
+int sidlsg_control_hint_u8(const void* images_u8, void* out, int B, int H, int W, int f32_out, void* stream);
+
 /* ---- CLIP text encoder (sid_lsg_amd/text.py HipCLIPTextModel; transformers' CLIPTextModel, which the reference calls) ------------
  * sidlsg_attn_causal_fwd(_f32): O = softmax(mask(Q K^T D^-1/2)) V per head, key j visible to query i iff j <= i.  Forward only, no
  *   LSE.  Q/K/V/O: [B][N][ld*] views of bf16 (_f32: fp32) holding H heads of width D side by side (token stride ld* >= H * D, batch

@@ -616,12 +616,15 @@ def gemm(a, w16, out=None, bias=None, res=None, rowvec=None, rows_per_batch=1, a
     return out
 
 
-def conv3x3(x, w16, bias=None, res=None, rowvec=None, stride=1, ups=0, out_f32=False, pad=1):
+def conv3x3(x, w16, bias=None, res=None, rowvec=None, stride=1, ups=0, out_f32=False, pad=1, silu=False):
     """x: [B,Hs,Ws,Cin] bf16 NHWC; w16: [Cout, 9*Cin]; -> [B,Ho,Wo,Cout].  pad=1: torch's padding=1 on all four sides.
+    silu (forward only, pad=1): y = silu(conv + bias + rowvec + res), the SIDLSG_SILU epilogue flag.
     pad='br' (stride 2 only, forward only): zero padding on the bottom and right only -- diffusers Downsample2D(padding=0),
     F.pad(x, (0, 1, 0, 1)) + conv2d(stride=2) (sidlsg_conv3x3_br_bf16); bias is its only epilogue operand."""
     B, Hs, Ws, Cin = x.shape
     if pad == 'br':
+        if silu:
+            raise RuntimeError("conv3x3(pad='br'): no SiLU epilogue through this wrapper")
         if stride != 2 or ups or res is not None or rowvec is not None or x.dtype != BF16 or isinstance(w16, (Pair, Fp8Weight)) or w16.dtype != BF16:
             raise RuntimeError("conv3x3(pad='br'): stride 2, bf16 activations and weights, no upsampling, residual or row vector")
         if Hs % 2 or Ws % 2:
@@ -644,7 +647,7 @@ def conv3x3(x, w16, bias=None, res=None, rowvec=None, stride=1, ups=0, out_f32=F
     else:
         fn = lib.sidlsg_conv3x3_bf16_g2 if g2 else _fn('conv3x3', x.dtype, '_bf16')
     fn(_p(x), Cin, *_weight_args(w16), _p(out), Cout, *_epilogue_args(g2, bias, res, rowvec, ldres=Cout), B, H, W, Cin, Cout, stride, ups,
-       1.0, 1 if (out_f32 and not f32) else 0, _s())
+       1.0, (1 if (out_f32 and not f32) else 0) | (2 if silu else 0), _s())
     return out
 
 
@@ -2025,6 +2028,20 @@ def image_to_nhwc8(images):
         lib.sidlsg_image_to_nhwc8_f32(_p(_chk(images, F32)), _p(out), B, H, W, _s())
     else:
         raise RuntimeError(f'image_to_nhwc8: expected uint8 [B, H, W, 3] or fp32 [B, 3, H, W], got {images.dtype} {tuple(images.shape)}')
+    return out
+
+
+def control_hint_u8(images, dtype=BF16):
+    """Control images uint8 [B, H, W, 3] (RGB) -> the ControlNet hint embedder's input [B, H, W, 8] of `dtype` (bf16 or fp32), channels 3..7
+    zero (sidlsg_control_hint_u8): float(x) / 255, one IEEE fp32 division, rounded to nearest even for bf16 -- the bits of
+    (images.float() / 255).to(dtype) formed on the host."""
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
+        raise RuntimeError(f'control_hint_u8: expected uint8 [B, H, W, 3], got {images.dtype} {tuple(images.shape)}')
+    if dtype not in (BF16, F32):
+        raise RuntimeError(f'control_hint_u8: output dtype {dtype}: expected bfloat16 or float32')
+    B, H, W, _ = images.shape
+    out = torch.empty((B, H, W, 8), device=images.device, dtype=dtype)
+    lib.sidlsg_control_hint_u8(_p(_chk(images, torch.uint8)), _p(out), B, H, W, 1 if dtype == F32 else 0, _s())
     return out
 
 

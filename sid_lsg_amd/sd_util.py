@@ -261,6 +261,29 @@ def load_vae_encoder(pretrained_model_name_or_path, device, seed=0):
     return enc.to(torch.device(device))
 
 
+def load_controlnet(spec, unet, device, seed=0):
+    """A ControlNet (controlnet.HipControlNet) for `unet`, in its compute dtype:
+      * a local directory in diffusers' layout (config.json, diffusion_pytorch_model.safetensors): the config must describe a copy of
+        the UNet's encoder (block_out_channels, cross_attention_dim, use_linear_projection, heads) without global_pool_conditions,
+        class_embed_type, addition_embed_type or conditioning_channels != 3; a missing key or a wrong shape is refused by name;
+      * 'random:controlnet[:seed]': seeded weights of the UNet's own architecture (seed from the spec, else `seed`).
+    In the seeded form the thirteen tap convolutions and the embedder's conv_out get ordinary fan-in-scaled NON-zero weights.  diffusers
+    initialises them to zero, so that an untrained ControlNet changes nothing; here that would make a seeded ControlNet a no-op and every
+    test of the conditioning path vacuous."""
+    from . import controlnet as cn
+    net = _unwrap(unet)
+    _require_hip(net)
+    if isinstance(net, cn.HipControlNet):
+        raise TypeError('load_controlnet: `unet` is itself a ControlNet')
+    name = str(spec)
+    if os.path.isdir(name):
+        return cn.load_controlnet_dir(name, net, torch.device(device))
+    if not name.lower().startswith('random:'):
+        raise FileNotFoundError(f"{name}: not a local ControlNet directory; pass a directory or '{cn.RANDOM_PREFIX}[:seed]'")
+    s = cn.parse_random_spec(name)
+    return cn.HipControlNet(net.cfg, compute_dtype=net.compute_dtype).materialize(torch.device(device), seed=seed if s is None else s)
+
+
 def encode_contexts(contexts, text_encoder, tokenizer, device):
     """list[str] -> [B, L, D] text states (no grad); a tensor is passed through (pre-computed states)."""
     if torch.is_tensor(contexts):
@@ -272,12 +295,12 @@ def encode_contexts(contexts, text_encoder, tokenizer, device):
 
 
 # ------------------------------------------------------------------------------------------------
-def hip_generate(unet, z, ctx16, init_t, sched, x0=None):
+def hip_generate(unet, z, ctx16, init_t, sched, x0=None, control=None):
     """x_t = s0*x0 + s1*z at t_init ; o = G(x_t) ; x_hat = (x_t - s1*o)/s0 (epsilon) or s0*x_t - s1*o (v)   (sid_sd_util.py:182-185)"""
     s0, s1 = sched.coefficients(init_t)
     net = _unwrap(unet)
     xin, xt = ops.noisy_input(x0, z, s0, s1, 1, net.compute_dtype)
-    eps = _ddp_exchange(unet, net.forward_nhwc(xin, init_t, ctx16))
+    eps = _ddp_exchange(unet, net.forward_nhwc(xin, init_t, ctx16, control=control))
     return ops.cfg_x0(eps, xt, s0, s1, 1.0, True, net.compute_dtype, prediction_type=sched.config.prediction_type)
 
 
@@ -341,8 +364,9 @@ def hip_denoise(unet, prep, guidance_scale, predict_x0):
 # ------------------------------------------------------------------------------------------------
 def sid_sd_sampler(unet, latents, contexts, init_timesteps, noise_scheduler, text_encoder, tokenizer, resolution,
                    dtype=torch.float16, return_images=False, vae=None, guidance_scale=1, num_steps=1, train_sampler=True,
-                   num_steps_eval=1, init_latents=None, start_step=0, mask=None):
-    """init_latents / start_step (eval mode only; image-to-image): the chain is entered at step `start_step` with D_x = init_latents
+                   num_steps_eval=1, init_latents=None, start_step=0, mask=None, control=None):
+    """control (eval mode only): a controlnet.ControlState (HipControlNet.prepare(images, scale, dup=1)), passed to every UNet call of the loop.
+    init_latents / start_step (eval mode only; image-to-image): the chain is entered at step `start_step` with D_x = init_latents
     (scaled latents [B, 4, h, w], e.g. HipAutoencoderKLEncoder.encode_latents); the first executed step takes `latents` as its noise,
     so its input is x_{t_k} = s0 init_latents + s1 latents -- what a generator trained with --num_steps N saw at step k.
     mask (eval mode only, needs init_latents; inpainting): uint8 / bool [B, h, w] or [1, h, w], nonzero = repaint.  After every
@@ -362,6 +386,8 @@ def sid_sd_sampler(unet, latents, contexts, init_timesteps, noise_scheduler, tex
         if train_sampler:
             raise ValueError('sid_sd_sampler: mask is for the evaluation sampler (train_sampler=False)')
         mask = check_mask(mask, init_latents, latents, 'sid_sd_sampler')
+    if control is not None and train_sampler:
+        raise ValueError('sid_sd_sampler: control is for the evaluation sampler (train_sampler=False): ControlNet conditioning is forward only')
     _require_hip(unet)
     check_prediction_type(unet, noise_scheduler)
     emb = encode_contexts(contexts, text_encoder, tokenizer, latents.device).to(_unwrap(unet).compute_dtype).contiguous()
@@ -379,7 +405,7 @@ def sid_sd_sampler(unet, latents, contexts, init_timesteps, noise_scheduler, tex
             for i in range(start_step, steps):
                 noise = latents if i == start_step else torch.randn_like(latents)
                 t_i = (init_timesteps * (1 - i / steps)).to(torch.long)
-                D_x = hip_generate(unet, noise.to(torch.float32).contiguous(), emb, t_i.contiguous(), noise_scheduler, x0=D_x)
+                D_x = hip_generate(unet, noise.to(torch.float32).contiguous(), emb, t_i.contiguous(), noise_scheduler, x0=D_x, control=control)
                 if mask is not None:
                     D_x = ops.masked_renoise(D_x, z0, mask, want_input=False, inplace=True)[1]
     if not return_images:
@@ -470,7 +496,7 @@ def teacher_sample(unet, latents, contexts, noise_scheduler, text_encoder, token
 
 def teacher_sample_i2i(unet, latents, contexts, noise_scheduler, text_encoder, tokenizer, resolution, guidance_scale=TEACHER_CFG,
                        num_inference_steps=TEACHER_STEPS, return_images=False, vae=None, schedule_config=None, init_latents=None,
-                       start_index=0, mask=None):
+                       start_index=0, mask=None, control=None):
     """The teacher itself, sampled the way every SiD-LSG table samples it: classifier-free guidance and an N-step deterministic DDIM
     sampler (Song et al. 2021, eta = 0; diffusers' DDIMScheduler with 'leading' spacing).  x_T = latents (DDIM's init_noise_sigma is
     1); per step one UNet pass on the stacked [uncond ; cond] batch (unconditional prompt '', as sid_sd_denoise) and one
@@ -485,6 +511,8 @@ def teacher_sample_i2i(unet, latents, contexts, noise_scheduler, text_encoder, t
     sidlsg_masked_renoise launch re-imposes the known region at the step's target level, x <- mask ? x : s0p_i*z0 + s1p_i*latents
     (after the last step: z0 itself), and writes the next network input; with a mask and k = 0 the start is pure noise (diffusers'
     is_strength_max).  These rules restate diffusers' img2img / inpainting pipelines; agreement with the package is not pinned by a test.
+    control: a controlnet.ControlState (HipControlNet.prepare(images, scale, dup=2 with guidance, else 1)), passed to every UNet call; it
+    composes with init_latents / start_index / mask and needs none of them (teacher_sample keeps its pinned signature: the argument lives here).
     -> the final latent x_0 fp32 NCHW, or (return_images) the decoded images as sid_sd_sampler returns them."""
     _require_hip(unet)
     check_prediction_type(unet, noise_scheduler)
@@ -511,7 +539,7 @@ def teacher_sample_i2i(unet, latents, contexts, noise_scheduler, text_encoder, t
         else:
             xin, xt = ops.noisy_input(None, z, ones, ones, dup, dt)      # x_T = z, as the [uncond ; cond] NHWC batch
         for i in range(start_index, n):
-            eps = net.forward_nhwc(xin, tt[i], ctx)
+            eps = net.forward_nhwc(xin, tt[i], ctx, control=control)
             last = i == n - 1
             xin, xt, _ = ops.ddim_step(eps, xt, s0[i], s1[i], s0p[i], s1p[i], guidance_scale, dt, prediction_type=pt,
                                        last=last or mask is not None)
@@ -543,7 +571,7 @@ def teacher_sample_solver(unet, latents, contexts, noise_scheduler, text_encoder
 def teacher_sample_solver_i2i(unet, latents, contexts, noise_scheduler, text_encoder, tokenizer, resolution, guidance_scale=TEACHER_CFG,
                               num_inference_steps=TEACHER_STEPS, return_images=False, vae=None, schedule_config=None, solver='dpmpp2m',
                               spacing=None, eta=0.0, guidance_rescale=0.0, negative_contexts=None, randn=None, init_latents=None,
-                              start_index=0, mask=None):
+                              start_index=0, mask=None, control=None):
     """The teacher under the solvers it is usually run with: `solver` 'dpmpp2m' (DPM-Solver++ 2M) or 'ddim' (any `eta` >= 0), timestep
     `spacing` 'leading' / 'trailing' / 'linspace' (None: the model's timestep_spacing), guidance rescale `guidance_rescale` (phi of
     Lin et al. 2024; 0 = plain classifier-free guidance) and `negative_contexts` in place of '' in the unconditional half.  The
@@ -555,6 +583,7 @@ def teacher_sample_solver_i2i(unet, latents, contexts, noise_scheduler, text_enc
     init_latents / start_index / mask: image-to-image and inpainting as in teacher_sample.  The tables are solver_schedule's with
     start = start_index (DPM-Solver++ 2M takes its first executed step at first order); the masked boundary of step i noises the known
     region to the level of t_{i+1}, known = s0[i+1]*z0 + s1[i+1]*latents (after the last step: z0), and leaves the x0 history alone.
+    control: a controlnet.ControlState, as in teacher_sample_i2i.
     -> the final latent x_0 fp32 NCHW, or (return_images) the decoded images as sid_sd_sampler returns them."""
     _require_hip(unet)
     check_prediction_type(unet, noise_scheduler)
@@ -595,7 +624,7 @@ def teacher_sample_solver_i2i(unet, latents, contexts, noise_scheduler, text_enc
         history = [torch.empty_like(z), torch.empty_like(z)]
         x0_prev = None
         for i in range(start_index, n):
-            eps = net.forward_nhwc(xin, tt[i], ctx)
+            eps = net.forward_nhwc(xin, tt[i], ctx, control=control)
             scale = ops.cfg_rescale_stats(eps, z.shape[1], guidance_scale, phi) if guided and phi != 0 else None
             noise = randn(tuple(z.shape)).to(device=dev, dtype=torch.float32).contiguous() if flags[i][3] else None
             last = i == n - 1
