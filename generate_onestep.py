@@ -38,6 +38,13 @@ local directory in diffusers' layout or `random:controlnet[:seed]`; sample `idx`
 JPEG, sorted by name), which must already be `--resolution` square -- an edge map or a pose skeleton is not resampled behind the user's
 back.  `--control_scale` (default 1) scales the thirteen residuals.  It applies to `--network teacher` under every `--teacher_*` option
 and to snapshots with any `--num_steps_eval`, and combines with `--init_images` / `--mask_images`.
+
+`--ip_adapter SPEC --ip_image_encoder DIR --ip_images DIR` gives every sample a reference picture as an image prompt (IP-Adapter,
+sid_lsg_amd.ip_adapter.HipIPAdapter): SPEC is a local `.safetensors` / `.bin` file of an SD 1.5 adapter with the linear image projection
+or `random:ip-adapter[:seed]`; the image encoder is a local CLIP directory (config.json, model.safetensors) or `random:clip-<arch>`;
+sample `idx` takes prompt image `idx % len(files)` of DIR, any size (the encoder's CLIPImageProcessor transform resizes).  `--ip_scale`
+(default 1) scales the image attention; 0 issues exactly the launches of a run without the options.  It applies wherever `--controlnet`
+does and combines with it.
 """
 import math
 import os
@@ -49,8 +56,9 @@ import numpy as np
 import torch
 
 from sid_lsg_amd import distributed as dist
+from sid_lsg_amd.clip import load_clip_vision
 from sid_lsg_amd.preview import save_png
-from sid_lsg_amd.sd_util import (TEACHER, TEACHER_CFG, TEACHER_STEPS, check_prediction_type, load_controlnet, load_sd15, load_vae_encoder,
+from sid_lsg_amd.sd_util import (TEACHER, TEACHER_CFG, TEACHER_STEPS, check_prediction_type, load_controlnet, load_ip_adapter, load_sd15, load_vae_encoder,
                                  sid_sd_sampler, teacher_sample_i2i, teacher_sample_solver_i2i, teacher_start_index)
 
 
@@ -282,6 +290,45 @@ def load_control_batch(files, indices, resolution):
     return np.stack([load_control_image(files[i % len(files)], resolution) for i in indices])
 
 
+def list_ip_images(path):
+    """The PNG / JPEG files of --ip_images, sorted by name."""
+    if not os.path.isdir(path):
+        raise click.UsageError(f'--ip_images {path}: not a directory')
+    files = sorted(f for f in os.listdir(path) if f.lower().endswith(IMAGE_EXTENSIONS) and os.path.isfile(os.path.join(path, f)))
+    if not files:
+        raise click.UsageError(f'--ip_images {path}: no PNG or JPEG files')
+    return [os.path.join(path, f) for f in files]
+
+
+def ip_options(ip_adapter, ip_image_encoder, ip_images, ip_scale):
+    """-> None without the IP-Adapter options, else (adapter spec, image encoder spec, prompt image files, scale); one or two of
+    --ip_adapter / --ip_image_encoder / --ip_images without the rest, or --ip_scale without them, is a usage error."""
+    given = {'--ip_adapter': ip_adapter, '--ip_image_encoder': ip_image_encoder, '--ip_images': ip_images}
+    if all(v is None for v in given.values()):
+        if ip_scale is not None:
+            raise click.UsageError('--ip_scale applies to --ip_adapter / --ip_image_encoder / --ip_images only')
+        return None
+    missing = [k for k, v in given.items() if v is None]
+    if missing:
+        have = [k for k, v in given.items() if v is not None]
+        raise click.UsageError(f'{" / ".join(have)} need{"s" if len(have) == 1 else ""} {" and ".join(missing)} (an IP-Adapter file or '
+                               'random:ip-adapter[:seed], a CLIP image encoder directory or random:clip-<arch>, and the directory of prompt images)')
+    return ip_adapter, ip_image_encoder, list_ip_images(ip_images), 1.0 if ip_scale is None else float(ip_scale)
+
+
+def load_ip_image(path):
+    """-> uint8 [3, H, W] RGB, any size: the image encoder's transform resizes."""
+    import PIL.Image
+    with PIL.Image.open(path) as im:
+        return np.ascontiguousarray(np.asarray(im.convert('RGB'), dtype=np.uint8).transpose(2, 0, 1))
+
+
+def ip_image_embeds(files, indices, tower, device):
+    """Sample idx takes file idx % len(files) -> image embeddings [B, E] fp32; one tower call per image (the files may differ in size)."""
+    with torch.no_grad():
+        return torch.cat([tower(torch.from_numpy(load_ip_image(files[i % len(files)])).to(device)[None]).float() for i in indices])
+
+
 @click.command()
 @click.option('--network', 'network_pkl', type=str, required=True, metavar='PATH', help=f'Network snapshot pickle, or "{TEACHER}": sample the UNet of --repo_id itself')
 @click.option('--outdir', type=str, required=True, metavar='DIR', help='Where to save the output images')
@@ -314,11 +361,15 @@ def load_control_batch(files, indices, resolution):
 @click.option('--controlnet', type=str, default=None, metavar='SPEC', help='ControlNet: a local diffusers-layout directory, or random:controlnet[:seed]; needs --control_images')
 @click.option('--control_images', type=str, default=None, metavar='DIR', help='Control images, already --resolution square: PNG/JPEG files (sorted by name); sample idx uses file idx mod len(files)')
 @click.option('--control_scale', type=click.FloatRange(min=0), default=None, help='Scale of the ControlNet residuals  [default: 1]')
+@click.option('--ip_adapter', type=str, default=None, metavar='SPEC', help='IP-Adapter (image prompt): a local .safetensors / .bin file, or random:ip-adapter[:seed]; needs --ip_image_encoder and --ip_images')
+@click.option('--ip_image_encoder', type=str, default=None, metavar='DIR', help='CLIP image encoder of --ip_adapter: a local directory (config.json, model.safetensors), or random:clip-<arch>')
+@click.option('--ip_images', type=str, default=None, metavar='DIR', help='Prompt images of --ip_adapter, any size: PNG/JPEG files (sorted by name); sample idx uses file idx mod len(files)')
+@click.option('--ip_scale', type=click.FloatRange(min=0), default=None, help='Scale of the image attention  [default: 1]')
 @click.option('--text_encoder', type=click.Choice(['torch', 'hip']), default=None, help='CLIP text encoder: the PyTorch module, or the same weights on the HIP kernels  [default: $SIDLSG_TEXT_ENCODER, else torch] (not a reference option)')
 def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, init_timestep, text_prompts, repo_id, resolution, use_fp16,
          enable_compress_npz, num_steps_eval, custom_seed, teacher_steps, guidance_scale, init_images, strength, sample_posterior, text_encoder,
          teacher_sampler, teacher_spacing, teacher_eta, guidance_rescale, negative_prompt, mask_images, mask_composite, controlnet, control_images,
-         control_scale):
+         control_scale, ip_adapter, ip_image_encoder, ip_images, ip_scale):
     text_encoder_kind = text_encoder
     if resolution % 8:
         raise click.BadParameter(f'{resolution}: must be a multiple of 8', param_hint='--resolution')
@@ -327,6 +378,7 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
     img2img = image_to_image_options(network_pkl, init_images, strength, sample_posterior, num_steps_eval, teacher_steps)
     masks = mask_options(init_images, mask_images, mask_composite, 0 if img2img is None else len(img2img[0]))
     control = control_options(controlnet, control_images, control_scale)
+    ip = ip_options(ip_adapter, ip_image_encoder, ip_images, ip_scale)
     dist.init()
     device = torch.device('cuda')
     rank, world = dist.get_rank(), dist.get_world_size()
@@ -363,6 +415,11 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
     if control is not None:
         control_net = load_controlnet(control[0], G_ema, device)
         dist.print0(f'ControlNet "{control[0]}": scale {control[2]:g}, {len(control[1])} control image(s) from "{control_images}"')
+    if ip is not None:
+        ip_tower = load_clip_vision(ip[1], device, G_ema.compute_dtype)
+        ip_net = load_ip_adapter(ip[0], G_ema, device, ip_tower.cfg.projection_dim)
+        dist.print0(f'IP-Adapter "{ip[0]}": {ip_net.tokens} image tokens, scale {ip[3]:g}, image encoder "{ip[1]}", {len(ip[2])} prompt image(s) '
+                    f'from "{ip_images}"')
     if masks is not None:
         dist.print0(f'Inpainting: {len(masks[0])} mask image(s) from "{mask_images}"' + (', kept pixels composited from the init images' if masks[1] else ''))
     if world > 1 and rank == 0:
@@ -395,6 +452,9 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
         if control is not None:        # one conversion launch + the hint embedder, once per batch; the guided teacher batch is [uncond ; cond]
             hints = torch.from_numpy(load_control_batch(control[1], batch, resolution)).to(device)
             i2i['control'] = control_net.prepare(hints, scale=control[2], dup=2 if (teacher is not None and teacher[1] != 1) else 1)
+        if ip is not None:             # the image tower, the projection and ONE k|v GEMM for all layers, once per batch
+            i2i['ip'] = ip_net.prepare(ip_image_embeds(ip[2], batch, ip_tower, device), scale=ip[3],
+                                       dup=2 if (teacher is not None and teacher[1] != 1) else 1)
         with torch.no_grad():
             if teacher is not None and solver_kw is not None:
                 kw = {k: v for k, v in solver_kw.items() if k != 'negative_prompt'}

@@ -279,6 +279,29 @@ int sidlsg_attn_bwd_ps(const void* Q, const void* K, const void* V, const void* 
                        void* dK, void* dV, float* delta, int B, int H, int Nq, int Nk, int D, int ldq, int ldk, int ldv, int ldo,
                        long long bsq, long long bsk, long long bsv, long long bso, void* stream);
 
+/* ---- decoupled cross-attention of an image-prompt adapter (IP-Adapter; csrc/ip_attn.hip), forward only, no LSE -------------------
+ * O = softmax(Q K^T D^-1/2) V + s * softmax(Q K2^T D^-1/2) V2 per head, in ONE launch: two key sets (K / V the text, K2 / V2 the image
+ * tokens), each softmax normalised on its own, the two results summed in fp32 and rounded once.  Q / O are [B][Nq][ld] views with H
+ * heads side by side as in sidlsg_attn_fwd; K, V, K2 and V2 are [B][N*][ld*] views with their own token strides ld* and batch strides
+ * bs* (elements): K2 / V2 are typically column slices of one wide per-batch buffer, so ldk2 = ldv2 >> H * D and the pointers carry the
+ * column offsets.  s == 0 reads neither K2 nor V2 and gives the one-set attention.
+ * Admitted: B, H >= 1; any Nq >= 1; 1 <= Nk <= 128; 1 <= Nk2 <= 32; s finite; bf16 (plain and _ps): D a multiple of 8, 8 <= D <= 160
+ * (tiled at D rounded up to 32); fp32: D a multiple of 4, 4 <= D <= 160 (tiled at D rounded up to 16), and the fp32 LDS image
+ * 2 * (ceil16(Nk) + ceil16(Nk2)) * (ceil16(D) + 4) * 4 bytes must fit 160 KiB; all six pointers non-null and 16-byte aligned; every
+ * ld* >= H * D and every ld*, bs* a multiple of 16 bytes, bs* >= 0; B * H * workgroups-per-head < 2^31.  Anything else returns
+ * SIDLSG_EINVAL before anything is launched or written.
+ * _ps: Q holds q * (D^-1/2 * log2 e) as for sidlsg_attn_fwd_ps; the one factor serves both sets because they share q.
+ * _f32: the fp32 family, nothing rounded to bf16. */
+int sidlsg_attn_cross2_fwd(const void* Q, const void* K, const void* V, const void* K2, const void* V2, void* O, float s, int B, int H,
+                           int Nq, int Nk, int Nk2, int D, int ldq, int ldk, int ldv, int ldk2, int ldv2, int ldo, long long bsq,
+                           long long bsk, long long bsv, long long bsk2, long long bsv2, long long bso, void* stream);
+int sidlsg_attn_cross2_fwd_ps(const void* Q, const void* K, const void* V, const void* K2, const void* V2, void* O, float s, int B, int H,
+                              int Nq, int Nk, int Nk2, int D, int ldq, int ldk, int ldv, int ldk2, int ldv2, int ldo, long long bsq,
+                              long long bsk, long long bsv, long long bsk2, long long bsv2, long long bso, void* stream);
+int sidlsg_attn_cross2_fwd_f32(const void* Q, const void* K, const void* V, const void* K2, const void* V2, void* O, float s, int B, int H,
+                               int Nq, int Nk, int Nk2, int D, int ldq, int ldk, int ldv, int ldk2, int ldv2, int ldo, long long bsq,
+                               long long bsk, long long bsv, long long bsk2, long long bsv2, long long bso, void* stream);
+
 /* Fused backward of the d = 40 self-attention (attn_bwd_fused_kernel: S, dP and the exponentials once for dQ, dK and dV; the key
  * groups' partial dQ go to fp32 slabs in the stream's workspace and are added in a fixed order, so the result is bit-reproducible).
  * Taken inside sidlsg_attn_bwd / _ps when 32 < D <= 48, dK and dV are requested, Nq == Nk is a multiple of 512 and at least the

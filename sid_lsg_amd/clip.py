@@ -348,6 +348,44 @@ def load_clip(path, device, compute_dtype=None, seed=0, text_tower='torch', prep
     return HipCLIPDetector(vision, text, state['text_projection.weight'].detach().to(device, F32), tokenizer, t.eos_token_id)
 
 
+def parse_vision_config(cfg, where='config.json'):
+    """The image tower's fields from either a full CLIP config (`vision_config` + `projection_dim`) or the flat
+    CLIPVisionModelWithProjection config (the fields at top level) -> the vision namespace, checked as parse_clip_config checks it."""
+    vc = cfg['vision_config'] if isinstance(cfg.get('vision_config'), dict) else cfg
+    part = 'vision_config' if vc is not cfg else 'config'
+    for f in VISION_FIELDS:
+        if f not in vc:
+            raise KeyError(f'{where}: {part}.{f} is missing')
+    pd = cfg.get('projection_dim', vc.get('projection_dim'))
+    if pd is None:
+        raise KeyError(f'{where}: projection_dim is missing')
+    t = dict(hidden_size=8, intermediate_size=8, num_hidden_layers=1, num_attention_heads=1, hidden_act=ACTS[0], layer_norm_eps=1e-5)
+    return parse_clip_config(dict(vision_config={f: vc[f] for f in VISION_FIELDS}, text_config=t, projection_dim=int(pd)), where)[0]
+
+
+def load_clip_vision(path, device, compute_dtype=None, seed=0, preprocess='pil'):
+    """The image tower alone (HipCLIPVisionTower; an IP-Adapter's image encoder): a local directory with config.json (full CLIP config or
+    the flat CLIPVisionModelWithProjection one) and model.safetensors, of which only the vision_keys are required, or
+    'random:clip-<arch>' (the seeded image tower load_clip builds for that spec)."""
+    device = torch.device(device)
+    name = str(path)
+    if name.lower().startswith('random:'):
+        arch = name.lower()[len('random:'):]
+        if not arch.startswith('clip-') or arch[5:] not in CLIP_ARCHS:
+            raise ValueError(f"{name}: expected 'random:clip-<arch>' with <arch> in {sorted(CLIP_ARCHS)}")
+        v, t = parse_clip_config(CLIP_ARCHS[arch[5:]], name)
+        return HipCLIPVisionTower(v, _random_state(v, t, device, seed), device, compute_dtype, preprocess)
+    cj, st = os.path.join(name, 'config.json'), os.path.join(name, 'model.safetensors')
+    if not os.path.isfile(cj):
+        raise FileNotFoundError(f'{name}: not a CLIP image encoder directory (no config.json)')
+    if not os.path.isfile(st):
+        raise FileNotFoundError(f'{st}: the weights of the CLIP image encoder directory are missing')
+    with open(cj) as f:
+        v = parse_vision_config(json.load(f), cj)
+    from safetensors.torch import load_file
+    return HipCLIPVisionTower(v, load_file(st), device, compute_dtype, preprocess)
+
+
 # ---- checkpoints in open_clip's layout (HPS_v2_compressed.pt, open_clip_pytorch_model.bin, open_clip_model.safetensors) ---------------
 _OC_LAYER = (('ln_1', 'layer_norm1'), ('ln_2', 'layer_norm2'), ('attn.out_proj', 'self_attn.out_proj'), ('mlp.c_fc', 'mlp.fc1'),
              ('mlp.c_proj', 'mlp.fc2'))

@@ -1274,6 +1274,63 @@ def cross_attention(q, kv, heads, prescaled=False):
     return _Attention.apply(q, kv, heads, C // heads, 0, 0, C, prescaled)
 
 
+CROSS2_MAX_KEYS = 128         # sidlsg_attn_cross2_fwd: text keys of one (batch, head), staged in one workgroup's LDS
+CROSS2_MAX_KEYS2 = 32         # ... and image keys
+CROSS2_LDS_BYTES = 160 * 1024
+
+
+def cross_attention2(q, kv, k2v2, heads, s, prescaled=False):
+    """softmax(q k^T / sqrt(D)) v + s * softmax(q k2^T / sqrt(D)) v2 per head in ONE launch (sidlsg_attn_cross2_fwd, csrc/ip_attn.hip):
+    the decoupled cross-attention of an image-prompt adapter.  q: [B, N, C]; kv: [B, L, 2C] (the fused k|v projection of the text
+    states); k2v2: [B, T, 2C], the adapter's k|v for this layer -- contiguous or a column slice of a wider per-batch buffer (unit
+    channel stride; its row and batch strides are passed on).  1 <= L <= 128, 1 <= T <= 32; C / heads a multiple of 8 (fp32: 4) up to
+    160.  Forward only: refuses enabled autograd on an input that requires grad.  -> [B, N, C]."""
+    _chk(q, ACT)
+    _chk(kv, q.dtype)
+    if not k2v2.is_cuda or k2v2.dtype != q.dtype:
+        raise RuntimeError(f'cross_attention2: the image keys / values must be {q.dtype} CUDA(HIP) tensors, got {k2v2.dtype} on {k2v2.device}')
+    if torch.is_grad_enabled() and (q.requires_grad or kv.requires_grad or k2v2.requires_grad):
+        raise RuntimeError('cross_attention2 is forward only (no backward kernel): call it under torch.no_grad()')
+    if q.dim() != 3 or kv.dim() != 3 or k2v2.dim() != 3:
+        raise RuntimeError('cross_attention2: q, kv and k2v2 must be [B, tokens, channels]')
+    B, Nq, C = q.shape
+    es = q.element_size()
+    sfx = '_ps' if (prescaled and q.dtype == BF16) else ''
+    if prescaled and not sfx:
+        raise RuntimeError('pre-scaled queries exist in the bf16 compute mode only')
+    if heads <= 0 or C % heads:
+        raise RuntimeError(f'cross_attention2: {heads} heads do not divide {C} channels')
+    D = C // heads
+    step = 4 if q.dtype == F32 else 8
+    if D % step or D > 160:
+        raise RuntimeError(f'cross_attention2: head width {D} is not admitted: it must be a multiple of {step} up to 160')
+    if kv.shape[0] != B or kv.shape[2] != 2 * C:
+        raise RuntimeError(f'cross_attention2: kv {tuple(kv.shape)}: expected [{B}, L, {2 * C}]')
+    if tuple(k2v2.shape[::2]) != (B, 2 * C):
+        raise RuntimeError(f'cross_attention2: k2v2 {tuple(k2v2.shape)}: expected [{B}, T, {2 * C}]')
+    Nk, Nk2 = kv.shape[1], k2v2.shape[1]
+    if not 1 <= Nk <= CROSS2_MAX_KEYS:
+        raise RuntimeError(f'cross_attention2: {Nk} text keys: the kernel admits 1 .. {CROSS2_MAX_KEYS}')
+    if not 1 <= Nk2 <= CROSS2_MAX_KEYS2:
+        raise RuntimeError(f'cross_attention2: {Nk2} image keys: the kernel admits 1 .. {CROSS2_MAX_KEYS2}')
+    ld2, bs2 = k2v2.stride(1), k2v2.stride(0)
+    if k2v2.stride(2) != 1 or ld2 < 2 * C or (ld2 * es) % 16 or (bs2 * es) % 16 or (k2v2.data_ptr() % 16) or bs2 < 0:
+        raise RuntimeError(f'cross_attention2: k2v2 strides {tuple(k2v2.stride())}: expected unit channel stride and 16-byte aligned rows, '
+                           'batches and base address')
+    if q.dtype == F32:
+        r16 = lambda n: (n + 15) // 16 * 16      # noqa: E731
+        need = 2 * (r16(Nk) + r16(Nk2)) * (r16(D) + 4) * 4
+        if need > CROSS2_LDS_BYTES:
+            raise RuntimeError(f'cross_attention2 (fp32): {Nk} + {Nk2} keys of width {D} need {need} bytes of LDS, more than {CROSS2_LDS_BYTES}')
+    s = float(s)
+    if s != s or s in (float('inf'), float('-inf')):
+        raise RuntimeError(f'cross_attention2: scale {s} is not finite')
+    o = torch.empty((B, Nq, C), device=q.device, dtype=q.dtype)
+    _fn('attn_cross2_fwd' + sfx, q.dtype)(_p(q), _p(kv), kv.data_ptr() + C * es, k2v2.data_ptr(), k2v2.data_ptr() + C * es, _p(o), s,
+                                        B, heads, Nq, Nk, Nk2, D, C, 2 * C, 2 * C, ld2, ld2, C, Nq * C, Nk * 2 * C, Nk * 2 * C, bs2, bs2, Nq * C, _s())
+    return o
+
+
 class _GEGLU(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h):

@@ -284,6 +284,15 @@ def load_controlnet(spec, unet, device, seed=0):
     return cn.HipControlNet(net.cfg, compute_dtype=net.compute_dtype).materialize(torch.device(device), seed=seed if s is None else s)
 
 
+def load_ip_adapter(spec, unet, device, embed_dim, seed=0):
+    """An IP-Adapter (ip_adapter.HipIPAdapter) for `unet`, in its compute dtype, for an image encoder of projection_dim `embed_dim`: a
+    local `.safetensors` / `.bin` file in the published layout or 'random:ip-adapter[:seed]' (ip_adapter.load_ip_adapter)."""
+    from . import ip_adapter as ipa
+    net = _unwrap(unet)
+    _require_hip(net)
+    return ipa.load_ip_adapter(spec, net, torch.device(device), embed_dim, seed=seed)
+
+
 def encode_contexts(contexts, text_encoder, tokenizer, device):
     """list[str] -> [B, L, D] text states (no grad); a tensor is passed through (pre-computed states)."""
     if torch.is_tensor(contexts):
@@ -295,12 +304,12 @@ def encode_contexts(contexts, text_encoder, tokenizer, device):
 
 
 # ------------------------------------------------------------------------------------------------
-def hip_generate(unet, z, ctx16, init_t, sched, x0=None, control=None):
+def hip_generate(unet, z, ctx16, init_t, sched, x0=None, control=None, ip=None):
     """x_t = s0*x0 + s1*z at t_init ; o = G(x_t) ; x_hat = (x_t - s1*o)/s0 (epsilon) or s0*x_t - s1*o (v)   (sid_sd_util.py:182-185)"""
     s0, s1 = sched.coefficients(init_t)
     net = _unwrap(unet)
     xin, xt = ops.noisy_input(x0, z, s0, s1, 1, net.compute_dtype)
-    eps = _ddp_exchange(unet, net.forward_nhwc(xin, init_t, ctx16, control=control))
+    eps = _ddp_exchange(unet, net.forward_nhwc(xin, init_t, ctx16, control=control, ip=ip))
     return ops.cfg_x0(eps, xt, s0, s1, 1.0, True, net.compute_dtype, prediction_type=sched.config.prediction_type)
 
 
@@ -364,8 +373,10 @@ def hip_denoise(unet, prep, guidance_scale, predict_x0):
 # ------------------------------------------------------------------------------------------------
 def sid_sd_sampler(unet, latents, contexts, init_timesteps, noise_scheduler, text_encoder, tokenizer, resolution,
                    dtype=torch.float16, return_images=False, vae=None, guidance_scale=1, num_steps=1, train_sampler=True,
-                   num_steps_eval=1, init_latents=None, start_step=0, mask=None, control=None):
-    """control (eval mode only): a controlnet.ControlState (HipControlNet.prepare(images, scale, dup=1)), passed to every UNet call of the loop.
+                   num_steps_eval=1, init_latents=None, start_step=0, mask=None, control=None, ip=None):
+    """ip (eval mode only): an ip_adapter.IPState (HipIPAdapter.prepare(image_embeds, scale, dup=1)), passed to every UNet call of the loop;
+    it composes with control.
+    control (eval mode only): a controlnet.ControlState (HipControlNet.prepare(images, scale, dup=1)), passed to every UNet call of the loop.
     init_latents / start_step (eval mode only; image-to-image): the chain is entered at step `start_step` with D_x = init_latents
     (scaled latents [B, 4, h, w], e.g. HipAutoencoderKLEncoder.encode_latents); the first executed step takes `latents` as its noise,
     so its input is x_{t_k} = s0 init_latents + s1 latents -- what a generator trained with --num_steps N saw at step k.
@@ -388,6 +399,8 @@ def sid_sd_sampler(unet, latents, contexts, init_timesteps, noise_scheduler, tex
         mask = check_mask(mask, init_latents, latents, 'sid_sd_sampler')
     if control is not None and train_sampler:
         raise ValueError('sid_sd_sampler: control is for the evaluation sampler (train_sampler=False): ControlNet conditioning is forward only')
+    if ip is not None and train_sampler:
+        raise ValueError('sid_sd_sampler: ip is for the evaluation sampler (train_sampler=False): IP-Adapter conditioning is forward only')
     _require_hip(unet)
     check_prediction_type(unet, noise_scheduler)
     emb = encode_contexts(contexts, text_encoder, tokenizer, latents.device).to(_unwrap(unet).compute_dtype).contiguous()
@@ -405,7 +418,7 @@ def sid_sd_sampler(unet, latents, contexts, init_timesteps, noise_scheduler, tex
             for i in range(start_step, steps):
                 noise = latents if i == start_step else torch.randn_like(latents)
                 t_i = (init_timesteps * (1 - i / steps)).to(torch.long)
-                D_x = hip_generate(unet, noise.to(torch.float32).contiguous(), emb, t_i.contiguous(), noise_scheduler, x0=D_x, control=control)
+                D_x = hip_generate(unet, noise.to(torch.float32).contiguous(), emb, t_i.contiguous(), noise_scheduler, x0=D_x, control=control, ip=ip)
                 if mask is not None:
                     D_x = ops.masked_renoise(D_x, z0, mask, want_input=False, inplace=True)[1]
     if not return_images:
@@ -496,7 +509,7 @@ def teacher_sample(unet, latents, contexts, noise_scheduler, text_encoder, token
 
 def teacher_sample_i2i(unet, latents, contexts, noise_scheduler, text_encoder, tokenizer, resolution, guidance_scale=TEACHER_CFG,
                        num_inference_steps=TEACHER_STEPS, return_images=False, vae=None, schedule_config=None, init_latents=None,
-                       start_index=0, mask=None, control=None):
+                       start_index=0, mask=None, control=None, ip=None):
     """The teacher itself, sampled the way every SiD-LSG table samples it: classifier-free guidance and an N-step deterministic DDIM
     sampler (Song et al. 2021, eta = 0; diffusers' DDIMScheduler with 'leading' spacing).  x_T = latents (DDIM's init_noise_sigma is
     1); per step one UNet pass on the stacked [uncond ; cond] batch (unconditional prompt '', as sid_sd_denoise) and one
@@ -513,6 +526,8 @@ def teacher_sample_i2i(unet, latents, contexts, noise_scheduler, text_encoder, t
     is_strength_max).  These rules restate diffusers' img2img / inpainting pipelines; agreement with the package is not pinned by a test.
     control: a controlnet.ControlState (HipControlNet.prepare(images, scale, dup=2 with guidance, else 1)), passed to every UNet call; it
     composes with init_latents / start_index / mask and needs none of them (teacher_sample keeps its pinned signature: the argument lives here).
+    ip: an ip_adapter.IPState (HipIPAdapter.prepare(image_embeds, scale, dup=2 with guidance, else 1)), passed to every UNet call; it
+    composes with control and with the image-to-image arguments in the same way.
     -> the final latent x_0 fp32 NCHW, or (return_images) the decoded images as sid_sd_sampler returns them."""
     _require_hip(unet)
     check_prediction_type(unet, noise_scheduler)
@@ -539,7 +554,7 @@ def teacher_sample_i2i(unet, latents, contexts, noise_scheduler, text_encoder, t
         else:
             xin, xt = ops.noisy_input(None, z, ones, ones, dup, dt)      # x_T = z, as the [uncond ; cond] NHWC batch
         for i in range(start_index, n):
-            eps = net.forward_nhwc(xin, tt[i], ctx, control=control)
+            eps = net.forward_nhwc(xin, tt[i], ctx, control=control, ip=ip)
             last = i == n - 1
             xin, xt, _ = ops.ddim_step(eps, xt, s0[i], s1[i], s0p[i], s1p[i], guidance_scale, dt, prediction_type=pt,
                                        last=last or mask is not None)
@@ -571,7 +586,7 @@ def teacher_sample_solver(unet, latents, contexts, noise_scheduler, text_encoder
 def teacher_sample_solver_i2i(unet, latents, contexts, noise_scheduler, text_encoder, tokenizer, resolution, guidance_scale=TEACHER_CFG,
                               num_inference_steps=TEACHER_STEPS, return_images=False, vae=None, schedule_config=None, solver='dpmpp2m',
                               spacing=None, eta=0.0, guidance_rescale=0.0, negative_contexts=None, randn=None, init_latents=None,
-                              start_index=0, mask=None, control=None):
+                              start_index=0, mask=None, control=None, ip=None):
     """The teacher under the solvers it is usually run with: `solver` 'dpmpp2m' (DPM-Solver++ 2M) or 'ddim' (any `eta` >= 0), timestep
     `spacing` 'leading' / 'trailing' / 'linspace' (None: the model's timestep_spacing), guidance rescale `guidance_rescale` (phi of
     Lin et al. 2024; 0 = plain classifier-free guidance) and `negative_contexts` in place of '' in the unconditional half.  The
@@ -583,7 +598,7 @@ def teacher_sample_solver_i2i(unet, latents, contexts, noise_scheduler, text_enc
     init_latents / start_index / mask: image-to-image and inpainting as in teacher_sample.  The tables are solver_schedule's with
     start = start_index (DPM-Solver++ 2M takes its first executed step at first order); the masked boundary of step i noises the known
     region to the level of t_{i+1}, known = s0[i+1]*z0 + s1[i+1]*latents (after the last step: z0), and leaves the x0 history alone.
-    control: a controlnet.ControlState, as in teacher_sample_i2i.
+    control: a controlnet.ControlState, ip: an ip_adapter.IPState, as in teacher_sample_i2i.
     -> the final latent x_0 fp32 NCHW, or (return_images) the decoded images as sid_sd_sampler returns them."""
     _require_hip(unet)
     check_prediction_type(unet, noise_scheduler)
@@ -624,7 +639,7 @@ def teacher_sample_solver_i2i(unet, latents, contexts, noise_scheduler, text_enc
         history = [torch.empty_like(z), torch.empty_like(z)]
         x0_prev = None
         for i in range(start_index, n):
-            eps = net.forward_nhwc(xin, tt[i], ctx, control=control)
+            eps = net.forward_nhwc(xin, tt[i], ctx, control=control, ip=ip)
             scale = ops.cfg_rescale_stats(eps, z.shape[1], guidance_scale, phi) if guided and phi != 0 else None
             noise = randn(tuple(z.shape)).to(device=dev, dtype=torch.float32).contiguous() if flags[i][3] else None
             last = i == n - 1
