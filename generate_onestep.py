@@ -45,7 +45,14 @@ or `random:ip-adapter[:seed]`; the image encoder is a local CLIP directory (conf
 sample `idx` takes prompt image `idx % len(files)` of DIR, any size (the encoder's CLIPImageProcessor transform resizes).  `--ip_scale`
 (default 1) scales the image attention; 0 issues exactly the launches of a run without the options.  It applies wherever `--controlnet`
 does and combines with it.
+
+`--fidelity 1` (with `--init_images`) compares every written image, as the uint8 that goes into its PNG, with the init image it started
+from (the crop load_init_image produced) on the device: PSNR and SSIM (sid_lsg_amd.fidelity, sidlsg_psnr_ssim_u8), and LPIPS-VGG when
+`--lpips_vgg SPEC --lpips_lin SPEC` name a torchvision VGG16 state dict and the lpips package's lin weights (or
+`random:lpips-vgg[:seed]` for both).  With `--mask_images` the `_keep` figures are those of the kept region (mask < 128).  Rank 0 writes
+`<outdir>/fidelity.json` (`options`, `per_image` keyed by PNG name, `mean`).  Without the option nothing changes.
 """
+import json
 import math
 import os
 import pickle
@@ -57,6 +64,9 @@ import torch
 
 from sid_lsg_amd import distributed as dist
 from sid_lsg_amd.clip import load_clip_vision
+from sid_lsg_amd.fidelity import aggregate as aggregate_fidelity
+from sid_lsg_amd.fidelity import check_specs as check_lpips_specs
+from sid_lsg_amd.fidelity import format_means, load_lpips, score_batch
 from sid_lsg_amd.preview import save_png
 from sid_lsg_amd.sd_util import (TEACHER, TEACHER_CFG, TEACHER_STEPS, check_prediction_type, load_controlnet, load_ip_adapter, load_sd15, load_vae_encoder,
                                  sid_sd_sampler, teacher_sample_i2i, teacher_sample_solver_i2i, teacher_start_index)
@@ -316,6 +326,23 @@ def ip_options(ip_adapter, ip_image_encoder, ip_images, ip_scale):
     return ip_adapter, ip_image_encoder, list_ip_images(ip_images), 1.0 if ip_scale is None else float(ip_scale)
 
 
+def fidelity_options(init_images, fidelity, lpips_vgg, lpips_lin):
+    """-> None without --fidelity, else (lpips_vgg, lpips_lin) (both None: PSNR and SSIM only); inconsistent options are refused."""
+    given = [f for f, v in (('--lpips_vgg', lpips_vgg), ('--lpips_lin', lpips_lin)) if v is not None]
+    if not fidelity:
+        if given:
+            raise click.UsageError(f'{" / ".join(given)} apply to --fidelity 1 only')
+        return None
+    if init_images is None:
+        raise click.UsageError('--fidelity applies to --init_images only: an output is compared with the init image it started from')
+    if given:
+        try:
+            check_lpips_specs(lpips_vgg, lpips_lin)
+        except ValueError as e:
+            raise click.UsageError(str(e))
+    return lpips_vgg, lpips_lin
+
+
 def load_ip_image(path):
     """-> uint8 [3, H, W] RGB, any size: the image encoder's transform resizes."""
     import PIL.Image
@@ -365,11 +392,14 @@ def ip_image_embeds(files, indices, tower, device):
 @click.option('--ip_image_encoder', type=str, default=None, metavar='DIR', help='CLIP image encoder of --ip_adapter: a local directory (config.json, model.safetensors), or random:clip-<arch>')
 @click.option('--ip_images', type=str, default=None, metavar='DIR', help='Prompt images of --ip_adapter, any size: PNG/JPEG files (sorted by name); sample idx uses file idx mod len(files)')
 @click.option('--ip_scale', type=click.FloatRange(min=0), default=None, help='Scale of the image attention  [default: 1]')
+@click.option('--fidelity', type=bool, default=False, show_default=True, help='With --init_images: PSNR / SSIM (and LPIPS) of every written image against its init image -> <outdir>/fidelity.json')
+@click.option('--lpips_vgg', type=str, default=None, metavar='SPEC', help='With --fidelity: a torch.save\'d torchvision VGG16 state dict, or random:lpips-vgg[:seed]; needs --lpips_lin')
+@click.option('--lpips_lin', type=str, default=None, metavar='SPEC', help='With --fidelity: the lin weights of the lpips package (its vgg.pth), or random:lpips-vgg[:seed]; needs --lpips_vgg')
 @click.option('--text_encoder', type=click.Choice(['torch', 'hip']), default=None, help='CLIP text encoder: the PyTorch module, or the same weights on the HIP kernels  [default: $SIDLSG_TEXT_ENCODER, else torch] (not a reference option)')
 def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, init_timestep, text_prompts, repo_id, resolution, use_fp16,
          enable_compress_npz, num_steps_eval, custom_seed, teacher_steps, guidance_scale, init_images, strength, sample_posterior, text_encoder,
          teacher_sampler, teacher_spacing, teacher_eta, guidance_rescale, negative_prompt, mask_images, mask_composite, controlnet, control_images,
-         control_scale, ip_adapter, ip_image_encoder, ip_images, ip_scale):
+         control_scale, ip_adapter, ip_image_encoder, ip_images, ip_scale, fidelity, lpips_vgg, lpips_lin):
     text_encoder_kind = text_encoder
     if resolution % 8:
         raise click.BadParameter(f'{resolution}: must be a multiple of 8', param_hint='--resolution')
@@ -379,6 +409,7 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
     masks = mask_options(init_images, mask_images, mask_composite, 0 if img2img is None else len(img2img[0]))
     control = control_options(controlnet, control_images, control_scale)
     ip = ip_options(ip_adapter, ip_image_encoder, ip_images, ip_scale)
+    fid = fidelity_options(init_images, fidelity, lpips_vgg, lpips_lin)
     dist.init()
     device = torch.device('cuda')
     rank, world = dist.get_rank(), dist.get_world_size()
@@ -422,6 +453,10 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
                     f'from "{ip_images}"')
     if masks is not None:
         dist.print0(f'Inpainting: {len(masks[0])} mask image(s) from "{mask_images}"' + (', kept pixels composited from the init images' if masks[1] else ''))
+    if fid is not None:
+        lpips_net = load_lpips(fid[0], fid[1], device) if fid[0] is not None else None
+        fid_rows = {}
+        dist.print0('Fidelity against the init images: PSNR, SSIM' + (f', LPIPS-VGG "{fid[0]}" / "{fid[1]}"' if lpips_net is not None else ''))
     if world > 1 and rank == 0:
         torch.distributed.barrier()
     if teacher is None and num_steps_eval > 1:
@@ -476,12 +511,31 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
         arr = (images.float() * 127.5 + 128).clip(0, 255).to(torch.uint8).permute(0, 2, 3, 1).cpu().numpy()
         if masks is not None and masks[1]:
             arr = composite(arr, init_pixels, pixel_mask)
+        if fid is not None:            # the uint8 that goes into the PNG against the crop load_init_image produced, both on the device
+            rows = score_batch(pixels.permute(0, 3, 1, 2).contiguous(), torch.from_numpy(np.ascontiguousarray(arr)).to(device).permute(0, 3, 1, 2).contiguous(),
+                               None if masks is None else torch.from_numpy(pixel_mask).to(device), lpips_net)
+            fid_rows.update({f'{key:06d}.png': row for key, row in zip(batch, rows)})
         for key, img in zip(batch, arr):
             d = os.path.join(outdir, f'{key - key % 1000:06d}') if subdirs else outdir
             os.makedirs(d, exist_ok=True)
             save_png(os.path.join(d, f'{key:06d}.png'), np.ascontiguousarray(img))
         if enable_compress_npz:
             np.savez_compressed(os.path.join(outdir, f'images_{batch[0]:06d}.npz'), images=arr)
+    if fid is not None:
+        if world > 1:
+            parts = [None] * world
+            torch.distributed.all_gather_object(parts, fid_rows)
+            fid_rows = {k: v for part in parts for k, v in part.items()}
+        if rank == 0:
+            fid_rows = dict(sorted(fid_rows.items()))
+            report = dict(options=dict(network=network_pkl, init_images=init_images, mask_images=mask_images, mask_composite=bool(mask_composite),
+                                       strength=strength, init_timestep=init_timestep, num_steps_eval=num_steps_eval, resolution=resolution,
+                                       teacher_steps=teacher_steps, controlnet=controlnet, ip_adapter=ip_adapter, lpips_vgg=fid[0], lpips_lin=fid[1]),
+                          per_image=fid_rows, mean=aggregate_fidelity(fid_rows))
+            os.makedirs(outdir, exist_ok=True)
+            with open(os.path.join(outdir, 'fidelity.json'), 'w') as f:      # inf / nan are written as Infinity / NaN, which json.load reads back
+                json.dump(report, f, indent=1)
+            dist.print0(f'Fidelity over {len(fid_rows)} images: {format_means(report["mean"])}')
     if world > 1:
         torch.distributed.barrier()
     dist.print0('Done.')

@@ -495,6 +495,45 @@ int sidlsg_pool2d_f32(const float* X, int ldx, float* Y, int ldy, int B, int H, 
                       void* stream);
 int sidlsg_inception_input_u8(const void* images, float* out, int B, int H, int W, void* stream);
 
+/* ---- paired image fidelity: PSNR, SSIM, LPIPS (sid_lsg_amd/fidelity.py, csrc/fidelity.hip) ----------------------------------------
+ * No atomics, no data-dependent loops: one workspace slot per workgroup and quantity, added by a second launch in a fixed order, so
+ * the same inputs give the same bits on every run.
+ * sidlsg_psnr_ssim_u8: a, b uint8 [B][3][H][W]; mask uint8 [B][H][W] or NULL (NULL = every pixel kept); a pixel is KEPT when its
+ *   mask byte is < 128 (the convention of --mask_images).  out [B][8] doubles:
+ *     0 sse       sum over the 3 channels and all pixels of (a - b)^2 (an integer below 2^53, exact in the double)
+ *     1 n         number of terms of sse = 3 H W
+ *     2 ssim_sum  sum of the SSIM index over the 3 channels and the (H - 10) x (W - 10) valid window centres
+ *     3 ssim_n    number of terms of ssim_sum
+ *     4..7        the same four restricted to kept positions; a kept SSIM term is a window whose CENTRE pixel is kept (the window
+ *                 itself may cover pixels that are not).
+ *   SSIM (Wang et al.): 11 x 11 separable Gaussian window, sigma 1.5, weights exp(-x^2 / (2 sigma^2)), x = -5..5, normalised (built
+ *   in double on the host); K1 = 0.01, K2 = 0.03, L = 255; population moments; valid windows only.  The five window moments
+ *   (x, y, x^2, y^2, xy: the horizontal pass first, then the vertical) and the formula
+ *   ((2 mx my + C1)(2 cov + C2)) / ((mx^2 + my^2 + C1)(vx + vy + C2)) are evaluated in fp64, each operation rounded once; a window
+ *   over bit-identical pixels gives exactly 1.  ws: sidlsg_psnr_ssim_ws_doubles(B, H, W) doubles (a host query; negative for
+ *   sizes the entry point rejects).  SIDLSG_EINVAL, and no launch, for H or W < 11, B < 1 or > 21845, null a / b / out / ws, out or
+ *   ws not 8-byte aligned, an operand of 2^31 bytes or more.
+ * sidlsg_lpips_input_u8: a, b uint8 [B][3][H][W] -> out fp32 NHWC [2B][H][W][4], rows 0..B-1 from a, rows B..2B-1 from b, channel 3
+ *   zero (the 4-channel feed of sidlsg_conv2d_relu_f32).  In fp32, exactly: t = x / 127.5f; t = t - 1; (t - shift_c) / scale_c, IEEE
+ *   divisions.  out 16-byte aligned, scale_c != 0, fewer than 2^31 output bytes; SIDLSG_EINVAL and no launch otherwise.
+ * sidlsg_lpips_layer_f32: F fp32 NHWC [2B][h][wd][ldf] of which the first C channels are read, w [C] ->
+ *   out[i] (double) = mean over the h wd pixels of  sum_c w_c (f0_c / (|f0|_2 + 1e-10) - f1_c / (|f1|_2 + 1e-10))^2,  f0 the pixel of
+ *   row i, f1 that of row B + i, the norms over the C channels.  Per pixel in fp32, each operation rounded once: 16 lanes share a
+ *   pixel, lane l sums the elements of its 16-byte chunks l, l + 16, .. in channel order, the lanes are added by an xor butterfly
+ *   (8, 4, 2, 1); the pixel values are added in double.  Bit-identical f0 and f1, and a pixel that is all zero in both, give exactly
+ *   0.  ws: sidlsg_lpips_layer_ws_doubles(B, h, wd) doubles.  C and ldf multiples of 4, ldf >= C, F and w 16-byte aligned, out and
+ *   ws 8-byte aligned, B <= 32767, F below 2^31 bytes; SIDLSG_EINVAL and no launch otherwise.
+ * sidlsg_lpips_sum_f64: vals [taps][B] doubles -> out[i] = ((vals[0][i] + vals[1][i]) + vals[2][i]) + .., the taps of a pair added in
+ *   order: a pair's LPIPS does not depend on the batch it travels in (a library reduction may pick its order by the shape).
+ *   1 <= taps <= 64, 1 <= B <= 32767, 8-byte aligned pointers; SIDLSG_EINVAL and no launch otherwise. */
+int sidlsg_psnr_ssim_ws_doubles(int B, int H, int W);
+int sidlsg_psnr_ssim_u8(const void* a, const void* b, const void* mask, int B, int H, int W, double* out, double* ws, void* stream);
+int sidlsg_lpips_input_u8(const void* a, const void* b, float* out, int B, int H, int W, float shift0, float shift1, float shift2,
+                          float scale0, float scale1, float scale2, void* stream);
+int sidlsg_lpips_layer_ws_doubles(int B, int h, int wd);
+int sidlsg_lpips_layer_f32(const float* F, int ldf, const float* w, int B, int h, int wd, int C, double* out, double* ws, void* stream);
+int sidlsg_lpips_sum_f64(const double* vals, int taps, int B, double* out, void* stream);
+
 /* ---- snapshot preview grids (save_image_grid, sid_training_loop.py:99-115, 597-614) -------------------------------------
  * B decoded fp32 images -> their tiles of ONE uint8 grid image [gh*H][gw*W][3] (HWC, what a PNG writer takes): image i goes to
  * tile first + i, row (first + i) / gw, column (first + i) % gw, so the batches of a grid are placed as they leave the decoder and

@@ -6,7 +6,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
-SOURCES = ['gemm.hip', 'norm.hip', 'attention.hip', 'elementwise.hip', 'optim.hip', 'fp32.hip', 'trace.hip', 'image_grid.hip', 'pr_dist.hip', 'clip.hip', 'attn_wide.hip', 'vae_io.hip', 'text.hip', 'hps.hip', 'solver.hip', 'inpaint.hip', 'mmd.hip', 'inception.hip', 'controlnet.hip', 'ip_attn.hip']
+SOURCES = ['gemm.hip', 'norm.hip', 'attention.hip', 'elementwise.hip', 'optim.hip', 'fp32.hip', 'trace.hip', 'image_grid.hip', 'pr_dist.hip', 'clip.hip', 'attn_wide.hip', 'vae_io.hip', 'text.hip', 'hps.hip', 'solver.hip', 'inpaint.hip', 'mmd.hip', 'inception.hip', 'controlnet.hip', 'ip_attn.hip', 'fidelity.hip']
 LIB = os.path.join(PKG, 'libsidlsg_hip.so')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-munsafe-fp-atomics', '-Wno-unused-result']
 # Per-file extras.  attention.hip: the softmax works on MFMA results with VALU ops; with the default heuristics the
@@ -19,9 +19,10 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-munsafe-fp-ato
 # inpaint.hip: likewise the known region of the masked step boundary (a rounded product, then one fma), bit-equal to noisy_input's x_t.
 # controlnet.hip: likewise the control image's conversion (one division).
 # inception.hip: likewise the detector's input resize (two lerps, subtract, divide); its MFMA contractions are not affected.
+# fidelity.hip: likewise the SSIM moments and formula (fp64), the LPIPS input (divide, subtract, subtract, divide) and the per-tap distance.
 EXTRA = {'attention.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form', '-fno-honor-nans'], 'image_grid.hip': ['-ffp-contract=off'],
          'clip.hip': ['-ffp-contract=off'], 'vae_io.hip': ['-ffp-contract=off'], 'hps.hip': ['-ffp-contract=off'], 'inpaint.hip': ['-ffp-contract=off'],
-         'inception.hip': ['-ffp-contract=off'], 'controlnet.hip': ['-ffp-contract=off']}
+         'inception.hip': ['-ffp-contract=off'], 'controlnet.hip': ['-ffp-contract=off'], 'fidelity.hip': ['-ffp-contract=off']}
 
 
 def digest():
