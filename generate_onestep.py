@@ -46,6 +46,12 @@ sample `idx` takes prompt image `idx % len(files)` of DIR, any size (the encoder
 (default 1) scales the image attention; 0 issues exactly the launches of a run without the options.  It applies wherever `--controlnet`
 does and combines with it.
 
+`--lora SPEC` (repeatable) merges LoRA files into the UNet and the text encoder before sampling (sid_lsg_amd.lora.LoraSet: one merge launch
+per network on the fp32 masters, then the usual refresh of the compute copies): SPEC is a local kohya / A1111 or diffusers / PEFT
+`.safetensors` / `.bin` / `.pt` file, or `random:lora[:rank[:seed]]`.  `--lora_scale S` (repeatable: none = 1, one value for all files, or
+one per file; negative allowed) scales them; 0 leaves weights equal (torch.equal) to those of a run without `--lora`.  The sampling loop is untouched, so it applies to
+snapshots and to `--network teacher` under every option above, and a LoRA run issues exactly the launches of the plain run per step.
+
 `--fidelity 1` (with `--init_images`) compares every written image, as the uint8 that goes into its PNG, with the init image it started
 from (the crop load_init_image produced) on the device: PSNR and SSIM (sid_lsg_amd.fidelity, sidlsg_psnr_ssim_u8), and LPIPS-VGG when
 `--lpips_vgg SPEC --lpips_lin SPEC` name a torchvision VGG16 state dict and the lpips package's lin weights (or
@@ -68,7 +74,7 @@ from sid_lsg_amd.fidelity import aggregate as aggregate_fidelity
 from sid_lsg_amd.fidelity import check_specs as check_lpips_specs
 from sid_lsg_amd.fidelity import format_means, load_lpips, score_batch
 from sid_lsg_amd.preview import save_png
-from sid_lsg_amd.sd_util import (TEACHER, TEACHER_CFG, TEACHER_STEPS, check_prediction_type, load_controlnet, load_ip_adapter, load_sd15, load_vae_encoder,
+from sid_lsg_amd.sd_util import (TEACHER, TEACHER_CFG, TEACHER_STEPS, check_prediction_type, load_controlnet, load_ip_adapter, load_lora, load_sd15, load_vae_encoder, lora_scales,
                                  sid_sd_sampler, teacher_sample_i2i, teacher_sample_solver_i2i, teacher_start_index)
 
 
@@ -326,6 +332,16 @@ def ip_options(ip_adapter, ip_image_encoder, ip_images, ip_scale):
     return ip_adapter, ip_image_encoder, list_ip_images(ip_images), 1.0 if ip_scale is None else float(ip_scale)
 
 
+def lora_options(lora, lora_scale):
+    """-> None without --lora, else (specs, scales): --lora_scale may be given never, once (for all files) or once per file; anything
+    else, and --lora_scale without --lora, is a usage error."""
+    try:
+        scales = lora_scales(len(lora or ()), lora_scale)
+    except ValueError as e:
+        raise click.UsageError(str(e))
+    return (list(lora), scales) if lora else None
+
+
 def fidelity_options(init_images, fidelity, lpips_vgg, lpips_lin):
     """-> None without --fidelity, else (lpips_vgg, lpips_lin) (both None: PSNR and SSIM only); inconsistent options are refused."""
     given = [f for f, v in (('--lpips_vgg', lpips_vgg), ('--lpips_lin', lpips_lin)) if v is not None]
@@ -392,6 +408,8 @@ def ip_image_embeds(files, indices, tower, device):
 @click.option('--ip_image_encoder', type=str, default=None, metavar='DIR', help='CLIP image encoder of --ip_adapter: a local directory (config.json, model.safetensors), or random:clip-<arch>')
 @click.option('--ip_images', type=str, default=None, metavar='DIR', help='Prompt images of --ip_adapter, any size: PNG/JPEG files (sorted by name); sample idx uses file idx mod len(files)')
 @click.option('--ip_scale', type=click.FloatRange(min=0), default=None, help='Scale of the image attention  [default: 1]')
+@click.option('--lora', type=str, multiple=True, metavar='SPEC', help='LoRA file merged into the UNet and the text encoder (repeatable): a local kohya / diffusers .safetensors / .bin / .pt file, or random:lora[:rank[:seed]]')
+@click.option('--lora_scale', type=float, multiple=True, help='Scale of --lora (repeatable: one for all files, or one per file; negative allowed)  [default: 1]')
 @click.option('--fidelity', type=bool, default=False, show_default=True, help='With --init_images: PSNR / SSIM (and LPIPS) of every written image against its init image -> <outdir>/fidelity.json')
 @click.option('--lpips_vgg', type=str, default=None, metavar='SPEC', help='With --fidelity: a torch.save\'d torchvision VGG16 state dict, or random:lpips-vgg[:seed]; needs --lpips_lin')
 @click.option('--lpips_lin', type=str, default=None, metavar='SPEC', help='With --fidelity: the lin weights of the lpips package (its vgg.pth), or random:lpips-vgg[:seed]; needs --lpips_vgg')
@@ -399,7 +417,7 @@ def ip_image_embeds(files, indices, tower, device):
 def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, init_timestep, text_prompts, repo_id, resolution, use_fp16,
          enable_compress_npz, num_steps_eval, custom_seed, teacher_steps, guidance_scale, init_images, strength, sample_posterior, text_encoder,
          teacher_sampler, teacher_spacing, teacher_eta, guidance_rescale, negative_prompt, mask_images, mask_composite, controlnet, control_images,
-         control_scale, ip_adapter, ip_image_encoder, ip_images, ip_scale, fidelity, lpips_vgg, lpips_lin):
+         control_scale, ip_adapter, ip_image_encoder, ip_images, ip_scale, fidelity, lpips_vgg, lpips_lin, lora, lora_scale):
     text_encoder_kind = text_encoder
     if resolution % 8:
         raise click.BadParameter(f'{resolution}: must be a multiple of 8', param_hint='--resolution')
@@ -410,6 +428,7 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
     control = control_options(controlnet, control_images, control_scale)
     ip = ip_options(ip_adapter, ip_image_encoder, ip_images, ip_scale)
     fid = fidelity_options(init_images, fidelity, lpips_vgg, lpips_lin)
+    lora_opt = lora_options(lora, lora_scale)
     dist.init()
     device = torch.device('cuda')
     rank, world = dist.get_rank(), dist.get_world_size()
@@ -439,6 +458,8 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
         G_ema.eval().requires_grad_(False)
         if num_steps_eval != 1:
             dist.print0(f'Note: --num_steps_eval {num_steps_eval} is ignored with --network {TEACHER} (the step count is --teacher_steps)')
+    if lora_opt is not None:           # merged once, before anything derives from the weights; the sampling loop below does not change
+        load_lora(lora_opt[0], lora_opt[1], G_ema, text_encoder, log=dist.print0)
     if img2img is not None:
         vae_encoder = load_vae_encoder(repo_id, device)
         dist.print0(f'Image-to-image: {len(img2img[0])} init images from "{init_images}", entering at step {img2img[1]} of '

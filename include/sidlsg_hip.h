@@ -437,6 +437,28 @@ int sidlsg_transpose_w16_batched(const void* jobs, int njobs, int nblocks, void*
  * sorted by blk0 = index of the job's first block of 2048 elements; nblocks = total. */
 int sidlsg_scale_cast_ranges(const void* jobs, int njobs, int nblocks, void* stream);
 
+/* ---- LoRA merge (csrc/lora.hip): low-rank updates of fp32 master weights, every touched layer of a network in ONE launch ------
+ * Replaces the per-layer `W += scale * alpha / rank * (up @ down)` of the kohya / diffusers loaders.  For every job
+ *   dst[n][k] = base[n][k] + sum_r coef[r] * up[n][r] * down[r][k],   n < N, k < KK, r < R, everything fp32,
+ * on v_mfma_f32_16x16x4_f32: c = coef[r] * up[n][r] is rounded once, the sum is an fp32 fma chain over r in ascending order starting
+ * from 0, and base is added once at the end.  No atomics; every element of dst is written exactly once, by the lane that read the
+ * same element of base, so base == dst (in place) is allowed and two launches on the same inputs give the same bits.  No other
+ * overlap between a job's dst and any operand of the launch is allowed.
+ * KK is the physical row of a master: Cin of a Linear / 1x1 conv, 9 Cin of a 3x3 conv in the [Cout][3][3][Cin] layout (the caller
+ * permutes `down` to that order).  coef[r] carries scale * alpha / rank of the adapter that column r belongs to; adapters on one
+ * layer are concatenated along R.
+ * jobs: DEVICE array, jobs_host: a HOST copy of the same njobs records (read only during the call).  Only the host copy can be
+ * validated before the launch and only the device copy is read by the kernel: the CALLER guarantees that the two are byte-identical
+ * and that the device copy is not modified before the launch has run.  A device copy that differs is an unvalidated launch.
+ *   struct sidlsg_lora_job { const float* base; float* dst; const float* up; const float* down; const float* coef;
+ *                            int N, KK, R, blk0; };                                             (56 bytes, no padding)
+ * base, dst [N][KK]; up [N][R]; down [R][KK]; coef [R].  Sorted by blk0 = index of the job's first 64 x 64 output tile, gap-free
+ * from 0: job i covers ceil(N/64) * ceil(KK/64) tiles; nblocks = their total.
+ * Admitted: all five pointers 16-byte aligned; N >= 1; KK % 4 == 0; R % 4 == 0, 4 <= R <= 4096 (pad with zero-coef columns);
+ * N * KK * 4 < 2^31 per job.  Anything else, a blk0 out of sequence or an nblocks that is not the total: SIDLSG_EINVAL, nothing
+ * is launched.  Edges of N and KK are predicated, nothing around a job's ranges is read or written. */
+int sidlsg_lora_merge_f32(const void* jobs_host, const void* jobs, int njobs, int nblocks, void* stream);
+
 /* ---- precision / recall (metrics/sid_precision_recall.py): fp16 feature distances on the MFMA, reduced in registers ----------
  * Feature matrices are [n][F] fp16 row-major, F a positive multiple of 32 (pad with zero columns on the host), 16-byte aligned.
  * In all three, exactly:  d2(i, j) = max(|a_i|^2 + |b_j|^2 - 2 a_i . b_j, 0)  with a . b on v_mfma_f32_16x16x32_f16 (fp32

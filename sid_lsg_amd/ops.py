@@ -2042,6 +2042,66 @@ def scale_cast_ranges(jobs, njobs, nblocks):
     lib.sidlsg_scale_cast_ranges(_p(jobs), njobs, nblocks, _s())
 
 
+LORA_JOB_DTYPE = [('base', '<u8'), ('dst', '<u8'), ('up', '<u8'), ('down', '<u8'), ('coef', '<u8'),
+                  ('N', '<i4'), ('KK', '<i4'), ('R', '<i4'), ('blk0', '<i4')]
+LORA_TILE = 64
+LORA_MAX_RANK = 4096
+
+
+class LoraJobTable:
+    """The job table of sidlsg_lora_merge_f32 (include/sidlsg_hip.h): `records` is a sequence of (base, dst, up, down, coef, N, KK, R)
+    with the five operands as device pointers; blk0 is filled in here (64 x 64 tiles, in order, gap-free).  Holds the host copy the
+    entry point validates and the device copy the kernel reads."""
+
+    def __init__(self, records, device):
+        import numpy as np
+        rec = np.zeros(len(records), dtype=np.dtype(LORA_JOB_DTYPE))
+        blk = 0
+        for i, (base, dst, up, down, coef, n, kk, r) in enumerate(records):
+            rec[i] = (base, dst, up, down, coef, n, kk, r, blk)
+            blk += -(-n // LORA_TILE) * -(-kk // LORA_TILE)
+        self.host = rec
+        self.njobs, self.nblocks = len(records), blk
+        self.device = torch.from_numpy(rec.view(np.uint8).copy()).to(device) if len(records) else None
+
+
+def lora_merge(table, names=None):
+    """One launch: dst = base + (coef * up) @ down for every job of `table` (LoraJobTable).  A record outside the admitted shapes
+    raises a ValueError that names the layer (`names`: one per job), before anything is launched."""
+    if table.njobs == 0:
+        return
+    fault = lora_job_fault(table.host, table.nblocks, names)
+    if fault is not None:
+        raise ValueError('LoRA merge job table: ' + fault)
+    lib.sidlsg_lora_merge_f32(table.host.ctypes.data, _p(table.device), table.njobs, table.nblocks, _s())
+
+
+def lora_job_fault(rec, nblocks, names=None):
+    """The Python side's ONE check of a LoRA job table against the contract of sidlsg_lora_merge_f32 (include/sidlsg_hip.h), run before
+    every launch: None when the table is admitted, else which record breaks which rule, in words.  The entry point checks again and
+    answers SIDLSG_EINVAL; a table that passes here and fails there is a disagreement between the two and surfaces as the binding's
+    RuntimeError with the code."""
+    blk = 0
+    for i, r in enumerate(rec):
+        who = names[i] if names else f'job {i}'
+        n, kk, rr = int(r['N']), int(r['KK']), int(r['R'])
+        for f in ('base', 'dst', 'up', 'down', 'coef'):
+            if int(r[f]) == 0 or int(r[f]) % 16:
+                return f'{who}: {f} pointer {int(r[f]):#x} is null or not 16-byte aligned'
+        if n < 1 or kk < 4 or kk % 4:
+            return f'{who}: weight [{n}][{kk}]: needs N >= 1 and a row length that is a multiple of 4'
+        if rr < 4 or rr % 4 or rr > LORA_MAX_RANK:
+            return f'{who}: concatenated rank {rr}: needs a multiple of 4 in [4, {LORA_MAX_RANK}]'
+        if n * kk * 4 >= 1 << 31:
+            return f'{who}: weight [{n}][{kk}] is 2^31 bytes or more'
+        if int(r['blk0']) != blk:
+            return f'{who}: blk0 {int(r["blk0"])} out of sequence (expected {blk})'
+        blk += -(-n // LORA_TILE) * -(-kk // LORA_TILE)
+    if blk != nblocks:
+        return f'nblocks {nblocks} is not the total {blk}'
+    return None
+
+
 def cast_bf16(src_f32, out=None):
     if out is None:
         out = torch.empty(src_f32.shape, device=src_f32.device, dtype=BF16)

@@ -293,6 +293,34 @@ def load_ip_adapter(spec, unet, device, embed_dim, seed=0):
     return ipa.load_ip_adapter(spec, net, torch.device(device), embed_dim, seed=seed)
 
 
+def lora_scales(nfiles, scales):
+    """The --lora_scale rule of both command lines: no value -> 1 for every file, one value -> that for every file, else one per file."""
+    scales = [float(s) for s in (scales or ())]
+    if nfiles == 0:
+        if scales:
+            raise ValueError('--lora_scale applies to --lora only')
+        return []
+    if len(scales) not in (0, 1, nfiles):
+        raise ValueError(f'{len(scales)} --lora_scale values for {nfiles} --lora files: give none, one, or one per file')
+    return [1.0] * nfiles if not scales else scales * nfiles if len(scales) == 1 else scales
+
+
+def load_lora(specs, scales, unet, text_encoder=None, seed=0, log=print):
+    """LoRA files ATTACHED to `unet` and `text_encoder` (lora.LoraSet; one merge launch per network, then the refresh): each spec is a
+    local kohya / diffusers `.safetensors` / `.bin` / `.pt` file or 'random:lora[:rank[:seed]]'; `scales` one per spec.  Prints one line
+    per file through `log` and returns the LoraSet (`set_scales`, `detach`)."""
+    from . import lora
+    net = _unwrap(unet)
+    _require_hip(net)
+    adapters, notes = lora.load_adapters(specs, net, text_encoder, seed=seed)
+    for note in notes:
+        log(note)
+    ls = lora.LoraSet(net, text_encoder).attach(adapters, scales)
+    for spec, s, (nu, nt, r0, r1) in zip(specs, scales, lora.summary(adapters)):
+        log(f'LoRA "{spec}": {nu} UNet + {nt} text-encoder layers, rank {r0 if r0 == r1 else f"{r0}-{r1}"}, scale {float(s):g}')
+    return ls
+
+
 def encode_contexts(contexts, text_encoder, tokenizer, device):
     """list[str] -> [B, L, D] text states (no grad); a tensor is passed through (pre-computed states)."""
     if torch.is_tensor(contexts):

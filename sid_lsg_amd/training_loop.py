@@ -131,6 +131,30 @@ def _hps_opt(metric_hps_path, hps_prompts, hps_arch, hps_tokenizer, sd_model, me
                 hps_tokenizer=hps_tokenizer if hps_tokenizer is not None else os.path.join(str(sd_model), 'tokenizer'), **cmmd)
 
 
+def _fuse_lora(lora, unet, text_encoder, text_encoder_only=False):
+    """`lora` = dict(specs=[...], scales=[...]) (sid_train.py --lora / --lora_scale) fused permanently into the loaded UNet and text
+    encoder (lora.fuse: one in-place merge launch per network); None or no specs: nothing happens.  text_encoder_only=True (the
+    evaluation of a snapshot, which brings its own UNet weights): the files are parsed against both networks as ever, but only their
+    text-encoder layers are fused and `unet` is left as it is."""
+    if not lora or not lora.get('specs'):
+        return
+    from . import lora as lora_mod
+    from .sd_util import lora_scales
+    specs = list(lora['specs'])
+    scales = lora_scales(len(specs), lora.get('scales'))
+    adapters, notes = lora_mod.load_adapters(specs, unet, text_encoder)
+    for note in notes:
+        dist.print0(note)
+    if text_encoder_only:
+        adapters = [[e for e in entries if e[0][0] == 'te'] for entries in adapters]
+        if not any(adapters):
+            dist.print0('LoRA: no text-encoder layers in the files; the snapshot is evaluated as it is')
+            return
+    lora_mod.fuse(unet, text_encoder, adapters, scales)
+    for spec, sc, (nu, nt, r0, r1) in zip(specs, scales, lora_mod.summary(adapters)):
+        dist.print0(f'LoRA "{spec}" fused: {nu} UNet + {nt} text-encoder layers, rank {r0 if r0 == r1 else f"{r0}-{r1}"}, scale {sc:g}')
+
+
 def training_loop(
     run_dir='.', dataset_kwargs={}, data_loader_kwargs={}, network_kwargs={}, loss_kwargs={},
     fake_score_optimizer_kwargs={}, g_optimizer_kwargs={}, augment_kwargs=None, seed=0, batch_size=512, batch_gpu=None,
@@ -143,7 +167,7 @@ def training_loop(
     network_pkl=None, enable_xformers=True, gradient_checkpointing=False, resolution=512, on_iteration=None,
     rng_device=None, metric_real_stats=None, metric_num_test=None, deterministic=False, snapshot_images=False,
     teacher_steps=None, teacher_cfg=None, text_encoder=None, metric_hps_path=None, hps_prompts=None, hps_arch=None, hps_tokenizer=None,
-    teacher_sampler=None, teacher_spacing=None, teacher_eta=None, teacher_rescale=None, metric_cmmd_clip_path=None,
+    teacher_sampler=None, teacher_spacing=None, teacher_eta=None, teacher_rescale=None, metric_cmmd_clip_path=None, lora=None,
 ):
     hps_kwargs = _hps_opt(metric_hps_path, hps_prompts, hps_arch, hps_tokenizer, pretrained_model_name_or_path, metric_cmmd_clip_path)
     if not train_mode and network_pkl == TEACHER:
@@ -155,14 +179,14 @@ def training_loop(
                                 metric_num_test=metric_num_test, dataset_prompt_text_kwargs=dataset_prompt_text_kwargs,
                                 snapshot_images=snapshot_images, batch_size=batch_size, batch_gpu=batch_gpu, text_encoder=text_encoder,
                                 teacher_sampler=teacher_sampler, teacher_spacing=teacher_spacing, teacher_eta=teacher_eta,
-                                teacher_rescale=teacher_rescale, **hps_kwargs)
+                                teacher_rescale=teacher_rescale, lora=lora, **hps_kwargs)
     if not train_mode:
         return evaluate_network(run_dir=run_dir, dataset_kwargs=dataset_kwargs, network_kwargs=network_kwargs, device=device, metrics=metrics,
                                 init_timestep=init_timestep, metric_pt_path=metric_pt_path, metric_open_clip_path=metric_open_clip_path, metric_clip_path=metric_clip_path,
                                 pretrained_model_name_or_path=pretrained_model_name_or_path, network_pkl=network_pkl, resolution=resolution,
                                 num_steps=num_steps, metric_real_stats=metric_real_stats, metric_num_test=metric_num_test,
                                 dataset_prompt_text_kwargs=dataset_prompt_text_kwargs, snapshot_images=snapshot_images,
-                                batch_size=batch_size, batch_gpu=batch_gpu, text_encoder=text_encoder, **hps_kwargs)
+                                batch_size=batch_size, batch_gpu=batch_gpu, text_encoder=text_encoder, lora=lora, **hps_kwargs)
     num_steps = int(num_steps)
     if num_steps < 1:
         raise ValueError(f'num_steps={num_steps}: expected >= 1')
@@ -189,6 +213,9 @@ def training_loop(
         weight_dtype=dtype, enable_xformers=enable_xformers, lora_config=None, compute_dtype=dtype, **_text_encoder_opt(text_encoder))
     if world > 1 and rank == 0:
         torch.distributed.barrier()
+    # --lora: fused before the three deep copies below, so the teacher, the fake score and the generator all start from the adapted
+    # model (--transfer / --resume then overwrite G / the fake score as ever; the teacher stays the fused one)
+    _fuse_lora(lora, unet, text_encoder)
     dist.print0('Loading network completed')
     dist.print0(f'Noise scheduler: {noise_scheduler}; teacher parameterisation: {noise_scheduler.config.prediction_type}')
 
@@ -445,7 +472,8 @@ def _evaluation_grid(msrc, vae, resolution, batch_size, batch_gpu, run_dir, devi
 def evaluate_network(run_dir, dataset_kwargs, network_kwargs, device, metrics, init_timestep, metric_pt_path, metric_open_clip_path,
                      pretrained_model_name_or_path, network_pkl, resolution, num_steps=1, metric_real_stats=None, metric_num_test=None,
                      dataset_prompt_text_kwargs=None, snapshot_images=False, batch_size=512, batch_gpu=None, metric_clip_path=None,
-                     text_encoder=None, metric_hps_path=None, hps_prompts=None, hps_arch=None, hps_tokenizer=None, metric_cmmd_clip_path=None):
+                     text_encoder=None, metric_hps_path=None, hps_prompts=None, hps_arch=None, hps_tokenizer=None, metric_cmmd_clip_path=None,
+                     lora=None):
     """`--train_mode 0` (sid_training_loop.py:680-745): load the text encoder / VAE / scheduler, un-pickle the distilled generator
     from `network_pkl` (`pickle.load(f)['ema']`, the file the training loop writes at the snapshot ticks) and evaluate every metric
     with 1, 2 and 4 generation steps; each result goes to `<dirname(run_dir)>/<metric><number>_<steps>.txt` in the reference's
@@ -462,9 +490,13 @@ def evaluate_network(run_dir, dataset_kwargs, network_kwargs, device, metrics, i
     if not network_pkl or not os.path.isfile(network_pkl):
         raise FileNotFoundError(f'--network_pkl {network_pkl!r}: a local network-snapshot-*.pkl is needed (there is no network to fetch one)')
     dtype = resolve_compute_dtype(dict(network_kwargs).get('compute_dtype'))
-    _, vae, noise_scheduler, text_encoder, tokenizer = load_sd15(
+    base_unet, vae, noise_scheduler, text_encoder, tokenizer = load_sd15(
         pretrained_model_name_or_path=pretrained_model_name_or_path, pretrained_vae_model_name_or_path=None, device=device,
         weight_dtype=dtype, lora_config=None, compute_dtype=dtype, **_text_encoder_opt(text_encoder))
+    # lora (the --lora of the run that wrote the snapshot): the snapshot brings its own UNet weights, so only the files' text-encoder
+    # layers are fused -- the generator was trained on the adapted text encoder's states
+    _fuse_lora(lora, base_unet, text_encoder, text_encoder_only=True)
+    del base_unet
     dist.print0('Loading network completed')
     dist.print0(f'Loading network from "{network_pkl}"...')
     with open(network_pkl, 'rb') as f:
@@ -530,7 +562,7 @@ def evaluate_teacher(run_dir, dataset_kwargs, network_kwargs, device, metrics, i
                      pretrained_model_name_or_path, resolution, teacher_steps=TEACHER_STEPS, teacher_cfg=TEACHER_CFG, metric_real_stats=None,
                      metric_num_test=None, dataset_prompt_text_kwargs=None, snapshot_images=False, batch_size=512, batch_gpu=None,
                      metric_clip_path=None, text_encoder=None, metric_hps_path=None, hps_prompts=None, hps_arch=None, hps_tokenizer=None,
-                     teacher_sampler=None, teacher_spacing=None, teacher_eta=None, teacher_rescale=None, metric_cmmd_clip_path=None):
+                     teacher_sampler=None, teacher_spacing=None, teacher_eta=None, teacher_rescale=None, metric_cmmd_clip_path=None, lora=None):
     """`--train_mode 0 --network_pkl teacher`: the teacher row of the tables under this project's own protocol.  The UNet of the model
     is sampled with classifier-free guidance `teacher_cfg` and a `teacher_steps`-step deterministic DDIM sampler
     (sd_util.teacher_sample) as the `G` of every metric -- the same prompts, seeds, VAE, detector resize and metric code as a
@@ -552,6 +584,7 @@ def evaluate_teacher(run_dir, dataset_kwargs, network_kwargs, device, metrics, i
         pretrained_model_name_or_path=pretrained_model_name_or_path, pretrained_vae_model_name_or_path=None, device=device,
         weight_dtype=dtype, lora_config=None, compute_dtype=dtype, **_text_encoder_opt(text_encoder))
     unet.eval().requires_grad_(False)
+    _fuse_lora(lora, unet, text_encoder)
     dist.print0('Loading network completed')
     tag = teacher_report_name(teacher_steps, teacher_cfg, teacher_sampler, teacher_spacing, teacher_eta, teacher_rescale)
     solver_kw = teacher_solver_kwargs(teacher_sampler, teacher_spacing, teacher_eta, teacher_rescale)

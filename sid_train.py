@@ -111,6 +111,8 @@ OPTIONS = [
     (('--optimizer',), dict(type=click.Choice(['adam', 'adamw']), default='adam', show_default=True, help='Optimizer')),
     (('--num_steps',), dict(type=click.IntRange(min=1), default=1, show_default=True, help='Number of generation steps of the trained generator')),
     (('--fake_score_use_lora',), dict(type=bool, default=False, show_default=True, help='Unsupported (must be False)')),
+    (('--lora',), dict(type=str, multiple=True, metavar='SPEC', help='LoRA file fused into the UNet and the text encoder of --sd_model before the teacher, the fake score and the generator are copied from it (repeatable): a local kohya / diffusers .safetensors / .bin / .pt file, or random:lora[:rank[:seed]] (not a reference option)')),
+    (('--lora_scale',), dict(type=float, multiple=True, help='Scale of --lora (repeatable: one for all files, or one per file; negative allowed)  [default: 1] (not a reference option)')),
 ]
 
 
@@ -224,6 +226,15 @@ def build_config(o):
             raise click.ClickException(f'--teacher_eta {c.teacher_eta:g}: --teacher_sampler dpmpp2m is deterministic (eta applies to ddim)')
         if c.get('teacher_sampler', 'ddim') == 'ddim' and c.get('teacher_spacing') == 'linspace':
             raise click.ClickException('--teacher_spacing linspace: not reproduced for --teacher_sampler ddim (use leading or trailing)')
+    if o.get('lora') or o.get('lora_scale'):      # (absent when not given: the printed options of every other run stay as they were)
+        from sid_lsg_amd.sd_util import lora_scales
+        try:
+            c.lora = EasyDict(specs=list(o.get('lora') or ()), scales=lora_scales(len(o.get('lora') or ()), o.get('lora_scale')))
+        except ValueError as e:
+            raise click.ClickException(str(e))
+        for spec in c.lora.specs:
+            if not str(spec).lower().startswith('random:') and not os.path.isfile(spec):
+                raise click.ClickException(f'--lora {spec}: not a local file (a .safetensors / .bin / .pt LoRA, or random:lora[:rank[:seed]])')
     if o.transfer is not None:
         c.resume_pkl = o.transfer
     if o.resume is not None:
