@@ -11,27 +11,26 @@
 //     16 k-slices x bf16x8 = 64 registers; a K + V tile in flight global -> registers -> LDS is another 64.  ~290 registers with the
 //     rest: one wave per SIMD (512-register file), so a block is 4 waves = 64 queries and __launch_bounds__(256, 1).
 //   - a 32-key tile of K and of V is 2 x 32 KB of bf16; rows are padded to 528 elements (an odd multiple of 32 bytes: conflict-free
-//     for the ds_read_b128 row reads and the transposed reads alike, see tile_ld() of attention.hip) -> 66 KB per stage, double
+//     for the ds_read_b128 row reads and the transposed reads alike, see tile_ld() of attn_frag.h) -> 66 KB per stage, double
 //     buffered = 132 KB of the CU's 160 KB.  With one wave per SIMD nothing else hides HBM / L2 latency, so the next tile's loads
 //     are issued before the current tile's MFMAs and committed to the other buffer after them: one barrier per key tile.
 //   - per tile and wave: 32 MFMAs for S^T (2 key sub-tiles x 16 k-slices), 32 for O^T (32 d-tiles); 32 ds_read_b128 + 64 transposed reads.
 // The O^T rescale (128 multiplies per lane) runs only on tiles where some query of the wave saw its running maximum grow (exactly: no
 // deferral threshold), which is the common case only in the first few tiles.
+// The row stride (tile_ld), the transposed read of V (tr_frag32) and pack_p are the shared ones of attn_frag.h.
 // N (queries = keys) is a multiple of 16; a trailing half tile of keys is masked to -inf, rows past N of the last block are idle waves.
-#include "common.h"
+#include "attn_frag.h"
 #include <math.h>
 
 namespace {
 
 constexpr int WD = 512;            // head width
-constexpr int WLD = 528;           // LDS row stride (elements)
+constexpr int WLD = tile_ld<WD>();  // LDS row stride (elements): 528
 constexpr int WKT = 32;            // keys per tile
 constexpr int WNS = WD / 32;       // k-slices of the QK^T contraction
 constexpr int WDT = WD / 16;       // output d-tiles
 constexpr int WTILE = WKT * WLD;   // elements of one staged tile
 constexpr int WPER = WKT * (WD / 8) / 256;   // 16-byte chunks per thread per tile (8)
-
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4_w;
 
 struct WideParams {
     const bf16 *Q, *K, *V;
@@ -41,16 +40,6 @@ struct WideParams {
     long long bsq, bsk, bsv, bso;
     float scale2;                  // D^-0.5 * log2(e)
 };
-
-DEVFN bf16x8 wide_tr_frag(const bf16* tile, int c0, int li, int lg) {       // as tr_frag32 of attention.hip, r0 = 0
-    const bf16* p0 = tile + (4 * lg + (li >> 2)) * WLD + c0 + (li & 3) * 4;
-    const bf16* p1 = p0 + 16 * WLD;
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_w*)p0);
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_w*)p1);
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
-    s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, v);
-}
 
 __global__ __launch_bounds__(256, 1) void attn_wide_kernel(WideParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem_w[];
@@ -140,9 +129,9 @@ __global__ __launch_bounds__(256, 1) void attn_wide_kernel(WideParams p) {
                 ps += s0[r] + s1[r];
             }
             l += ps;
-            const bf16x8 pf = {f2bf(s0[0]), f2bf(s0[1]), f2bf(s0[2]), f2bf(s0[3]), f2bf(s1[0]), f2bf(s1[1]), f2bf(s1[2]), f2bf(s1[3])};
+            const bf16x8 pf = pack_p(s0, s1);
 #pragma unroll
-            for (int i = 0; i < WDT; i++) acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wide_tr_frag(vt, i * 16, li, lg), pf, acc[i], 0, 0, 0);
+            for (int i = 0; i < WDT; i++) acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tr_frag32(vt, WLD, 0, i * 16, li, lg), pf, acc[i], 0, 0, 0);
         }
         if (t + 1 < ntiles) store_tile(buf ^ 1);     // that buffer was last read in iteration t - 1, before its closing barrier
         __syncthreads();
@@ -178,12 +167,7 @@ int sidlsg_attn_fwd_wide(const void* Q, const void* K, const void* V, void* O, i
     p.N = N; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo; p.bsq = bsq; p.bsk = bsk; p.bsv = bsv; p.bso = bso;
     p.scale2 = (float)(1.4426950408889634 / sqrt((double)D));
     const size_t lds = (size_t)4 * WTILE * sizeof(bf16);
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_wide_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return (int)hipGetLastError();
-        attr_done = true;
-    }
+    if (const int e = sidlsg_lds_limit<&attn_wide_kernel>(lds)) return e;
     SidlsgTraceScope ts(SIDLSG_FAM_ATTN_FWD, 4.0 * B * (double)N * N * D, 8.0 * B * (double)N * D);
     SIDLSG_LAUNCH(attn_wide_kernel, dim3((unsigned)((N + 63) / 64), (unsigned)B), dim3(256), lds, (hipStream_t)stream, p);
     return sidlsg_last_error();

@@ -27,7 +27,7 @@ EXTRA = {'attention.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form', '-fno-honor-nans'
 
 def digest():
     h = hashlib.md5()
-    for f in SOURCES + ['common.h', 'gemm_p8.h', 'bias_act_kernel.h']:
+    for f in SOURCES + sorted(f for f in os.listdir(HERE) if f.endswith('.h')):      # every header: a new one cannot leave a stale library
         with open(os.path.join(HERE, f), 'rb') as fh:
             h.update(fh.read())
     with open(os.path.join(os.path.dirname(PKG), 'include', 'sidlsg_hip.h'), 'rb') as fh:      # gemm.hip includes the C ABI header

@@ -226,6 +226,20 @@ struct SidlsgTraceScope {
 // Launch-error helper for the extern "C" entry points: returns the HIP error code (0 = ok).
 static inline int sidlsg_last_error() { return (int)hipGetLastError(); }
 
+// Raises KERNEL's dynamic-LDS limit to `bytes` -- the most that kernel can ask for -- on its first launch.  0, or the HIP error.
+template <auto KERNEL>
+int sidlsg_lds_limit(size_t bytes) {
+    static bool done = false;                        // per kernel instantiation
+    if (!done) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
+            const int e = (int)hipGetLastError();
+            return e ? e : (int)hipErrorUnknown;
+        }
+        done = true;
+    }
+    return 0;
+}
+
 // Deterministic mode (sidlsg_set_deterministic, defined in gemm.hip): every parameter-gradient reduction takes an order-fixed form,
 // so its bits depend only on the inputs and the launch configuration.  Off: the atomic forms of the fast path.
 bool sidlsg_det();

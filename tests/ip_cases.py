@@ -180,7 +180,7 @@ def _bf(t):
 
 
 def cross2_emulated(x, s, heads, ps=False):
-    """The algorithm of attn_cross2_bf16_kernel in fp32 on the CPU (module docstring) -> [B, Nq, C], rounded to bf16."""
+    """The algorithm of attn_cross2_kernel<bf16> in fp32 on the CPU (module docstring) -> [B, Nq, C], rounded to bf16."""
     H = heads
     qh, kh, vh, k2h, v2h = (_heads(x[n].float(), H) for n in ('q', 'k', 'v', 'k2', 'v2'))
     B, _, Nq, D = qh.shape

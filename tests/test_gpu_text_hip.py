@@ -48,7 +48,11 @@ def dev():
 
 
 # ---- causal attention ------------------------------------------------------------------------------------------------------------
-ATTN_SHAPES = [(2, 2, 77, 64), (1, 3, 77, 32), (2, 1, 1, 64), (1, 2, 16, 64), (1, 2, 17, 64), (1, 1, 128, 64)]
+# The last three reach the padded widths, whose staging the causal kernels share with the two-set kernels (csrc/attn_short.h):
+# (33, 40) D < DP in both dtypes, three waves, a ragged diagonal sub-tile; (17, 104) bf16 DP = 128 with 24 pad columns, fp32 DP = 112;
+# (128, 128) the largest LDS image (72 KB bf16, 132 KB fp32), which launches only once the dynamic-LDS limit has been raised.
+ATTN_SHAPES = [(2, 2, 77, 64), (1, 3, 77, 32), (2, 1, 1, 64), (1, 2, 16, 64), (1, 2, 17, 64), (1, 1, 128, 64),
+               (1, 2, 33, 40), (1, 1, 17, 104), (1, 1, 128, 128)]
 
 
 def _qkv(B, H, N, D, dtype):
