@@ -385,7 +385,8 @@ int sidlsg_masked_renoise(const float* x, const float* z0, const float* noise, c
 
 /* ---- losses with closed-form gradients (sid_training_loop.py:423-445, 508-530) -------------
  * Per-sample NaN filtering is done in-kernel (a sample containing NaN contributes 0 and gets zero
- * gradients), `scale` = loss_scaling / batch_gpu_total.  ws >= 2*S + 8*S floats.  loss: 1 float. */
+ * gradients), `scale` = loss_scaling / batch_gpu_total.  ws >= 2*S + 8*S floats.  loss: 1 float.
+ * S <= 0 or n <= 0: SIDLSG_EINVAL. */
 int sidlsg_g_loss(const float* x, const float* yr, const float* yf, float* dx, float* dyr, float* dyf, float* loss, float* ws,
                   int S, int n, float alpha, float scale, void* stream);
 int sidlsg_fake_loss(const float* e, const float* noise, float* de, float* loss, float* ws, int S, int n, float scale,
@@ -399,8 +400,9 @@ int sidlsg_fake_loss_v(const float* o, const float* x0, const float* noise, cons
                        float* de, float* loss, float* ws, int S, int n, float scale, void* stream);
 
 /* ---- optimizer: nan_to_num + clip + Adam/AdamW + EMA + bf16 weight copy + zero_grad --------
- * (sid_training_loop.py:458-462, 541-565; sid_train.py:219-226).  hyper: 11 floats in DEVICE memory:
- * lr, beta1, beta2, eps, bias_corr1, sqrt(bias_corr2), ema_beta, weight_decay, decoupled, clip, grad_scale.
+ * (sid_training_loop.py:458-462, 541-565; sid_train.py:219-226).  hyper: 13 floats in DEVICE memory:
+ * lr, beta1, beta2, eps, bias_corr1, sqrt(bias_corr2), ema_beta, weight_decay, decoupled, clip, grad_scale, 1 - beta1, 1 - beta2
+ * (the last two rounded from double, as torch forms the weights of lerp_ and addcmul_).
  * m may be NULL when beta1 == 0; ema, w_bf16 may be NULL. */
 int sidlsg_adam_ema(float* p, float* g, float* m, float* v, float* ema, void* w_bf16, const float* hyper, long long n,
                     int zero_grad, void* stream);

@@ -657,7 +657,7 @@ static int noisy_input_t(const float* x0, const float* noise, const float* s0, c
 template <typename T>
 static int noisy_input_bwd_t(const void* g, const float* s0, float* dx0, int B, int C, int HW, int Cp, int dup, int accumulate,
                              void* stream) {
-    if (C > 8 || Cp % 8) return SIDLSG_EINVAL;
+    if (C > 8 || Cp % 8 || Cp < 8) return SIDLSG_EINVAL;
     hipLaunchKernelGGL(noisy_input_bwd_kernel<T>, GRID1D((size_t)B * HW, 256), dim3(256), 0, (hipStream_t)stream, (const T*)g,
                        s0, dx0, B, C, HW, Cp, dup, accumulate);
     return sidlsg_last_error();
@@ -665,7 +665,7 @@ static int noisy_input_bwd_t(const void* g, const float* s0, float* dx0, int B, 
 template <typename T>
 static int cfg_x0_bwd_t(const float* g, const float* s0, const float* s1, void* deps, float* dxt, int B, int C, int HW, int Cp,
                         int dup, float kappa, int mode, void* stream) {
-    if (C > 8 || Cp % 8 || mode < 0 || mode > 2) return SIDLSG_EINVAL;
+    if (C > 8 || Cp % 8 || Cp < 8 || mode < 0 || mode > 2) return SIDLSG_EINVAL;
     const dim3 grid = GRID1D((size_t)B * HW, 256);
     hipStream_t s = (hipStream_t)stream;
     if (mode == 0) hipLaunchKernelGGL((cfg_x0_bwd_kernel<T, 0>), grid, dim3(256), 0, s, g, s0, s1, (T*)deps, dxt, B, C, HW, Cp, dup, kappa);
@@ -937,6 +937,7 @@ SIDLSG_BOTH(sidlsg_transpose_w_batched, transpose_w_batched_t, (const void* jobs
 #define SID_GB 8
 int sidlsg_g_loss(const float* x, const float* yr, const float* yf, float* dx, float* dyr, float* dyf, float* loss, float* ws,
                   int S, int n, float alpha, float scale, void* stream) {
+    if (S <= 0 || n <= 0) return SIDLSG_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     float* st = ws; float* part = ws + 2 * S;
     hipLaunchKernelGGL(sid_sample_stats_kernel, dim3(S), dim3(256), 0, s, x, yr, yf, st, n);
@@ -946,6 +947,7 @@ int sidlsg_g_loss(const float* x, const float* yr, const float* yf, float* dx, f
 }
 int sidlsg_fake_loss(const float* e, const float* noise, float* de, float* loss, float* ws, int S, int n, float scale,
                      void* stream) {
+    if (S <= 0 || n <= 0) return SIDLSG_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     float* st = ws; float* part = ws + 2 * S;
     hipLaunchKernelGGL(sid_sample_stats_kernel, dim3(S), dim3(256), 0, s, e, (const float*)nullptr, (const float*)nullptr, st, n);

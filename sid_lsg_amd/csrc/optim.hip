@@ -13,12 +13,15 @@
 
 // hyper: [0]=lr [1]=beta1 [2]=beta2 [3]=eps [4]=bias_corr1 [5]=sqrt(bias_corr2) [6]=ema_beta [7]=weight_decay
 //        [8]=decoupled(0/1) [9]=clip (<=0: off) [10]=grad_scale (e.g. 1/world for a summed all-reduce)
+//        [11]=1-beta1 [12]=1-beta2: rounded from the host's double like torch's lerp weight and addcmul value (1.f - 0.999f is
+//        1.3e-5 off 0.001f, and exp_avg_sq with it)
 __global__ __launch_bounds__(256) void adam_ema_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                        float* __restrict__ v, float* __restrict__ ema, bf16* __restrict__ w,
                                                        const float* __restrict__ hyper, size_t n, int zero_grad) {
-    const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], bc1 = hyper[4], bc2 = hyper[5];
+    const float lr = hyper[0], b2 = hyper[2], eps = hyper[3], bc1 = hyper[4], bc2 = hyper[5];
     const float eb = hyper[6], wd = hyper[7], clip = hyper[9], gs = hyper[10];
     const bool decoupled = hyper[8] != 0.f;
+    const float omb1 = hyper[11], omb2 = hyper[12];
     const float step = lr / bc1;  // hyper[5] holds sqrt(bias_corr2), as torch computes it on the host
     const size_t stride = (size_t)gridDim.x * blockDim.x * 4;
     for (size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += stride) {
@@ -36,8 +39,8 @@ __global__ __launch_bounds__(256) void adam_ema_kernel(float* __restrict__ p, fl
                 float pp = pv[e];
                 if (wd != 0.f) { if (decoupled) pp *= (1.f - lr * wd); else gg += wd * pp; }
                 float mm = gg;
-                if (m) { mm = mv[e] + (gg - mv[e]) * (1.f - b1); mv[e] = mm; }
-                const float v2 = b2 * vv[e] + (1.f - b2) * gg * gg;
+                if (m) { mm = mv[e] + (gg - mv[e]) * omb1; mv[e] = mm; }
+                const float v2 = b2 * vv[e] + omb2 * gg * gg;
                 vv[e] = v2;
                 pp -= step * mm / (sqrtf(v2) / bc2 + eps);
                 pv[e] = pp;
@@ -58,8 +61,8 @@ __global__ __launch_bounds__(256) void adam_ema_kernel(float* __restrict__ p, fl
                 float pp = p[j];
                 if (wd != 0.f) { if (decoupled) pp *= (1.f - lr * wd); else gg += wd * pp; }
                 float mm = gg;
-                if (m) { mm = m[j] + (gg - m[j]) * (1.f - b1); m[j] = mm; }
-                const float v2 = b2 * v[j] + (1.f - b2) * gg * gg;
+                if (m) { mm = m[j] + (gg - m[j]) * omb1; m[j] = mm; }
+                const float v2 = b2 * v[j] + omb2 * gg * gg;
                 v[j] = v2;
                 pp -= step * mm / (sqrtf(v2) / bc2 + eps);
                 p[j] = pp;

@@ -116,7 +116,8 @@ class FusedAdamEMA:
         b1, b2 = self.betas
         t = self.step_count
         h = [self.lr, b1, b2, self.eps, 1 - b1 ** t, math.sqrt(1 - b2 ** t), float(ema_beta), self.weight_decay,
-             1.0 if self.decoupled else 0.0, float(self.clip_value) if self.clip_value else 0.0, self.grad_scale]
+             1.0 if self.decoupled else 0.0, float(self.clip_value) if self.clip_value else 0.0, self.grad_scale,
+             1 - b1, 1 - b2]          # the weights of torch's lerp_ / addcmul_: formed in double, rounded once
         k = self._hyper_slot = (self._hyper_slot + 1) % len(self._hyper_host)
         if self._hyper_evt[k] is not None:
             self._hyper_evt[k].synchronize()          # the copy that last read this slot (4 optimizer steps ago) has completed
