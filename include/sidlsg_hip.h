@@ -116,7 +116,7 @@ int sidlsg_conv3x3_wgrad_bf16(const void* dY, int ldy, const void* X, int ldx, f
                               int Cin, int Cout, int stride, int ups, void* stream);
 
 /* ---- dispatch record (host diagnostic; tests/gemm_cases.py) ----------------------------------
- * Which kernel a GEMM / conv / weight-gradient entry point chose.  Every host launcher of csrc/gemm.hip and csrc/gemm_p8.h writes a
+ * Which kernel a GEMM / conv / weight-gradient entry point chose.  Every host launcher of csrc/gemm.hip, gemm_fp8.hip, wgrad.hip and gemm_p8.h writes a
  * thread-local record of SIDLSG_REC_INTS ints just before it launches: a handful of plain stores, no HIP call, nothing about the
  * launch changes.  The record is written BEFORE the launch, so it is there also when the launch itself fails (no device).
  * sidlsg_debug_last_launch copies the record of the calling thread's last such call: out[SIDLSG_REC_*], at most n ints; returns

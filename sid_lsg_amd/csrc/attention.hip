@@ -58,8 +58,7 @@ DEVFN void attn_block_coords(const AttnParams& p, int& bx, int& h, int& b) {
     if (!p.xcd) return;
     const unsigned nx = gridDim.x, ny = gridDim.y, total = nx * ny * gridDim.z;
     unsigned L = blockIdx.x + nx * (blockIdx.y + ny * blockIdx.z);
-    const unsigned q = total >> 3, r = total & 7, xcd = L & 7, idx = L >> 3;
-    L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    L = xcd_contiguous(L, total);
     bx = (int)(L % nx);
     const unsigned t = L / nx;
     h = (int)(t % ny); b = (int)(t / ny);
@@ -1061,7 +1060,7 @@ static int launch_attn(const AttnParams& p, int mode, hipStream_t s) {
 // backward 1134 -> 436 MB (4.9x -> 1.9x).
 // SIDLSG_ATTN_XCD: bit mask of the passes that may renumber (1 forward, 2 dQ, 4 dK/dV; 8: also the long backward passes); default 15.
 static int attn_xcd_on(int mode, const AttnParams& p) {
-    static const int mask = getenv("SIDLSG_ATTN_XCD") ? atoi(getenv("SIDLSG_ATTN_XCD")) : 15;
+    static const int mask = sidlsg_env_int("SIDLSG_ATTN_XCD", 15);
     if (!((mask >> mode) & 1)) return 0;
     return mode == 0 || (mask & 8) || (p.Nq <= 1024 && p.Nk <= 1024);
 }
@@ -1070,7 +1069,7 @@ static int attn_xcd_on(int mode, const AttnParams& p) {
 // algorithmic bytes -- profiles/r05_traffic_attn*.json -- and bytes are what the step is short of);
 // only together with the XCD-contiguous numbering (without it an XCD holds 4 blocks of each of 16 heads: nothing walks in lockstep)
 static int attn_rot_on(int mode, const AttnParams& p) {
-    static const int mask = getenv("SIDLSG_ATTN_ROT") ? atoi(getenv("SIDLSG_ATTN_ROT")) : 6;
+    static const int mask = sidlsg_env_int("SIDLSG_ATTN_ROT", 6);
     return p.xcd && ((mask >> mode) & 1);
 }
 template <bool PS>
@@ -1084,7 +1083,7 @@ static int dispatch_attn(const AttnParams& p_in, int mode, hipStream_t s) {
     // wave at one wave per SIMD measured up to 3x slower at d=40 (the softmax VALU work only overlaps MFMA across waves).
     // dK/dV with 32 keys per wave halves the LDS fragment traffic per MFMA: measured (N=4096, B=16) 3075 -> 2661 us for
     // the whole d=40 backward, neutral at d=64 -> only DP=48 uses it (SIDLSG_ATTN_KT2=0 switches it off for A/B runs).
-    static const bool allow_kt2 = !(getenv("SIDLSG_ATTN_KT2") && atoi(getenv("SIDLSG_ATTN_KT2")) == 0);
+    static const bool allow_kt2 = sidlsg_env_on("SIDLSG_ATTN_KT2");
     const bool kt2 = allow_kt2 && mode == 2 && p.Nk >= 1024;
     switch (dp) {
         case 16: return launch_attn<16, 2, 1, PS>(p, mode, s);
@@ -1125,8 +1124,7 @@ constexpr int AF_MIN_N = 4096;
 static int g_attn_fused_mode = -1;      // -1: not read yet
 static int attn_fused_mode() {
     if (g_attn_fused_mode < 0) {
-        const char* e = getenv("SIDLSG_ATTN_BWD_FUSED");
-        const int v = e ? atoi(e) : AF_DEFAULT_MODE;
+        const int v = sidlsg_env_int("SIDLSG_ATTN_BWD_FUSED", AF_DEFAULT_MODE);
         g_attn_fused_mode = v < 0 ? 0 : (v > 2 ? 2 : v);
     }
     return g_attn_fused_mode;
@@ -1148,13 +1146,8 @@ static int attn_bwd_fused(bool ps, const AttnParams& p_in, float* ws, long long 
         SIDLSG_LAUNCH(attn_delta_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, p.O, p.dO, p.delta_out, B, p.H, p.Nq, p.D, p.ldo, p.bso);
     }
     constexpr int lds = attn_fused_lds_bytes<48>();
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_fused_kernel<48, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_fused_kernel<48, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-            return SIDLSG_EINVAL;
-        attr_done = true;
-    }
+    if (const int e = sidlsg_lds_limit<&attn_bwd_fused_kernel<48, false>>(lds)) return e;
+    if (const int e = sidlsg_lds_limit<&attn_bwd_fused_kernel<48, true>>(lds)) return e;
     const long long per_b = (long long)p.H * p.G * p.Nq * p.D * 4;
     int bc = (int)(ws_bytes / per_b < B ? ws_bytes / per_b : B);       // >= 1 (attn_fused_rule)
     // One workgroup per CU is resident and all of them run equally long, so a chunk whose workgroups do not fill the CUs a whole number

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 typedef __bf16 bf16;
 typedef bf16 bf16x2 __attribute__((ext_vector_type(2)));
@@ -72,6 +73,15 @@ DEVFN float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
+}
+
+// XCD-contiguous block numbering.  Hardware block b runs on XCD b % 8; the renumbering gives every XCD a contiguous range of the
+// nblk logical blocks, so blocks that share an operand panel (a GEMM's A row-panel, an attention head's K / V, a GroupNorm sample)
+// sit on one XCD and meet in its L2.  I: int, or unsigned where the caller's ids are.
+template <typename I>
+DEVFN I xcd_contiguous(I bid, I nblk) {
+    const I q = nblk >> 3, r = nblk & 7, xcd = bid & 7, idx = bid >> 3;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
 
 // 16-byte global load/store of 8 bf16
@@ -240,7 +250,16 @@ int sidlsg_lds_limit(size_t bytes) {
     return 0;
 }
 
-// Deterministic mode (sidlsg_set_deterministic, defined in gemm.hip): every parameter-gradient reduction takes an order-fixed form,
+// Environment switches of the host launchers (read once: every site keeps its `static const`).  A number: the variable's atoi, `dflt`
+// when unset.  An on-by-default switch: off only when the variable is set and its atoi is 0; an off-by-default one: env_int(name, 0) != 0.
+static inline int sidlsg_env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+static inline bool sidlsg_env_on(const char* name) { return sidlsg_env_int(name, 1) != 0; }
+
+// ---- library state (state.hip)
+// Deterministic mode (sidlsg_set_deterministic): every parameter-gradient reduction takes an order-fixed form,
 // so its bits depend only on the inputs and the launch configuration.  Off: the atomic forms of the fast path.
 bool sidlsg_det();
 // The split-K / pixel-split scratch of stream `s` (sidlsg_set_stream_workspace, else sidlsg_set_workspace); null / 0 when none.

@@ -1,6 +1,6 @@
 // ---------------------------------------------------------------------------------------------------------------------
 // "p8": bf16 GEMM / implicit-GEMM conv3x3 on 256-row output tiles, 512 threads = 8 waves in TWO STAGGERED GROUPS.
-// (included by gemm.hip behind gemm_v3_kernel: shares GemmParams, the loader conventions, the epilogue and the split-K slabs)
+// (included by gemm.hip behind gemm_v3_kernel: shares gemm_core.h's GemmParams, the loader conventions, the epilogue and the split-K slabs)
 //
 // Why another structure.  gemm_v3_kernel (128 x 160 tile, 4 waves, 2 blocks per CU) stages 230 bytes per MFMA through the
 // L2 -> LDS path and issues 0.45 ds_read_b128 per MFMA; tools/ubench measured that path at 55 % of its cap inside the loop and
@@ -353,12 +353,7 @@ DEVFN void gemm_p8_body(GemmParams& p) {
     const int nk_all = p.K / BK;
     const int nsplit = p.kt_per_split ? (nk_all + p.kt_per_split - 1) / p.kt_per_split : 1;
     const int ntile = tiles_n * tiles_m;
-    int bid = blockIdx.x;
-    {
-        const int nblk = ntile * nsplit;
-        const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = xcd_contiguous((int)blockIdx.x, ntile * nsplit);
     const int split = bid / ntile;
     int mt, nt;
     {
@@ -397,12 +392,9 @@ DEVFN void gemm_p8_body(GemmParams& p) {
             aoff[j] = ok ? ((unsigned)m * (unsigned)p.lda + kcs * 8) * 2u : OOB;
             tmask[j] = 0;
         } else {
-            const int mm = ok ? m : 0;
-            const int hw = p.Ho * p.Wo;
-            const int b = mm / hw, rem = mm - b * hw;
-            const int ho = rem / p.Wo, wo = rem - ho * p.Wo;
-            const int hi0 = ho * p.stride, wi0 = wo * p.stride;          // centre tap
-            aoff[j] = ((unsigned)(b * p.H * p.Wd) * (unsigned)p.lda + kcs * 8) * 2u + (unsigned)(hi0 * p.Wd + wi0) * tap_ps;
+            const ConvRow cr = conv_row(p, m);
+            const int hi0 = cr.ho * p.stride, wi0 = cr.wo * p.stride;          // centre tap
+            aoff[j] = ((unsigned)(cr.b * p.H * p.Wd) * (unsigned)p.lda + kcs * 8) * 2u + (unsigned)(hi0 * p.Wd + wi0) * tap_ps;
             unsigned mk = 0;
 #pragma unroll
             for (int tp = 0; tp < 9; tp++) {
@@ -605,7 +597,7 @@ __global__ __launch_bounds__(512, 1) void gemm_p8w_geglu_bwd_kernel(GemmParams p
 // The GEGLU fusions on the 256 x 320 configuration: admission (shapes, alignment, 31-bit descriptors) and the cost model of gemm.hip::p8_rule without
 // K splits (the epilogues finish their tile).  SIDLSG_P8_GEGLU=0: the v3 kernels as before (A/B switch).
 static bool p8_geglu_takes(const GemmParams& p) {
-    static const bool on = !(getenv("SIDLSG_P8_GEGLU") && atoi(getenv("SIDLSG_P8_GEGLU")) == 0);
+    static const bool on = sidlsg_env_on("SIDLSG_P8_GEGLU");
     const int F = p.geglu ? p.geglu : p.geglu_bwd;
     if (!on || !F || (p.geglu && p.geglu_bwd) || F % 160 || p.N % 320 || p.K % BK || p.kt_per_split || p.wscale || p.res || p.rowvec || p.flags) return false;
     if ((p.ldy & 7) || ((uintptr_t)p.Y & 15) || (p.lda & 7) || ((uintptr_t)p.A & 15)) return false;
@@ -624,15 +616,11 @@ template <int EPI>
 static int launch_gemm_p8_geglu(const GemmParams& p, hipStream_t s) {
     using G = P8<1>;
     const int tiles = m_tiles_rt(p, G::BM) * (p.N / G::BN);
-    static bool attr_done = false;
-    auto kern = EPI == 1 ? &gemm_p8w_geglu_kernel : &gemm_p8w_geglu_bwd_kernel;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-        attr_done = true;
-    }
+    constexpr auto kern = EPI == 1 ? &gemm_p8w_geglu_kernel : &gemm_p8w_geglu_bwd_kernel;
     GemmParams q = p;
     q.group_m = 4;
     record_launch(EPI == 1 ? SIDLSG_K_GEMM_P8W_GEGLU : SIDLSG_K_GEMM_P8W_GEGLU_BWD, G::BM, G::BN, 0, -1, 1, 1, SIDLSG_PART_ONE);
+    if (const int e = sidlsg_lds_limit<kern>(G::LDS_BYTES)) return e;
     SIDLSG_LAUNCH(kern, dim3(tiles), dim3(G::NTH), (size_t)G::LDS_BYTES, s, q);
     return sidlsg_last_error();
 }
@@ -661,17 +649,14 @@ template <int MODE, int CFG>
 static int launch_gemm_p8(const GemmParams& p, hipStream_t s) {
     using G = P8<CFG>;
     const int tiles = m_tiles_rt(p, G::BM) * (p.N / G::BN);
-    static bool attr_done = false;
-    auto kern = CFG ? &gemm_p8w_kernel<MODE> : &gemm_p8s_kernel<MODE>;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-        attr_done = true;
-    }
+    constexpr auto kern = CFG ? &gemm_p8w_kernel<MODE> : &gemm_p8s_kernel<MODE>;
     const int nk = p.K / BK;
     const int splits = p.kt_per_split ? (nk + p.kt_per_split - 1) / p.kt_per_split : 1;
     GemmParams q = p;
     q.group_m = 4;
     record_launch(CFG ? SIDLSG_K_GEMM_P8W : SIDLSG_K_GEMM_P8S, G::BM, G::BN, MODE, -1, CFG, splits, p.kt_per_split ? SIDLSG_PART_SLABS : SIDLSG_PART_ONE);
+    if (p.kt_per_split) record_followup(SIDLSG_FIN_GEMM);
+    if (const int e = sidlsg_lds_limit<kern>(G::LDS_BYTES)) return e;
     SIDLSG_LAUNCH(kern, dim3(tiles * splits), dim3(G::NTH), (size_t)G::LDS_BYTES, s, q);
     if (p.kt_per_split) launch_gemm_finish(p, splits, s);
     return sidlsg_last_error();

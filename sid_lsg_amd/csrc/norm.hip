@@ -674,10 +674,7 @@ struct GnSmall {
 };
 
 DEVFN int gn_small_block(const GnSmall& g, int& b, int& gr) {     // XCD-contiguous logical order: consecutive ids = (sample, range) row-major
-    int bid = blockIdx.x;
-    const int nblk = g.B * g.ngr;
-    const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    const int bid = xcd_contiguous((int)blockIdx.x, g.B * g.ngr);
     b = bid / g.ngr; gr = bid - b * g.ngr;
     return bid;
 }
@@ -866,10 +863,7 @@ struct GnGrp {
     int B, HW, C, G, cpg, D, R, NT;      // R pixel rows in flight, NT = D * R live threads (block size = NT rounded up to waves)
 };
 DEVFN void gn_grp_block(const GnGrp& g, int& b, int& gr) {
-    int bid = blockIdx.x;
-    const int nblk = g.B * g.G;
-    const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    const int bid = xcd_contiguous((int)blockIdx.x, g.B * g.G);
     b = bid / g.G; gr = bid - b * g.G;
     // (scalar registers: the buffer descriptors built from them must not end up in VGPRs -- waterfall loops around every buffer operation)
     b = __builtin_amdgcn_readfirstlane(b); gr = __builtin_amdgcn_readfirstlane(gr);
@@ -1059,8 +1053,8 @@ static bool gn_grp_geom(GnGrp& g, int& threads, int& P, int B, int HW, int C, in
     // everywhere (29.5 -> 33 us at 64x64 x 320, 37-41 -> 36.5 us at 32x32 x 1920).  Inside the step the backward under those two limits
     // is neutral (SIDLSG_GN_GROUP=2 vs 0, three alternations: 208.3 vs 208.1 ms): the kernels stay in the library, tested, and OFF by
     // default (mask bit 2 lifts the limits for measurements and for the test).
-    static const int mask = getenv("SIDLSG_GN_GROUP") ? atoi(getenv("SIDLSG_GN_GROUP")) : 0;
-    static const int min_hw = getenv("SIDLSG_GN_GROUP_MIN_HW") ? atoi(getenv("SIDLSG_GN_GROUP_MIN_HW")) : 1024;
+    static const int mask = sidlsg_env_int("SIDLSG_GN_GROUP", 0);
+    static const int min_hw = sidlsg_env_int("SIDLSG_GN_GROUP_MIN_HW", 1024);
     if (!((mask >> dirbit) & 1) || C % G || (C & 1) || B <= 0 || HW < min_hw) return false;
     const int cpg = C / G;
     if (cpg & 1) return false;
@@ -1078,7 +1072,7 @@ static bool gn_grp_geom(GnGrp& g, int& threads, int& P, int B, int HW, int C, in
 
 // Geometry of the one-pass kernels for a shape, or false: pmax = the largest per-thread chunk count the caller has a kernel for.
 static bool gn_small_geom(GnSmall& g, int& threads, int& P, int B, int HW, int C, int G, int pmax) {
-    static const bool on = !(getenv("SIDLSG_GN_ONEPASS") && atoi(getenv("SIDLSG_GN_ONEPASS")) == 0);      // A/B switch
+    static const bool on = sidlsg_env_on("SIDLSG_GN_ONEPASS");      // A/B switch
     if (!on || C % 8 || C % G || B <= 0 || HW <= 0) return false;
     g.B = B; g.HW = HW; g.C = C; g.G = G; g.cpg = C / G;
     int gpb = 0;
@@ -1101,12 +1095,12 @@ static bool gn_small_geom(GnSmall& g, int& threads, int& P, int B, int HW, int C
 static int gn_geom(GnGeom& g, int B, int HW, int C, int G) {
     if (C % 8 || C % G || C > GN_MAX_C || B <= 0 || HW <= 0) return SIDLSG_EINVAL;
     g.C = C; g.HW = HW; g.G = G; g.cpg = C / G; g.C8 = C / 8;
-    static const int gn_threads = getenv("SIDLSG_GN_THREADS") ? atoi(getenv("SIDLSG_GN_THREADS")) : 256;
+    static const int gn_threads = sidlsg_env_int("SIDLSG_GN_THREADS", 256);
     g.rows = gn_threads / g.C8; if (g.rows < 1) g.rows = 1;
     if (g.rows > HW) g.rows = HW;
     // enough (sample, chunk) blocks for ~6 blocks per CU (latency bound: bytes in flight per CU are what count; with
     // 2 blocks per CU the kernels ran at 2-3 TB/s), each chunk >= rows*4 pixels
-    static const int target = getenv("SIDLSG_GN_BLOCKS") ? atoi(getenv("SIDLSG_GN_BLOCKS")) : 512;
+    static const int target = sidlsg_env_int("SIDLSG_GN_BLOCKS", 512);
     int want = (target + B - 1) / B;
     int maxch = HW / (g.rows * 4); if (maxch < 1) maxch = 1;
     g.nch = want < maxch ? want : maxch;

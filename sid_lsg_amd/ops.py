@@ -359,7 +359,7 @@ def flush_deferred():
     _passes.flush()
 
 
-# ---- grouped dense weight gradients (csrc/gemm.hip "grouped dense weight gradients") -----------------------------------------------
+# ---- grouped dense weight gradients (csrc/wgrad.hip "grouped dense weight gradients") -----------------------------------------------
 # The C x C projections of a transformer block (to_out of both attentions, the cross-attention's to_q, proj_in / proj_out) and its
 # 77-token k|v projection each need ~56 pixel splits to fill the chip alone.  Their weight gradients are QUEUED here (operands kept
 # alive) and launched eight at a time as one grid + one slab reduction (sidlsg_wgrad_group_bf16); whatever is queued is launched when a

@@ -1,5 +1,5 @@
 """Shared by tests/test_gemm_cases_host.py and tests/test_gpu_gemm_exact.py (not a test module): EXACT cases for the bf16 GEMM / conv3x3 /
-weight-gradient family of csrc/gemm.hip and csrc/gemm_p8.h, the dispatch record every case must produce, and guarded buffers.
+weight-gradient family of csrc/gemm.hip, csrc/wgrad.hip and csrc/gemm_p8.h, the dispatch record every case must produce, and guarded buffers.
 
 Exact operands.  Activations and dY are integers in [-3, 3], weights integers in [-2, 2], all stored as bf16; bias, row vector and the
 previous contents of an accumulated output are integer-valued fp32, the residual is integer-valued bf16, alpha is 1, 0.5 or 2.  Every

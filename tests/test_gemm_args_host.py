@@ -1,4 +1,4 @@
-"""The argument contract of the GEMM / conv / weight-gradient entry points of csrc/gemm.hip, checked without a GPU.
+"""The argument contract of the GEMM / conv / weight-gradient entry points of csrc/gemm.hip, gemm_fp8.hip and wgrad.hip, checked without a GPU.
 
 Every entry point rejects a bad call with SIDLSG_EINVAL (-22) before its first HIP call.  For each one the table below holds one
 admissible argument list and flips one thing at a time.  The calls run in a child process that sees no GPU (HIP_VISIBLE_DEVICES=-1),

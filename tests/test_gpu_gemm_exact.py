@@ -1,4 +1,4 @@
-"""The bf16 GEMM / conv3x3 / weight-gradient kernels of csrc/gemm.hip and csrc/gemm_p8.h on the EXACT cases of tests/gemm_cases.py: for
+"""The bf16 GEMM / conv3x3 / weight-gradient kernels of csrc/gemm.hip, csrc/wgrad.hip and csrc/gemm_p8.h on the EXACT cases of tests/gemm_cases.py: for
 every table row the dispatch record must name the row's kernel, the result must equal the fp64 reference bit for bit (rounded once to
 bf16, to nearest even, where the output is bf16), the sentinel around the output must be intact and no NaN of the poisoned padding,
 guard rows or workspace may have reached the output.  Then the data-gradient chains of ops._conv_dgrad and one autograd pass each of
