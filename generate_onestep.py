@@ -57,6 +57,14 @@ from (the crop load_init_image produced) on the device: PSNR and SSIM (sid_lsg_a
 `--lpips_vgg SPEC --lpips_lin SPEC` name a torchvision VGG16 state dict and the lpips package's lin weights (or
 `random:lpips-vgg[:seed]` for both).  With `--mask_images` the `_keep` figures are those of the kept region (mask < 128).  Rank 0 writes
 `<outdir>/fidelity.json` (`options`, `per_image` keyed by PNG name, `mean`).  Without the option nothing changes.
+
+`--seeds_per_prompt K` (default 1) draws K samples per condition: sample `idx` keeps its seed and its file name and takes condition
+`idx // K` wherever `idx` selects one above (the prompt, the init image, the mask, the control image, the IP image).  `--diversity 1`
+(with K >= 2, both `--lpips_*` specs and a sample count that is a multiple of K) then scores, after generation, how different the K
+images of each prompt are (sid_lsg_amd.diversity): the LPIPS of all K (K - 1) / 2 pairs from ONE VGG16 pass over the K images
+(sidlsg_lpips_group_f32, each value the bits the paired path gives), their mean and minimum, and the mean SSIM and MSE of the same
+pairs.  Group g is scored by rank g mod world from the PNG files read back, so batch and rank boundaries do not matter.  Rank 0 writes
+`<outdir>/diversity.json` (`options`, `per_prompt` keyed by group index with `prompt`, `files` and the figures, `mean`).
 """
 import json
 import math
@@ -69,6 +77,7 @@ import numpy as np
 import torch
 
 from sid_lsg_amd import distributed as dist
+from sid_lsg_amd import diversity as prompt_diversity
 from sid_lsg_amd.clip import load_clip_vision
 from sid_lsg_amd.fidelity import aggregate as aggregate_fidelity
 from sid_lsg_amd.fidelity import check_specs as check_lpips_specs
@@ -342,12 +351,12 @@ def lora_options(lora, lora_scale):
     return (list(lora), scales) if lora else None
 
 
-def fidelity_options(init_images, fidelity, lpips_vgg, lpips_lin):
+def fidelity_options(init_images, fidelity, lpips_vgg, lpips_lin, diversity=False):
     """-> None without --fidelity, else (lpips_vgg, lpips_lin) (both None: PSNR and SSIM only); inconsistent options are refused."""
     given = [f for f, v in (('--lpips_vgg', lpips_vgg), ('--lpips_lin', lpips_lin)) if v is not None]
     if not fidelity:
-        if given:
-            raise click.UsageError(f'{" / ".join(given)} apply to --fidelity 1 only')
+        if given and not diversity:
+            raise click.UsageError(f'{" / ".join(given)} apply to --fidelity or --diversity only')
         return None
     if init_images is None:
         raise click.UsageError('--fidelity applies to --init_images only: an output is compared with the init image it started from')
@@ -357,6 +366,41 @@ def fidelity_options(init_images, fidelity, lpips_vgg, lpips_lin):
         except ValueError as e:
             raise click.UsageError(str(e))
     return lpips_vgg, lpips_lin
+
+
+def diversity_options(diversity, seeds_per_prompt, lpips_vgg, lpips_lin, keys):
+    """-> None without --diversity, else (lpips_vgg, lpips_lin, {group: [sample keys]}); `keys` are the samples' indices (the index
+    that picks a sample's condition).  Inconsistent options are refused by name."""
+    if not diversity:
+        return None
+    if seeds_per_prompt < 2:
+        raise click.UsageError('--diversity needs --seeds_per_prompt K with K >= 2: the K samples of one prompt are compared with each other')
+    try:
+        prompt_diversity.check_group_size(seeds_per_prompt)
+        check_lpips_specs(lpips_vgg, lpips_lin)
+    except ValueError as e:
+        raise click.UsageError(f'--diversity: {e}')
+    if len(keys) % seeds_per_prompt:
+        raise click.UsageError(f'--diversity: {len(keys)} samples (--seeds, --num) are not a multiple of --seeds_per_prompt {seeds_per_prompt}')
+    try:
+        return lpips_vgg, lpips_lin, prompt_diversity.groups_of(keys, seeds_per_prompt)
+    except ValueError as e:
+        raise click.UsageError(f'--diversity: {e}')
+
+
+def sample_path(outdir, subdirs, key):
+    """Where sample `key` is written."""
+    return os.path.join(os.path.join(outdir, f'{key - key % 1000:06d}') if subdirs else outdir, f'{key:06d}.png')
+
+
+def load_png_group(paths, device):
+    """The written files of one group, read back (PNG is lossless: these are the bits that were written) -> uint8 [K, 3, H, W]."""
+    import PIL.Image
+    arrs = []
+    for path in paths:
+        with PIL.Image.open(path) as im:
+            arrs.append(np.asarray(im.convert('RGB'), dtype=np.uint8))
+    return torch.from_numpy(np.stack(arrs)).to(device).permute(0, 3, 1, 2).contiguous()
 
 
 def load_ip_image(path):
@@ -413,11 +457,13 @@ def ip_image_embeds(files, indices, tower, device):
 @click.option('--fidelity', type=bool, default=False, show_default=True, help='With --init_images: PSNR / SSIM (and LPIPS) of every written image against its init image -> <outdir>/fidelity.json')
 @click.option('--lpips_vgg', type=str, default=None, metavar='SPEC', help='With --fidelity: a torch.save\'d torchvision VGG16 state dict, or random:lpips-vgg[:seed]; needs --lpips_lin')
 @click.option('--lpips_lin', type=str, default=None, metavar='SPEC', help='With --fidelity: the lin weights of the lpips package (its vgg.pth), or random:lpips-vgg[:seed]; needs --lpips_vgg')
+@click.option('--seeds_per_prompt', type=click.IntRange(min=1), default=1, show_default=True, help='K samples per condition: sample idx keeps its seed and file name and takes prompt (and init / mask / control / IP image) idx // K')
+@click.option('--diversity', type=bool, default=False, show_default=True, help='With --seeds_per_prompt K >= 2 and --lpips_vgg / --lpips_lin: all-pairs LPIPS (and SSIM, MSE) among the K samples of every prompt -> <outdir>/diversity.json')
 @click.option('--text_encoder', type=click.Choice(['torch', 'hip']), default=None, help='CLIP text encoder: the PyTorch module, or the same weights on the HIP kernels  [default: $SIDLSG_TEXT_ENCODER, else torch] (not a reference option)')
 def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, init_timestep, text_prompts, repo_id, resolution, use_fp16,
          enable_compress_npz, num_steps_eval, custom_seed, teacher_steps, guidance_scale, init_images, strength, sample_posterior, text_encoder,
          teacher_sampler, teacher_spacing, teacher_eta, guidance_rescale, negative_prompt, mask_images, mask_composite, controlnet, control_images,
-         control_scale, ip_adapter, ip_image_encoder, ip_images, ip_scale, fidelity, lpips_vgg, lpips_lin, lora, lora_scale):
+         control_scale, ip_adapter, ip_image_encoder, ip_images, ip_scale, fidelity, lpips_vgg, lpips_lin, lora, lora_scale, seeds_per_prompt, diversity):
     text_encoder_kind = text_encoder
     if resolution % 8:
         raise click.BadParameter(f'{resolution}: must be a multiple of 8', param_hint='--resolution')
@@ -427,8 +473,10 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
     masks = mask_options(init_images, mask_images, mask_composite, 0 if img2img is None else len(img2img[0]))
     control = control_options(controlnet, control_images, control_scale)
     ip = ip_options(ip_adapter, ip_image_encoder, ip_images, ip_scale)
-    fid = fidelity_options(init_images, fidelity, lpips_vgg, lpips_lin)
+    fid = fidelity_options(init_images, fidelity, lpips_vgg, lpips_lin, diversity)
     lora_opt = lora_options(lora, lora_scale)
+    div = diversity_options(diversity, seeds_per_prompt, lpips_vgg, lpips_lin,
+                            list(range(len(seeds[:num_fid_samples]))) if custom_seed else [int(s) for s in seeds[:num_fid_samples]])
     dist.init()
     device = torch.device('cuda')
     rank, world = dist.get_rank(), dist.get_world_size()
@@ -494,22 +542,23 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
         batch_seeds = [seeds[i] for i in batch] if custom_seed else batch
         rnd = StackedRandomGenerator(device, batch_seeds)
         z = rnd.randn([len(batch), 4, lat, lat], device=device)
-        prompts = [captions[i % len(captions)] for i in batch]
+        cond = [i // seeds_per_prompt for i in batch]          # the index that selects a sample's condition; K = 1: the sample's own
+        prompts = [captions[i % len(captions)] for i in cond]
         i2i = {}
         if img2img is not None:
             files, start_step, sample = img2img
-            init_pixels = load_init_batch(files, batch, resolution)
+            init_pixels = load_init_batch(files, cond, resolution)
             pixels = torch.from_numpy(init_pixels).to(device)
             eps = rnd.randn([len(batch), 4, lat, lat], device=device) if sample else None
             i2i = {'init_latents': vae_encoder.encode_latents(pixels, eps=eps), 'start_step' if teacher is None else 'start_index': start_step}
             if masks is not None:
-                pixel_mask = load_mask_batch(masks[0], batch, resolution)
+                pixel_mask = load_mask_batch(masks[0], cond, resolution)
                 i2i['mask'] = torch.from_numpy(latent_mask(pixel_mask)).to(device)
         if control is not None:        # one conversion launch + the hint embedder, once per batch; the guided teacher batch is [uncond ; cond]
-            hints = torch.from_numpy(load_control_batch(control[1], batch, resolution)).to(device)
+            hints = torch.from_numpy(load_control_batch(control[1], cond, resolution)).to(device)
             i2i['control'] = control_net.prepare(hints, scale=control[2], dup=2 if (teacher is not None and teacher[1] != 1) else 1)
         if ip is not None:             # the image tower, the projection and ONE k|v GEMM for all layers, once per batch
-            i2i['ip'] = ip_net.prepare(ip_image_embeds(ip[2], batch, ip_tower, device), scale=ip[3],
+            i2i['ip'] = ip_net.prepare(ip_image_embeds(ip[2], cond, ip_tower, device), scale=ip[3],
                                        dup=2 if (teacher is not None and teacher[1] != 1) else 1)
         with torch.no_grad():
             if teacher is not None and solver_kw is not None:
@@ -537,9 +586,9 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
                                None if masks is None else torch.from_numpy(pixel_mask).to(device), lpips_net)
             fid_rows.update({f'{key:06d}.png': row for key, row in zip(batch, rows)})
         for key, img in zip(batch, arr):
-            d = os.path.join(outdir, f'{key - key % 1000:06d}') if subdirs else outdir
-            os.makedirs(d, exist_ok=True)
-            save_png(os.path.join(d, f'{key:06d}.png'), np.ascontiguousarray(img))
+            path = sample_path(outdir, subdirs, key)
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            save_png(path, np.ascontiguousarray(img))
         if enable_compress_npz:
             np.savez_compressed(os.path.join(outdir, f'images_{batch[0]:06d}.npz'), images=arr)
     if fid is not None:
@@ -557,6 +606,29 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
             with open(os.path.join(outdir, 'fidelity.json'), 'w') as f:      # inf / nan are written as Infinity / NaN, which json.load reads back
                 json.dump(report, f, indent=1)
             dist.print0(f'Fidelity over {len(fid_rows)} images: {format_means(report["mean"])}')
+    if div is not None:            # after every file is written: group g is scored by rank g mod world from the files read back
+        if world > 1:
+            torch.distributed.barrier()
+        lpips_div = load_lpips(div[0], div[1], device)
+        div_rows = {}
+        for n, (g, keys) in enumerate(div[2].items()):
+            if n % world == rank:
+                row = prompt_diversity.score_groups(load_png_group([sample_path(outdir, subdirs, k) for k in keys], device), seeds_per_prompt, lpips_div)[0]
+                div_rows[g] = dict(prompt=captions[g % len(captions)], files=[f'{k:06d}.png' for k in keys], **row)
+        if world > 1:
+            parts = [None] * world
+            torch.distributed.all_gather_object(parts, div_rows)
+            div_rows = {k: v for part in parts for k, v in part.items()}
+        if rank == 0:
+            div_rows = {str(g): div_rows[g] for g in sorted(div_rows)}
+            report = dict(options=dict(network=network_pkl, seeds_per_prompt=seeds_per_prompt, text_prompts=text_prompts, resolution=resolution,
+                                       init_timestep=init_timestep, num_steps_eval=num_steps_eval, teacher_steps=teacher_steps,
+                                       guidance_scale=guidance_scale, init_images=init_images, controlnet=controlnet, ip_adapter=ip_adapter,
+                                       lpips_vgg=div[0], lpips_lin=div[1]),
+                          per_prompt=div_rows, mean=prompt_diversity.aggregate(div_rows))
+            with open(os.path.join(outdir, 'diversity.json'), 'w') as f:
+                json.dump(report, f, indent=1)
+            dist.print0(f'Diversity over {prompt_diversity.format_means(report["mean"])}')
     if world > 1:
         torch.distributed.barrier()
     dist.print0('Done.')

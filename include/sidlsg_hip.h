@@ -549,7 +549,24 @@ int sidlsg_inception_input_u8(const void* images, float* out, int B, int H, int 
  *   ws 8-byte aligned, B <= 32767, F below 2^31 bytes; SIDLSG_EINVAL and no launch otherwise.
  * sidlsg_lpips_sum_f64: vals [taps][B] doubles -> out[i] = ((vals[0][i] + vals[1][i]) + vals[2][i]) + .., the taps of a pair added in
  *   order: a pair's LPIPS does not depend on the batch it travels in (a library reduction may pick its order by the shape).
- *   1 <= taps <= 64, 1 <= B <= 32767, 8-byte aligned pointers; SIDLSG_EINVAL and no launch otherwise. */
+ *   1 <= taps <= 64, 1 <= B <= 32767, 8-byte aligned pointers; SIDLSG_EINVAL and no launch otherwise.
+ * sidlsg_lpips_group_f32: the all-pairs form of sidlsg_lpips_layer_f32.  F fp32 NHWC [G*K][h][wd][ldf], group g = rows gK .. gK+K-1;
+ *   out [G][P] doubles, P = K (K - 1) / 2, pairs (i, j), i < j, in lexicographic order: (0,1), (0,2), .., (0,K-1), (1,2), ..
+ *   out[g][p(i,j)] has exactly the bits sidlsg_lpips_layer_f32 writes for the pair (row gK+i, row gK+j): the same per-lane channel
+ *   order, butterfly, norm, division, difference, weighted square, per-group double sums in pixel order, one slot per 128-pixel
+ *   block and the same final reduction.  Maps of 512 pixel blocks and more (over all groups) are read once, every vector normalised
+ *   once and all pairs formed on chip; smaller ones, and groups too large for LDS, spread the pairs over the grid (see
+ *   sidlsg_lpips_group_form_f32).  A pair's value
+ *   does not depend on G, on K or on where the pair sits; an identical pair gives exactly 0, an all-zero pixel contributes 0.  No
+ *   atomics.  ws: sidlsg_lpips_group_ws_doubles(G, K, h, wd) doubles (negative outside the admitted set).  2 <= K <= 16, G >= 1,
+ *   G K <= 32767, G P <= 32767, C >= 4, C and ldf multiples of 4, ldf >= C, F and w 16-byte aligned, out and ws 8-byte aligned, F
+ *   below 2^31 bytes, G P ceil(h wd / 128) below 2^31; SIDLSG_EINVAL, no launch and out untouched otherwise.
+ * sidlsg_lpips_group_form_f32: the same with the launch form named: 1 = one workgroup per 128-pixel block and group, all pairs formed
+ *   on chip (one read of F); it keeps the K normalised vectors of 128 pixels in LDS and is SIDLSG_EINVAL where they do not fit in
+ *   64 KB next to the 128 P bytes of accumulators (2048 K ceil(C / 64) bytes: C 128 from K 14, C 256 from K 8, C 512 from K 4).
+ *   2 = one workgroup per block, pair and group (the paired kernel's grid without the gathered copies; every map is read K - 1
+ *   times).  0 = form 1 where it is admitted and has at least 512 workgroups, else form 2, which is what sidlsg_lpips_group_f32
+ *   does.  The forms write the same bits; the tests and tools/fidelity_cost.py name them.  Any other form is SIDLSG_EINVAL. */
 int sidlsg_psnr_ssim_ws_doubles(int B, int H, int W);
 int sidlsg_psnr_ssim_u8(const void* a, const void* b, const void* mask, int B, int H, int W, double* out, double* ws, void* stream);
 int sidlsg_lpips_input_u8(const void* a, const void* b, float* out, int B, int H, int W, float shift0, float shift1, float shift2,
@@ -557,6 +574,10 @@ int sidlsg_lpips_input_u8(const void* a, const void* b, float* out, int B, int H
 int sidlsg_lpips_layer_ws_doubles(int B, int h, int wd);
 int sidlsg_lpips_layer_f32(const float* F, int ldf, const float* w, int B, int h, int wd, int C, double* out, double* ws, void* stream);
 int sidlsg_lpips_sum_f64(const double* vals, int taps, int B, double* out, void* stream);
+int sidlsg_lpips_group_ws_doubles(int G, int K, int h, int wd);
+int sidlsg_lpips_group_f32(const float* F, int ldf, const float* w, int G, int K, int h, int wd, int C, double* out, double* ws, void* stream);
+int sidlsg_lpips_group_form_f32(const float* F, int ldf, const float* w, int G, int K, int h, int wd, int C, int form, double* out, double* ws,
+                                void* stream);
 
 /* ---- snapshot preview grids (save_image_grid, sid_training_loop.py:99-115, 597-614) -------------------------------------
  * B decoded fp32 images -> their tiles of ONE uint8 grid image [gh*H][gw*W][3] (HWC, what a PNG writer takes): image i goes to

@@ -184,13 +184,11 @@ DEVFN float lp_group_sum(float v) {
     return v;
 }
 
-// grid = (pixel blocks, B).  ws[image * nblk + block]
-__global__ __launch_bounds__(256) void lp_layer_kernel(const float* __restrict__ F, int ldf, const float* __restrict__ w, int B, int npix, int C,
-                                                       int nblk, double* __restrict__ ws) {
+// the 128-pixel block blockIdx.x of the maps F0 and F1 -> *slot; 256 threads
+DEVFN void lp_pair_block(const float* __restrict__ F0, const float* __restrict__ F1, int ldf, const float* __restrict__ w, int npix, int C,
+                         double* __restrict__ slot) {
     __shared__ double red[16];
-    const int t = threadIdx.x, l = t & 15, grp = t >> 4, img = blockIdx.y, c4 = C >> 2;
-    const float* F0 = F + (size_t)img * npix * ldf;
-    const float* F1 = F + (size_t)(B + img) * npix * ldf;
+    const int t = threadIdx.x, l = t & 15, grp = t >> 4, c4 = C >> 2;
     double acc = 0.0;
     for (int j = 0; j < LP_PPG; j++) {
         const int p = blockIdx.x * LP_PPB + j * 16 + grp;
@@ -230,8 +228,15 @@ __global__ __launch_bounds__(256) void lp_layer_kernel(const float* __restrict__
         double s = 0.0;
 #pragma unroll
         for (int g = 0; g < 16; g++) s += red[g];
-        ws[(size_t)img * nblk + blockIdx.x] = s;
+        *slot = s;
     }
+}
+
+// grid = (pixel blocks, B).  ws[image * nblk + block]
+__global__ __launch_bounds__(256) void lp_layer_kernel(const float* __restrict__ F, int ldf, const float* __restrict__ w, int B, int npix, int C,
+                                                       int nblk, double* __restrict__ ws) {
+    const int img = blockIdx.y;
+    lp_pair_block(F + (size_t)img * npix * ldf, F + (size_t)(B + img) * npix * ldf, ldf, w, npix, C, ws + (size_t)img * nblk + blockIdx.x);
 }
 
 // out[image] = (the image's nblk slots, added as in fd_reduce_kernel) / npix.  grid = B.
@@ -257,6 +262,151 @@ __global__ __launch_bounds__(256) void lp_sum_kernel(const double* __restrict__ 
     double s = v[i];
     for (int k = 1; k < taps; k++) s += v[(size_t)k * B + i];
     out[i] = s;
+}
+
+// ---- LPIPS group: all pairs of K images ---------------------------------------------------------------------------------------------
+// Two launch forms that write the same bits, those of lp_layer_kernel for each pair.
+//
+// lp_group_pair_kernel spreads the pairs over the grid: block (x, pair, g) is lp_layer_kernel's block x for the rows gK + i and gK + j
+// of the pair, without the gathered copies.  Every map is read K - 1 times, from L2 at the sizes this form is taken for.
+//
+// lp_group_kernel forms all pairs of a 128-pixel block in one workgroup, so F is read once: f / n does not depend on the partner, so
+// every vector is normalised once; d * d is symmetric, so only i < j is formed.  A lane only ever touches its own 16-byte chunks
+// (l, l + 16, ..) of the K vectors of a pixel, so the normalised copy in LDS is lane-private: qs[(image * nch + chunk) * T + thread],
+// one ds_read_b128 per chunk, no bank conflict and no barrier.  Per pair and lane group one double in LDS (accs[pair][group]), added
+// to by lane 0 of the group alone in pixel order; thread `pair` adds the 16 groups in order into the pair's slot of this block.  The
+// block has T = 256 or 128 threads (the larger whose copy fits next to the accumulators) and walks the 16 lane groups of the pixel
+// block in 256 / T rounds.  NCH > 0: a lane owns at most NCH chunks (C <= 64 NCH) and the chunk loops are unrolled, image i's chunks
+// and the weights held in registers; NCH == 0: any C, loops over nch chunks.
+constexpr int LPG_KMAX = 16, LPG_LDS = 64 * 1024, LPG_MIN_BLOCKS = 512;
+
+// grid = (pixel blocks, P, G).  ws[(g * P + pair) * nblk + block]
+__global__ __launch_bounds__(256) void lp_group_pair_kernel(const float* __restrict__ F, int ldf, const float* __restrict__ w, int K, int npix, int C,
+                                                            int nblk, double* __restrict__ ws) {
+    int i = 0, first = 0;                                     // pair -> (i, j): row i holds the pairs first .. first + K - 2 - i
+    while ((int)blockIdx.y >= first + K - 1 - i) {
+        first += K - 1 - i;
+        i++;
+    }
+    const int j = i + 1 + ((int)blockIdx.y - first);
+    const float* Fg = F + (size_t)blockIdx.z * K * npix * ldf;
+    lp_pair_block(Fg + (size_t)i * npix * ldf, Fg + (size_t)j * npix * ldf, ldf, w, npix, C,
+                  ws + ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * nblk + blockIdx.x);
+}
+
+// grid = (pixel blocks, G), T threads, P * 128 + K * nch * T * 16 bytes of LDS.  ws[(g * P + pair) * nblk + block]
+template <int NCH>
+__global__ __launch_bounds__(256) void lp_group_kernel(const float* __restrict__ F, int ldf, const float* __restrict__ w, int K, int npix, int C,
+                                                       int nblk, int nch, double* __restrict__ ws) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lpg_smem[];
+    const int T = blockDim.x, t = threadIdx.x, l = t & 15, c4 = C >> 2, P = K * (K - 1) / 2;
+    const int nc = NCH > 0 ? NCH : nch;
+    constexpr int LPG_UNROLL = NCH > 0 ? NCH : 1;                                        // the chunk loops: whole when NCH is known
+    double* accs = reinterpret_cast<double*>(lpg_smem);                                  // [P][16]
+    f32x4* qs = reinterpret_cast<f32x4*>(lpg_smem + (size_t)P * 16 * sizeof(double));    // [K][nch][T]
+    for (int i = t; i < P * 16; i += T) accs[i] = 0.0;
+    __syncthreads();
+    const size_t istride = (size_t)npix * ldf;
+    const float* Fg = F + (size_t)blockIdx.y * K * istride;
+    f32x4 wreg[NCH > 0 ? NCH : 1], areg[NCH > 0 ? NCH : 1];
+    if (NCH > 0) {
+#pragma unroll LPG_UNROLL
+        for (int c = 0; c < nc; c++) {
+            const int k = l + 16 * c;
+            if (k < c4) wreg[c] = *reinterpret_cast<const f32x4*>(w + 4 * k);
+        }
+    }
+    for (int g0 = 0; g0 < 16; g0 += T >> 4) {
+        const int grp = g0 + (t >> 4);
+        for (int j = 0; j < LP_PPG; j++) {
+            const int p = blockIdx.x * LP_PPB + j * 16 + grp;
+            const float* f = Fg + (size_t)min(p, npix - 1) * ldf;     // a group past the last pixel recomputes it and drops the values
+            for (int i = 0; i < K; i++) {                             // the K vectors of the pixel, normalised, into this lane's slots
+                const float* fi = f + (size_t)i * istride;
+                float s = 0.0f;
+#pragma unroll LPG_UNROLL
+                for (int c = 0; c < nc; c++) {
+                    const int k = l + 16 * c;
+                    if (k < c4) {
+                        const f32x4 a = *reinterpret_cast<const f32x4*>(fi + 4 * k);
+                        qs[(size_t)(i * nch + c) * T + t] = a;
+#pragma unroll
+                        for (int e = 0; e < 4; e++) s = __fadd_rn(s, __fmul_rn(a[e], a[e]));
+                    }
+                }
+                s = lp_group_sum(s);
+                const float n = __fadd_rn(__fsqrt_rn(s), 1e-10f);
+#pragma unroll LPG_UNROLL
+                for (int c = 0; c < nc; c++) {
+                    const int k = l + 16 * c;
+                    if (k < c4) {
+                        f32x4 a = qs[(size_t)(i * nch + c) * T + t];
+#pragma unroll
+                        for (int e = 0; e < 4; e++) a[e] = __fdiv_rn(a[e], n);
+                        qs[(size_t)(i * nch + c) * T + t] = a;
+                    }
+                }
+            }
+            int pair = 0;
+            for (int i = 0; i < K - 1; i++) {
+                if (NCH > 0) {
+#pragma unroll LPG_UNROLL
+                    for (int c = 0; c < nc; c++) {
+                        const int k = l + 16 * c;
+                        if (k < c4) areg[c] = qs[(size_t)(i * nch + c) * T + t];
+                    }
+                }
+                for (int jj = i + 1; jj < K; jj++, pair++) {
+                    float sd = 0.0f;
+#pragma unroll LPG_UNROLL
+                    for (int c = 0; c < nc; c++) {
+                        const int k = l + 16 * c;
+                        if (k < c4) {
+                            const f32x4 a = NCH > 0 ? areg[c] : qs[(size_t)(i * nch + c) * T + t];
+                            const f32x4 wk = NCH > 0 ? wreg[c] : *reinterpret_cast<const f32x4*>(w + 4 * k);
+                            const f32x4 b = qs[(size_t)(jj * nch + c) * T + t];
+#pragma unroll
+                            for (int e = 0; e < 4; e++) {
+                                const float d = __fsub_rn(a[e], b[e]);
+                                sd = __fadd_rn(sd, __fmul_rn(wk[e], __fmul_rn(d, d)));
+                            }
+                        }
+                    }
+                    const float val = lp_group_sum(sd);
+                    if (l == 0) accs[pair * 16 + grp] += p < npix ? (double)val : 0.0;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (int pr = t; pr < P; pr += T) {
+        double s = 0.0;
+#pragma unroll
+        for (int g = 0; g < 16; g++) s += accs[pr * 16 + g];
+        ws[((size_t)blockIdx.y * P + pr) * nblk + blockIdx.x] = s;
+    }
+}
+
+// the admitted set of sidlsg_lpips_group_f32 but for the pointers: pixel blocks, or false
+bool lpg_geometry(int G, int K, int h, int wd, int* nblk) {
+    if (K < 2 || K > LPG_KMAX || G < 1 || h < 1 || wd < 1) return false;
+    const long long P = (long long)K * (K - 1) / 2;
+    if ((long long)G * K > 32767 || (long long)G * P > 32767) return false;
+    const long long npix = (long long)h * wd;
+    if (npix >= (1LL << 31)) return false;
+    const long long nb = (npix + LP_PPB - 1) / LP_PPB;
+    if (nb * G * P >= (1LL << 31)) return false;
+    *nblk = (int)nb;
+    return true;
+}
+
+// threads of lp_group_kernel: the larger of 256 and 128 whose normalised copy fits next to the accumulators, or 0 (the copy does
+// not fit: C 128 from K 14, C 256 from K 8, C 512 from K 4)
+int lpg_threads(int K, int nch) {
+    const size_t accs = (size_t)(K * (K - 1) / 2) * 16 * sizeof(double);
+    for (int T = 256; T >= 128; T >>= 1)
+        if (accs + (size_t)K * nch * T * 16 <= (size_t)LPG_LDS) return T;
+    return 0;
 }
 
 bool lp_geometry(int B, int h, int wd, int* nblk) {
@@ -326,6 +476,49 @@ int sidlsg_lpips_layer_f32(const float* F, int ldf, const float* w, int B, int h
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(lp_layer_kernel, dim3((unsigned)nblk, (unsigned)B), dim3(256), 0, s, F, ldf, w, B, (int)npix, C, nblk, ws);
     hipLaunchKernelGGL(lp_reduce_kernel, dim3((unsigned)B), dim3(256), 0, s, (const double*)ws, out, nblk, (int)npix);
+    return sidlsg_last_error();
+}
+
+int sidlsg_lpips_group_ws_doubles(int G, int K, int h, int wd) {
+    int nblk;
+    if (!lpg_geometry(G, K, h, wd, &nblk)) return -1;
+    return G * (K * (K - 1) / 2) * nblk;
+}
+
+int sidlsg_lpips_group_form_f32(const float* F, int ldf, const float* w, int G, int K, int h, int wd, int C, int form, double* out, double* ws,
+                                void* stream);
+
+int sidlsg_lpips_group_f32(const float* F, int ldf, const float* w, int G, int K, int h, int wd, int C, double* out, double* ws, void* stream) {
+    return sidlsg_lpips_group_form_f32(F, ldf, w, G, K, h, wd, C, 0, out, ws, stream);
+}
+
+int sidlsg_lpips_group_form_f32(const float* F, int ldf, const float* w, int G, int K, int h, int wd, int C, int form, double* out, double* ws,
+                                void* stream) {
+    int nblk;
+    if (form < 0 || form > 2) return SIDLSG_EINVAL;
+    if (!F || !w || !out || !ws || (((uintptr_t)F | (uintptr_t)w) & 15) || (((uintptr_t)out | (uintptr_t)ws) & 7)) return SIDLSG_EINVAL;
+    if (C < 4 || (C & 3) || ldf < C || (ldf & 3)) return SIDLSG_EINVAL;
+    if (!lpg_geometry(G, K, h, wd, &nblk)) return SIDLSG_EINVAL;
+    const long long npix = (long long)h * wd;
+    if ((long long)G * K * npix * ldf * 4 >= (1LL << 31)) return SIDLSG_EINVAL;
+    const int P = K * (K - 1) / 2, nch = ((C >> 2) + 15) / 16, T = lpg_threads(K, nch);
+    if (form == 1 && !T) return SIDLSG_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    // The on-chip form reads F once, but each of its workgroups walks the P pairs of its pixels in turn: with fewer than LPG_MIN_BLOCKS
+    // workgroups most of the 256 CUs idle (128 workgroups at 128 x 128, K 4: 3.6 times the paired launch; profiles/diversity.txt).
+    // Such maps, and groups whose normalised copy does not fit in LDS, spread the pairs over the grid.
+    if (form == 2 || (form == 0 && (!T || (long long)nblk * G < LPG_MIN_BLOCKS))) {
+        hipLaunchKernelGGL(lp_group_pair_kernel, dim3((unsigned)nblk, (unsigned)P, (unsigned)G), dim3(256), 0, s, F, ldf, w, K, (int)npix, C, nblk, ws);
+    } else {
+        const size_t lds = (size_t)P * 16 * sizeof(double) + (size_t)K * nch * T * 16;
+        const dim3 grid((unsigned)nblk, (unsigned)G);
+        if (nch <= 1) hipLaunchKernelGGL(lp_group_kernel<1>, grid, dim3(T), lds, s, F, ldf, w, K, (int)npix, C, nblk, nch, ws);
+        else if (nch <= 2) hipLaunchKernelGGL(lp_group_kernel<2>, grid, dim3(T), lds, s, F, ldf, w, K, (int)npix, C, nblk, nch, ws);
+        else if (nch <= 4) hipLaunchKernelGGL(lp_group_kernel<4>, grid, dim3(T), lds, s, F, ldf, w, K, (int)npix, C, nblk, nch, ws);
+        else if (nch <= 8) hipLaunchKernelGGL(lp_group_kernel<8>, grid, dim3(T), lds, s, F, ldf, w, K, (int)npix, C, nblk, nch, ws);
+        else hipLaunchKernelGGL(lp_group_kernel<0>, grid, dim3(T), lds, s, F, ldf, w, K, (int)npix, C, nblk, nch, ws);
+    }
+    hipLaunchKernelGGL(lp_reduce_kernel, dim3((unsigned)(G * P)), dim3(256), 0, s, (const double*)ws, out, nblk, (int)npix);
     return sidlsg_last_error();
 }
 

@@ -18,6 +18,10 @@ input launch on (sidlsg_lpips_input_u8), the 13 convolutions run on ops.conv2d_r
 one sidlsg_lpips_layer_f32 launch, and the five per-tap values of a pair are added in tap order by one more (sidlsg_lpips_sum_f64).  LPIPS-Alex is not offered: its 11 x 11 /
 stride 4 first layer is outside the convolution's admitted set.
 
+`HipLPIPS.group_pairs` is the all-pairs form behind sid_lsg_amd.diversity: VGG16 once per image (`features`), and every tap one
+sidlsg_lpips_group_f32 launch that forms the K (K - 1) / 2 pairs of a group of K maps in place, each value the bits the paired launch
+gives that pair.
+
 Weights: a torch.save'd VGG16 state dict in torchvision key names and the lpips package's lin weights, or the seeded
 'random:lpips-vgg[:seed]' for both, whose scores mean nothing outside this package.
 """
@@ -149,6 +153,39 @@ def lpips_layer_f32(feats, w, out=None):
     return out
 
 
+GROUP_MAX = 16            # images per group that sidlsg_lpips_group_f32 admits
+
+
+GROUP_FORMS = {None: 0, 'chip': 1, 'pairs': 2}
+
+
+def lpips_group_f32(feats, w, K, out=None, form=None):
+    """feats fp32 NHWC [G*K, h, wd, ldf], w [C] (C <= ldf) -> [G, K (K - 1) / 2] fp64 (sidlsg_lpips_group_f32): what lpips_layer_f32
+    gives for every pair (i, j), i < j, of the K rows of a group, in lexicographic pair order, bit for bit.  `form` names the launch
+    form for tests and measurements ('chip': all pairs of a pixel block in one workgroup; 'pairs': one workgroup per block and pair);
+    None lets the library choose by the size of the map.  The forms write the same bits."""
+    ops._chk(feats, torch.float32), ops._chk(w, torch.float32)
+    if feats.dim() != 4 or K < 2 or feats.shape[0] % K or w.dim() != 1 or w.shape[0] > feats.shape[3]:
+        raise RuntimeError(f'lpips_group_f32: feats {tuple(feats.shape)}, w {tuple(w.shape)}, groups of {K}')
+    N, h, wd, ldf = feats.shape
+    G, P = N // K, K * (K - 1) // 2
+    nws = lib.sidlsg_lpips_group_ws_doubles.raw(G, K, h, wd)
+    if nws < 0:
+        raise RuntimeError(f'lpips_group_f32: {G} groups of {K} maps of {h} x {wd} pixels are outside the admitted set (2 <= K <= {GROUP_MAX}, '
+                           'at most 32767 maps and 32767 pairs)')
+    if out is None:
+        out = torch.empty((G, P), device=feats.device, dtype=torch.float64)
+    ops._chk(out, torch.float64)
+    if out.numel() != G * P:
+        raise RuntimeError(f'lpips_group_f32: out {tuple(out.shape)}, expected {(G, P)}')
+    ws = torch.empty(nws, device=feats.device, dtype=torch.float64)
+    if form is None:
+        lib.sidlsg_lpips_group_f32(ops._p(feats), ldf, ops._p(w), G, K, h, wd, w.shape[0], ops._p(out), ops._p(ws), ops._s())
+    else:
+        lib.sidlsg_lpips_group_form_f32(ops._p(feats), ldf, ops._p(w), G, K, h, wd, w.shape[0], GROUP_FORMS[form], ops._p(out), ops._p(ws), ops._s())
+    return out
+
+
 def vgg_shapes():
     """{state-dict key: shape} of the VGG16 tensors the network reads."""
     shapes = {}
@@ -276,6 +313,48 @@ class HipLPIPS:
         out = torch.empty(a.shape[0], device=self.device, dtype=torch.float64)
         lib.sidlsg_lpips_sum_f64(ops._p(vals), vals.shape[0], vals.shape[1], ops._p(out), ops._s())
         return out
+
+    def features(self, images):
+        """uint8 [N, 3, H, W] -> the five tap feature maps [N, h, w, C] of the N images (views of buffers this object keeps and
+        overwrites).  The images travel as the two halves of one `taps` batch, an odd N padded by its last image, so an image's maps
+        are the bits `taps` gives it."""
+        N = images.shape[0]
+        half = (N + 1) // 2
+        b = images[half:] if N % 2 == 0 else torch.cat([images[half:], images[-1:]])
+        return [f[:N] for f in self.taps(images[:half], b)]
+
+    def group_pass(self, images, K):
+        """One pass (at most 2 max_pairs(H, W) images, whole groups): [G, K (K - 1) / 2] fp64, a fresh tensor.  1 input + 13 convolution
+        + 4 pool + 5 group-layer + 1 sum launches, whatever K is."""
+        G, P = images.shape[0] // K, K * (K - 1) // 2
+        vals = self._buf('gvals', (len(TAP_CHANNELS), G * P), torch.float64)
+        for i, f in enumerate(self.features(images)):
+            lpips_group_f32(f, self.lins[i], K, out=vals[i])
+        out = torch.empty((G, P), device=self.device, dtype=torch.float64)
+        lib.sidlsg_lpips_sum_f64(ops._p(vals), vals.shape[0], vals.shape[1], ops._p(out), ops._s())
+        return out
+
+    @torch.no_grad()
+    def group_pairs(self, images, K):
+        """uint8 [G*K, 3, H, W], group g = images gK .. gK+K-1 -> [G, K (K - 1) / 2] fp64: LPIPS of every pair (i, j), i < j, of a
+        group in lexicographic pair order, each entry the bits of self(a_i[None], a_j[None]).  VGG16 runs once per image."""
+        if self.note and self.note not in _warned:
+            _warned.add(self.note)
+            dist.print0(self.note)
+        images = torch.as_tensor(images).to(self.device).contiguous()
+        ops._chk(images, torch.uint8)
+        if images.dim() != 4 or images.shape[1] != 3 or images.shape[0] < 1:
+            raise RuntimeError(f'HipLPIPS.group_pairs: expected uint8 [G*K, 3, H, W], got {tuple(images.shape)}')
+        N, _, H, W = images.shape
+        if not 2 <= K <= GROUP_MAX or N % K:
+            raise ValueError(f'HipLPIPS.group_pairs: {N} images in groups of {K}: expected 2 <= K <= {GROUP_MAX} and whole groups')
+        per_pass = 2 * self.max_pairs(H, W)
+        if K > per_pass:
+            raise ValueError(f'HipLPIPS.group_pairs: a group of K = {K} images of {H} x {W} exceeds one pass ({per_pass} images: the first '
+                             "stage's map is kept to 2^30 bytes)")
+        groups = max(1, min(per_pass // K, 32767 // (K * (K - 1) // 2)))
+        outs = [self.group_pass(images[g * K:(g + groups) * K], K) for g in range(0, N // K, groups)]
+        return outs[0] if len(outs) == 1 else torch.cat(outs)
 
     @torch.no_grad()
     def __call__(self, a, b):

@@ -367,9 +367,11 @@ class MetricOptions:
     def __init__(self, G, prompts=None, resolution=512, init_timestep=625, detector=None, real_stats=None, open_clip_detector=None,
                  clip_score_fn=None, device=None, seed=0, batch_gen=4, detector_size=256, progress=None, dataset_kwargs=None,
                  dataset=None, run_dir=None, metric_clip_path=None, metric_hps_path=None, hps_prompts=None, hps_arch=None, hps_tokenizer=None,
-                 hps_detector=None, metric_cmmd_clip_path=None):
+                 hps_detector=None, metric_cmmd_clip_path=None, metric_lpips_vgg=None, metric_lpips_lin=None, lpips_detector=None):
         from .dnnlib_util import construct_class_by_name
         self.metric_cmmd_clip_path = metric_cmmd_clip_path      # --metric_cmmd_clip_path: the CLIP image tower behind `cmmd*`
+        # --metric_lpips_vgg / --metric_lpips_lin: the LPIPS-VGG weights behind `lpipsdiv*` (or a ready fidelity.HipLPIPS)
+        self.metric_lpips_vgg, self.metric_lpips_lin, self.lpips_detector = metric_lpips_vgg, metric_lpips_lin, lpips_detector
         self.run_dir = run_dir
         if dataset is None and dataset_kwargs:
             dataset = construct_class_by_name(**dataset_kwargs)
@@ -823,6 +825,59 @@ def hpsv2_test(opts):
     return compute_hps(opts, 16)
 
 
+def compute_prompt_diversity(opts, num_prompts, per_prompt):
+    """Intra-prompt diversity (sid_lsg_amd.diversity): for each of `num_prompts` prompts, `per_prompt` images from the latents of
+    torch.Generator(p * per_prompt + j), j < per_prompt (compute_hps's rule), and the LPIPS-VGG of all their pairs from one VGG16
+    pass (HipLPIPS.group_pairs).  The prompts are the first `num_prompts` of the order generator_feature_stats uses
+    (InfiniteSampler(dataset, seed=0) over all ranks).  -> (mean over prompts of the mean pairwise LPIPS, mean over prompts of the
+    smallest pair).  Prompts are rank-strided; every rank returns the same numbers.  Neither real images nor their statistics are read."""
+    from . import fidelity
+    from .data import InfiniteSampler
+    lp = opts.lpips_detector
+    if lp is None:
+        if not opts.metric_lpips_vgg or not opts.metric_lpips_lin:
+            raise ValueError('lpipsdiv needs --metric_lpips_vgg (a torchvision VGG16 state dict) and --metric_lpips_lin (the lpips package\'s '
+                             f'vgg.pth), or {fidelity.RANDOM_PREFIX}[:seed] for both')
+        lp = fidelity.load_lpips(opts.metric_lpips_vgg, opts.metric_lpips_lin, opts.device)
+    if len(opts.dataset) < 1:
+        raise ValueError('lpipsdiv needs a prompt source: dataset_kwargs, dataset or prompts')
+    order = iter(InfiniteSampler(opts.dataset, rank=0, num_replicas=1, seed=0))
+    captions = [_caption(opts.dataset, next(order)) for _ in range(num_prompts)]
+    lat = opts.resolution // 8
+    full = torch.zeros((num_prompts, 2), dtype=torch.float64, device=opts.device)
+    for n, p in enumerate(range(opts.rank, num_prompts, opts.num_gpus)):
+        imgs = []
+        for i in range(0, per_prompt, opts.batch_gen):
+            js = range(i, min(i + opts.batch_gen, per_prompt))
+            z = torch.stack([torch.randn([4, lat, lat], device=opts.device, generator=torch.Generator(opts.device).manual_seed(p * per_prompt + j)) for j in js])
+            with torch.no_grad():
+                img = opts.G(latents=z, contexts=[captions[p]] * len(js), init_timesteps=opts.init_timestep * torch.ones(len(js), device=opts.device, dtype=torch.long))
+            imgs.append((img * 127.5 + 128).clamp(0, 255).to(torch.uint8))
+        pairs = lp.group_pairs(torch.cat(imgs), per_prompt)[0].cpu().tolist()
+        total = 0.0
+        for v in pairs:                                                                 # the pairs added in order, as diversity.score_groups does
+            total += v
+        full[p, 0], full[p, 1] = total / len(pairs), min(pairs)
+        if opts.progress is not None:
+            opts.progress((n + 1) * opts.num_gpus, num_prompts)
+    if opts.num_gpus > 1:
+        torch.distributed.all_reduce(full)
+    rows = full.cpu().tolist()
+    return sum(r[0] for r in rows) / num_prompts, sum(r[1] for r in rows) / num_prompts
+
+
+@register_metric
+def lpipsdiv1k_full(opts):
+    mean, low = compute_prompt_diversity(opts, 1000, 8)
+    return dict(lpipsdiv1k_full=mean, lpipsdiv1k_full_min=low)
+
+
+@register_metric
+def lpipsdiv_test(opts):
+    mean, low = compute_prompt_diversity(opts, max(1, getattr(opts, 'num_test', 1)), 4)
+    return dict(lpipsdiv_test=mean, lpipsdiv_test_min=low)
+
+
 @register_metric
 def kid30k_full(opts):
     return dict(kid30k_full=compute_kid(opts, max_real=None, num_gen=30000))
@@ -848,6 +903,7 @@ NEEDS_IMAGES = ('pr30k3_full', 'pr_test', 'kid30k_full', 'kid_test', 'cmmd30k_fu
 HPS_METRICS = ('hpsv2', 'hpsv2_test')          # metrics that need neither the Inception detector nor real-set statistics
 CMMD_METRICS = ('cmmd30k_full', 'cmmd_test')   # likewise: the CLIP image tower of --metric_cmmd_clip_path and the real images
 IS_METRICS = ('is30k_full', 'is_test')         # the Inception detector alone: neither real images nor their statistics
+LPIPSDIV_METRICS = ('lpipsdiv1k_full', 'lpipsdiv_test')      # --metric_lpips_vgg / --metric_lpips_lin alone: no Inception file, no statistics, no real images
 
 
 def calc_metric(metric, **kwargs):

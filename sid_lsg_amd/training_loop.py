@@ -120,11 +120,13 @@ def _text_encoder_opt(kind):
     return {} if kind is None else dict(text_encoder=kind)
 
 
-def _hps_opt(metric_hps_path, hps_prompts, hps_arch, hps_tokenizer, sd_model, metric_cmmd_clip_path=None):
+def _hps_opt(metric_hps_path, hps_prompts, hps_arch, hps_tokenizer, sd_model, metric_cmmd_clip_path=None, metric_lpips_vgg=None, metric_lpips_lin=None):
     """The HPSv2 options as calc_metric (and the evaluate_* functions) take them; nothing when no checkpoint was given.  The
     tokenizer defaults to the tokenizer/ directory of the Stable Diffusion model: the same CLIP vocabulary.  The CLIP model of the
-    CMMD metrics travels the same way, and is likewise absent when not given."""
+    CMMD metrics travels the same way, and is likewise absent when not given; so do the LPIPS weights of the `lpipsdiv*` metrics."""
     cmmd = {} if metric_cmmd_clip_path is None else dict(metric_cmmd_clip_path=metric_cmmd_clip_path)
+    if metric_lpips_vgg is not None or metric_lpips_lin is not None:
+        cmmd.update(metric_lpips_vgg=metric_lpips_vgg, metric_lpips_lin=metric_lpips_lin)
     if metric_hps_path is None and hps_prompts is None:
         return cmmd
     return dict(metric_hps_path=metric_hps_path, hps_prompts=hps_prompts, hps_arch=hps_arch,
@@ -168,8 +170,9 @@ def training_loop(
     rng_device=None, metric_real_stats=None, metric_num_test=None, deterministic=False, snapshot_images=False,
     teacher_steps=None, teacher_cfg=None, text_encoder=None, metric_hps_path=None, hps_prompts=None, hps_arch=None, hps_tokenizer=None,
     teacher_sampler=None, teacher_spacing=None, teacher_eta=None, teacher_rescale=None, metric_cmmd_clip_path=None, lora=None,
+    metric_lpips_vgg=None, metric_lpips_lin=None,
 ):
-    hps_kwargs = _hps_opt(metric_hps_path, hps_prompts, hps_arch, hps_tokenizer, pretrained_model_name_or_path, metric_cmmd_clip_path)
+    hps_kwargs = _hps_opt(metric_hps_path, hps_prompts, hps_arch, hps_tokenizer, pretrained_model_name_or_path, metric_cmmd_clip_path, metric_lpips_vgg, metric_lpips_lin)
     if not train_mode and network_pkl == TEACHER:
         return evaluate_teacher(run_dir=run_dir, dataset_kwargs=dataset_kwargs, network_kwargs=network_kwargs, device=device, metrics=metrics,
                                 init_timestep=init_timestep, metric_pt_path=metric_pt_path, metric_open_clip_path=metric_open_clip_path, metric_clip_path=metric_clip_path,
@@ -473,7 +476,7 @@ def evaluate_network(run_dir, dataset_kwargs, network_kwargs, device, metrics, i
                      pretrained_model_name_or_path, network_pkl, resolution, num_steps=1, metric_real_stats=None, metric_num_test=None,
                      dataset_prompt_text_kwargs=None, snapshot_images=False, batch_size=512, batch_gpu=None, metric_clip_path=None,
                      text_encoder=None, metric_hps_path=None, hps_prompts=None, hps_arch=None, hps_tokenizer=None, metric_cmmd_clip_path=None,
-                     lora=None):
+                     lora=None, metric_lpips_vgg=None, metric_lpips_lin=None):
     """`--train_mode 0` (sid_training_loop.py:680-745): load the text encoder / VAE / scheduler, un-pickle the distilled generator
     from `network_pkl` (`pickle.load(f)['ema']`, the file the training loop writes at the snapshot ticks) and evaluate every metric
     with 1, 2 and 4 generation steps; each result goes to `<dirname(run_dir)>/<metric><number>_<steps>.txt` in the reference's
@@ -486,7 +489,7 @@ def evaluate_network(run_dir, dataset_kwargs, network_kwargs, device, metrics, i
     from .sd_util import sid_sd_sampler
     if not metrics:
         raise ValueError('--train_mode 0 evaluates metrics: pass --metrics')
-    hps_kwargs = _hps_opt(metric_hps_path, hps_prompts, hps_arch, hps_tokenizer, pretrained_model_name_or_path, metric_cmmd_clip_path)
+    hps_kwargs = _hps_opt(metric_hps_path, hps_prompts, hps_arch, hps_tokenizer, pretrained_model_name_or_path, metric_cmmd_clip_path, metric_lpips_vgg, metric_lpips_lin)
     if not network_pkl or not os.path.isfile(network_pkl):
         raise FileNotFoundError(f'--network_pkl {network_pkl!r}: a local network-snapshot-*.pkl is needed (there is no network to fetch one)')
     dtype = resolve_compute_dtype(dict(network_kwargs).get('compute_dtype'))
@@ -562,7 +565,8 @@ def evaluate_teacher(run_dir, dataset_kwargs, network_kwargs, device, metrics, i
                      pretrained_model_name_or_path, resolution, teacher_steps=TEACHER_STEPS, teacher_cfg=TEACHER_CFG, metric_real_stats=None,
                      metric_num_test=None, dataset_prompt_text_kwargs=None, snapshot_images=False, batch_size=512, batch_gpu=None,
                      metric_clip_path=None, text_encoder=None, metric_hps_path=None, hps_prompts=None, hps_arch=None, hps_tokenizer=None,
-                     teacher_sampler=None, teacher_spacing=None, teacher_eta=None, teacher_rescale=None, metric_cmmd_clip_path=None, lora=None):
+                     teacher_sampler=None, teacher_spacing=None, teacher_eta=None, teacher_rescale=None, metric_cmmd_clip_path=None, lora=None,
+                     metric_lpips_vgg=None, metric_lpips_lin=None):
     """`--train_mode 0 --network_pkl teacher`: the teacher row of the tables under this project's own protocol.  The UNet of the model
     is sampled with classifier-free guidance `teacher_cfg` and a `teacher_steps`-step deterministic DDIM sampler
     (sd_util.teacher_sample) as the `G` of every metric -- the same prompts, seeds, VAE, detector resize and metric code as a
@@ -578,7 +582,7 @@ def evaluate_teacher(run_dir, dataset_kwargs, network_kwargs, device, metrics, i
     from .sd_util import teacher_sample, teacher_sample_solver
     if not metrics:
         raise ValueError('--train_mode 0 evaluates metrics: pass --metrics')
-    hps_kwargs = _hps_opt(metric_hps_path, hps_prompts, hps_arch, hps_tokenizer, pretrained_model_name_or_path, metric_cmmd_clip_path)
+    hps_kwargs = _hps_opt(metric_hps_path, hps_prompts, hps_arch, hps_tokenizer, pretrained_model_name_or_path, metric_cmmd_clip_path, metric_lpips_vgg, metric_lpips_lin)
     dtype = resolve_compute_dtype(dict(network_kwargs).get('compute_dtype'))
     unet, vae, noise_scheduler, text_encoder, tokenizer = load_sd15(
         pretrained_model_name_or_path=pretrained_model_name_or_path, pretrained_vae_model_name_or_path=None, device=device,

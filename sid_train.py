@@ -103,6 +103,8 @@ OPTIONS = [
     (('--metric_open_clip_path',), dict(type=str, default=None, help='CLIP model behind open_clipscore_30k: such a directory, or a pickled open_clip wrapper of the reference')),
     (('--metric_hps_path',), dict(type=str, default=None, metavar='FILE', help='Scorer behind hpsv2: HPS_v2_compressed.pt, or any checkpoint in open_clip\'s layout (.pt / .bin / .safetensors) (not a reference option)')),
     (('--metric_cmmd_clip_path',), dict(type=str, default=None, metavar='DIR', help='CLIP model behind cmmd30k_full / cmmd_test (ViT-L/14-336 in the published CMMD): a local directory in the Hugging Face layout, or random:clip-<arch> (not a reference option)')),
+    (('--metric_lpips_vgg',), dict(type=str, default=None, metavar='SPEC', help="LPIPS-VGG backbone behind lpipsdiv1k_full / lpipsdiv_test: a torch.save'd torchvision VGG16 state dict, or random:lpips-vgg[:seed] (not a reference option)")),
+    (('--metric_lpips_lin',), dict(type=str, default=None, metavar='SPEC', help="LPIPS lin weights behind lpipsdiv1k_full / lpipsdiv_test: the lpips package's vgg.pth, or random:lpips-vgg[:seed] (not a reference option)")),
     (('--hps_prompts',), dict(type=str, default=None, metavar='DIR', help='HPSv2 benchmark prompts: a directory with anime.json, concept-art.json, paintings.json, photo.json (not a reference option)')),
     (('--hps_arch',), dict(type=str, default=None, help='open_clip architecture of --metric_hps_path  [default: ViT-H-14] (not a reference option)')),
     (('--hps_tokenizer',), dict(type=str, default=None, metavar='DIR', help='vocab.json / merges.txt of the scorer  [default: <sd_model>/tokenizer] (not a reference option)')),
@@ -143,8 +145,9 @@ def build_config(o):
         hps = [m for m in o.metrics if m in _metrics.HPS_METRICS]      # scored by --metric_hps_path alone: no Inception file, no statistics
         cmmd = [m for m in o.metrics if m in _metrics.CMMD_METRICS]    # scored by --metric_cmmd_clip_path and the real images: likewise
         inception_score = [m for m in o.metrics if m in _metrics.IS_METRICS]      # the detector's class probabilities of the generated images: no statistics
-        need_stat = o.data_stat is not None or (len(needs_images) + len(hps) + len(inception_score) < len(o.metrics) and not has_images)
-        need_pt = len(hps) + len(cmmd) < len(o.metrics)
+        lpipsdiv = [m for m in o.metrics if m in _metrics.LPIPSDIV_METRICS]      # scored by --metric_lpips_vgg / --metric_lpips_lin alone: no Inception file, no statistics
+        need_stat = o.data_stat is not None or (len(needs_images) + len(hps) + len(inception_score) + len(lpipsdiv) < len(o.metrics) and not has_images)
+        need_pt = len(hps) + len(cmmd) + len(lpipsdiv) < len(o.metrics)
         for flag, path in ((('--metric_pt_path', o.metric_pt_path),) if need_pt else ()) + ((('--data_stat', o.data_stat),) if need_stat else ()):
             if flag == '--metric_pt_path' and _metrics.is_inception_spec(path):      # random:inception-v3[:seed], built by sid_lsg_amd.inception
                 continue
@@ -158,6 +161,15 @@ def build_config(o):
         if cmmd and not _metrics.is_clip_spec(o.get('metric_cmmd_clip_path')):
             raise click.ClickException(f'--metrics {",".join(cmmd)} needs --metric_cmmd_clip_path to be a local CLIP directory in the Hugging Face '
                                        f'layout or random:clip-<arch> (got {o.get("metric_cmmd_clip_path")!r})')
+        if lpipsdiv:
+            from sid_lsg_amd import fidelity as _fidelity
+            try:
+                _fidelity.check_specs(o.get('metric_lpips_vgg'), o.get('metric_lpips_lin'))
+                for flag in ('metric_lpips_vgg', 'metric_lpips_lin'):
+                    if not _fidelity.is_random_spec(o[flag]) and not os.path.isfile(o[flag]):
+                        raise ValueError(f'--{flag} {o[flag]!r}: not a local file')
+            except ValueError as e:
+                raise click.ClickException(f'--metrics {",".join(lpipsdiv)}: ' + str(e).replace('--lpips_', '--metric_lpips_'))
         if needs_images and not has_images:
             raise click.ClickException(f'--metrics {",".join(needs_images)} read the real images: --data must be a directory of images '
                                        f'with .txt captions (got {o.data!r})')
@@ -210,7 +222,7 @@ def build_config(o):
              metric_open_clip_path=o.metric_open_clip_path, metric_clip_path=o.metric_clip_path)
     if o.get('text_encoder') is not None:      # (absent when not given: load_sd15 then decides, and the printed options stay as they were)
         c.text_encoder = o.text_encoder
-    for k in ('metric_hps_path', 'hps_prompts', 'hps_arch', 'hps_tokenizer', 'metric_cmmd_clip_path'):      # (absent when not given, likewise)
+    for k in ('metric_hps_path', 'hps_prompts', 'hps_arch', 'hps_tokenizer', 'metric_cmmd_clip_path', 'metric_lpips_vgg', 'metric_lpips_lin'):      # (absent when not given, likewise)
         if o.get(k) is not None:
             c[k] = o[k]
     if teacher:      # (absent otherwise: the printed options of every other run stay as they were)

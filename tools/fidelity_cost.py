@@ -6,6 +6,10 @@
     square, weight, mean);
   * a full LPIPS-VGG pass in pairs / s, with its multiply-accumulate count.
     python tools/fidelity_cost.py [batch=8] [side=512]
+    python tools/fidelity_cost.py --diversity [side=512] [group=8]
+--diversity measures the all-pairs form instead (sid_lsg_amd.diversity; profiles/diversity.txt keeps a run): sidlsg_lpips_group_f32 on
+K maps against the paired launch on the gathered pair list at the five tap shapes, and HipLPIPS.group_pairs against HipLPIPS on the
+pair list of one group.
 Seeded inputs and weights.  Device events around windows of back-to-back calls after warm-up, five windows per variant, the variants
 alternating; median and range.  Nothing is asserted on the times (profiles/fidelity.txt keeps a run)."""
 import os
@@ -123,6 +127,56 @@ def main(batch=8, side=512):
               f'{2 * macs * batch / ms / 1e9:.1f} TFLOP/s fp32', flush=True)
 
 
+def diversity(side=512, group=8):
+    """--diversity: (a) sidlsg_lpips_group_f32 on K maps against sidlsg_lpips_layer_f32 on the gathered list of their K (K - 1) / 2
+    pairs (the gather itself is not timed), at the five tap shapes, K = 4, 8, 16; (b) HipLPIPS.group_pairs on one group against
+    HipLPIPS.__call__ on its pair list."""
+    from sid_lsg_amd import diversity as div
+    dev = torch.device('cuda:0')
+    print(f'device: {torch.cuda.get_device_name(0)}; all pairs of K maps, taps of {side} x {side}', flush=True)
+    g, gd = torch.Generator().manual_seed(0), torch.Generator(dev).manual_seed(0)
+    with torch.no_grad():
+        h = side
+        for C in fidelity.TAP_CHANNELS:
+            w = torch.rand(C, generator=g).to(dev) / C
+            for K in (4, 8, 16):
+                table = div.pair_index(K).to(dev)
+                step = min(table.shape[0], (fidelity.LIMIT - 1) // (2 * h * h * C * 4))      # pairs per paired launch: an operand stays below 2^31 bytes
+                F = torch.relu(torch.randn(K, h, h, C, generator=gd, device=dev))
+                lists = [torch.cat([F[table[s:s + step, 0]], F[table[s:s + step, 1]]]) for s in range(0, table.shape[0], step)]
+                paired = lambda: torch.cat([fidelity.lpips_layer_f32(p, w) for p in lists])  # noqa: E731
+                want = paired()
+                fits = K * (K - 1) // 2 * 128 + 2048 * K * ((C + 63) // 64) <= 65536           # the on-chip form's admitted set (sidlsg_hip.h)
+                forms = [('pairs on chip  ', 'chip')] * fits + [('pairs over grid', 'pairs')]
+                same = all(torch.equal(fidelity.lpips_group_f32(F, w, K, form=form).reshape(-1), want) for form in [f for _, f in forms] + [None])
+                t = report([(f'lpips_group on K maps, {name}   C {C:3d} {h:3d} x {h:3d} K {K:2d}', lambda form=form: fidelity.lpips_group_f32(F, w, K, form=form), 10)
+                            for name, form in forms]
+                           + [(f'lpips_layer, {len(lists):2d} launch(es) on the pairs  C {C:3d} {h:3d} x {h:3d} K {K:2d}', paired, 10)])
+                pick = 'on chip' if fits and (h * h + 127) // 128 >= 512 else 'over grid'
+                chip = f'on chip / paired {t[0] / t[-1]:.3f}' if fits else 'on chip: the copy of K vectors does not fit in LDS'
+                print(f'    {chip}; over grid / paired {t[-2] / t[-1]:.3f}; the library takes "{pick}" here; bit-equal: {same}', flush=True)
+                del F, lists
+            h //= 2
+        net = fidelity.HipLPIPS(*fidelity.random_state_dicts(0), dev)
+        x = torch.randint(0, 256, (group, 3, side, side), generator=g, dtype=torch.uint8).to(dev)
+        table = div.pair_index(group).to(dev)
+        a, b = x[table[:, 0]].contiguous(), x[table[:, 1]].contiguous()
+        same = torch.equal(net.group_pairs(x, group).reshape(-1), net(a, b))
+        t = report_ms([(f'group_pairs, one group of {group}', lambda: net.group_pairs(x, group), 1),
+                       (f'HipLPIPS on its {table.shape[0]} pairs', lambda: net(a, b), 1)])
+        print(f'    group_pairs / pair list {t[0] / t[1]:.3f} ({t[1] / t[0]:.2f} x; the multiply-accumulate counts give {group - 1} x); bit-equal: {same}', flush=True)
+
+
+def report_ms(variants):
+    samples = alternate(variants)
+    for name, v in samples.items():
+        print(line(name, v, 'ms', 1.0), flush=True)
+    return [statistics.median(samples[n]) for n, _, _ in variants]
+
+
 if __name__ == '__main__':
     args = sys.argv[1:]
-    main(int(args[0]) if args else 8, int(args[1]) if len(args) > 1 else 512)
+    if args and args[0] == '--diversity':
+        diversity(int(args[1]) if len(args) > 1 else 512, int(args[2]) if len(args) > 2 else 8)
+    else:
+        main(int(args[0]) if args else 8, int(args[1]) if len(args) > 1 else 512)
