@@ -52,6 +52,13 @@ per network on the fp32 masters, then the usual refresh of the compute copies): 
 one per file; negative allowed) scales them; 0 leaves weights equal (torch.equal) to those of a run without `--lora`.  The sampling loop is untouched, so it applies to
 snapshots and to `--network teacher` under every option above, and a LoRA run issues exactly the launches of the plain run per step.
 
+`--control_preprocess canny` makes the control images here: `--control_images` then holds photographs of any size, loaded by the rule
+of load_init_image (centre crop, LANCZOS resize), and their Canny edge map (sid_lsg_amd.edges.canny: OpenCV's Canny(img, 100, 200), the
+ControlNet annotator, on the device; `--canny_low` / `--canny_high`) is the hint.  `--control_adherence 1` scores every written image, as
+the uint8 that goes into its PNG: the Canny edges of the output against the edge set of its control image (any channel >= 128; for a
+preprocessed run the Canny map itself) -- precision, recall and F1 with `--edge_tolerance` pixels (default 1) -- into
+`<outdir>/control_adherence.json` (`options`, `per_image` keyed by PNG name, `mean`, micro-averaged).  Without the options nothing changes.
+
 `--fidelity 1` (with `--init_images`) compares every written image, as the uint8 that goes into its PNG, with the init image it started
 from (the crop load_init_image produced) on the device: PSNR and SSIM (sid_lsg_amd.fidelity, sidlsg_psnr_ssim_u8), and LPIPS-VGG when
 `--lpips_vgg SPEC --lpips_lin SPEC` name a torchvision VGG16 state dict and the lpips package's lin weights (or
@@ -79,6 +86,7 @@ import torch
 from sid_lsg_amd import distributed as dist
 from sid_lsg_amd import diversity as prompt_diversity
 from sid_lsg_amd.clip import load_clip_vision
+from sid_lsg_amd import edges as edge_maps
 from sid_lsg_amd.fidelity import aggregate as aggregate_fidelity
 from sid_lsg_amd.fidelity import check_specs as check_lpips_specs
 from sid_lsg_amd.fidelity import format_means, load_lpips, score_batch
@@ -315,6 +323,34 @@ def load_control_batch(files, indices, resolution):
     return np.stack([load_control_image(files[i % len(files)], resolution) for i in indices])
 
 
+def control_edge_options(controlnet, control_preprocess, canny_low, canny_high, control_adherence, edge_tolerance, resolution):
+    """-> None without the edge options, else (make the hints with Canny?, low, high, score the adherence?, tolerance); every inconsistent
+    option is refused by name, before a GPU is touched."""
+    given = [f for f, v in (('--control_preprocess', control_preprocess), ('--canny_low', canny_low), ('--canny_high', canny_high),
+                            ('--control_adherence', control_adherence or None), ('--edge_tolerance', edge_tolerance)) if v is not None]
+    if not given:
+        return None
+    if controlnet is None:
+        raise click.UsageError(f'{" / ".join(given)} apply to --controlnet only')
+    if control_preprocess is None and not control_adherence:
+        raise click.UsageError(f'{" / ".join(given)}: the Canny thresholds and the tolerance apply to --control_preprocess canny or --control_adherence 1')
+    if edge_tolerance is not None and not control_adherence:
+        raise click.UsageError('--edge_tolerance applies to --control_adherence 1 only')
+    low, high = 100 if canny_low is None else canny_low, 200 if canny_high is None else canny_high
+    tolerance = 1 if edge_tolerance is None else edge_tolerance
+    for flag, v in (('--canny_low', low), ('--canny_high', high), ('--edge_tolerance', tolerance)):
+        if v < 0:
+            raise click.UsageError(f'{flag} {v}: cannot be negative')
+    if low > high:
+        raise click.UsageError(f'--canny_low {low} is above --canny_high {high}')
+    if tolerance > edge_maps.MAX_TOLERANCE:
+        raise click.UsageError(f'--edge_tolerance {tolerance}: at most {edge_maps.MAX_TOLERANCE} pixels')
+    if edge_maps.hysteresis_lds_bytes(resolution, resolution) > edge_maps.HYST_LDS_MAX:
+        raise click.UsageError(f'--resolution {resolution}: the Canny hysteresis keeps both bit planes of an image on chip, '
+                               f'{edge_maps.hysteresis_lds_bytes(resolution, resolution)} bytes here against a limit of {edge_maps.HYST_LDS_MAX} (768 x 768)')
+    return control_preprocess is not None, low, high, bool(control_adherence), tolerance
+
+
 def list_ip_images(path):
     """The PNG / JPEG files of --ip_images, sorted by name."""
     if not os.path.isdir(path):
@@ -448,6 +484,11 @@ def ip_image_embeds(files, indices, tower, device):
 @click.option('--controlnet', type=str, default=None, metavar='SPEC', help='ControlNet: a local diffusers-layout directory, or random:controlnet[:seed]; needs --control_images')
 @click.option('--control_images', type=str, default=None, metavar='DIR', help='Control images, already --resolution square: PNG/JPEG files (sorted by name); sample idx uses file idx mod len(files)')
 @click.option('--control_scale', type=click.FloatRange(min=0), default=None, help='Scale of the ControlNet residuals  [default: 1]')
+@click.option('--control_preprocess', type=click.Choice(['canny']), default=None, help='--control_images holds photographs of any size: centre crop, LANCZOS resize, and their Canny edge map (made on the device) is the control image')
+@click.option('--canny_low', type=int, default=None, help='Lower Canny threshold of --control_preprocess / --control_adherence  [default: 100]')
+@click.option('--canny_high', type=int, default=None, help='Upper Canny threshold of --control_preprocess / --control_adherence  [default: 200]')
+@click.option('--control_adherence', type=bool, default=False, show_default=True, help='With --controlnet: precision / recall / F1 of the Canny edges of every written image against the edges of its control image -> <outdir>/control_adherence.json')
+@click.option('--edge_tolerance', type=int, default=None, help='With --control_adherence: an edge pixel is a hit within this many pixels (Chebyshev) of an edge of the other set  [default: 1]')
 @click.option('--ip_adapter', type=str, default=None, metavar='SPEC', help='IP-Adapter (image prompt): a local .safetensors / .bin file, or random:ip-adapter[:seed]; needs --ip_image_encoder and --ip_images')
 @click.option('--ip_image_encoder', type=str, default=None, metavar='DIR', help='CLIP image encoder of --ip_adapter: a local directory (config.json, model.safetensors), or random:clip-<arch>')
 @click.option('--ip_images', type=str, default=None, metavar='DIR', help='Prompt images of --ip_adapter, any size: PNG/JPEG files (sorted by name); sample idx uses file idx mod len(files)')
@@ -463,7 +504,8 @@ def ip_image_embeds(files, indices, tower, device):
 def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, init_timestep, text_prompts, repo_id, resolution, use_fp16,
          enable_compress_npz, num_steps_eval, custom_seed, teacher_steps, guidance_scale, init_images, strength, sample_posterior, text_encoder,
          teacher_sampler, teacher_spacing, teacher_eta, guidance_rescale, negative_prompt, mask_images, mask_composite, controlnet, control_images,
-         control_scale, ip_adapter, ip_image_encoder, ip_images, ip_scale, fidelity, lpips_vgg, lpips_lin, lora, lora_scale, seeds_per_prompt, diversity):
+         control_scale, ip_adapter, ip_image_encoder, ip_images, ip_scale, fidelity, lpips_vgg, lpips_lin, lora, lora_scale, seeds_per_prompt, diversity,
+         control_preprocess, canny_low, canny_high, control_adherence, edge_tolerance):
     text_encoder_kind = text_encoder
     if resolution % 8:
         raise click.BadParameter(f'{resolution}: must be a multiple of 8', param_hint='--resolution')
@@ -472,6 +514,7 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
     img2img = image_to_image_options(network_pkl, init_images, strength, sample_posterior, num_steps_eval, teacher_steps)
     masks = mask_options(init_images, mask_images, mask_composite, 0 if img2img is None else len(img2img[0]))
     control = control_options(controlnet, control_images, control_scale)
+    edge_opt = control_edge_options(controlnet, control_preprocess, canny_low, canny_high, control_adherence, edge_tolerance, resolution)
     ip = ip_options(ip_adapter, ip_image_encoder, ip_images, ip_scale)
     fid = fidelity_options(init_images, fidelity, lpips_vgg, lpips_lin, diversity)
     lora_opt = lora_options(lora, lora_scale)
@@ -515,6 +558,10 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
     if control is not None:
         control_net = load_controlnet(control[0], G_ema, device)
         dist.print0(f'ControlNet "{control[0]}": scale {control[2]:g}, {len(control[1])} control image(s) from "{control_images}"')
+        if edge_opt is not None:
+            adh_rows = {}
+            dist.print0(f'Canny {edge_opt[1]} / {edge_opt[2]}:' + (' control images made from the files of --control_images;' if edge_opt[0] else '')
+                        + (f' edge adherence with a tolerance of {edge_opt[4]} pixel(s)' if edge_opt[3] else ''))
     if ip is not None:
         ip_tower = load_clip_vision(ip[1], device, G_ema.compute_dtype)
         ip_net = load_ip_adapter(ip[0], G_ema, device, ip_tower.cfg.projection_dim)
@@ -555,7 +602,13 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
                 pixel_mask = load_mask_batch(masks[0], cond, resolution)
                 i2i['mask'] = torch.from_numpy(latent_mask(pixel_mask)).to(device)
         if control is not None:        # one conversion launch + the hint embedder, once per batch; the guided teacher batch is [uncond ; cond]
-            hints = torch.from_numpy(load_control_batch(control[1], cond, resolution)).to(device)
+            if edge_opt is not None and edge_opt[0]:      # photographs: the crop of load_init_image, then their Canny map, made on the device
+                control_edges = edge_maps.canny(torch.from_numpy(load_init_batch(control[1], cond, resolution)).to(device), edge_opt[1], edge_opt[2], rgb=True)
+                hints = control_edges.rgb_u8()
+            else:
+                hints = torch.from_numpy(load_control_batch(control[1], cond, resolution)).to(device)
+                if edge_opt is not None:
+                    control_edges = edge_maps.pack(hints)
             i2i['control'] = control_net.prepare(hints, scale=control[2], dup=2 if (teacher is not None and teacher[1] != 1) else 1)
         if ip is not None:             # the image tower, the projection and ONE k|v GEMM for all layers, once per batch
             i2i['ip'] = ip_net.prepare(ip_image_embeds(ip[2], cond, ip_tower, device), scale=ip[3],
@@ -585,6 +638,9 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
             rows = score_batch(pixels.permute(0, 3, 1, 2).contiguous(), torch.from_numpy(np.ascontiguousarray(arr)).to(device).permute(0, 3, 1, 2).contiguous(),
                                None if masks is None else torch.from_numpy(pixel_mask).to(device), lpips_net)
             fid_rows.update({f'{key:06d}.png': row for key, row in zip(batch, rows)})
+        if edge_opt is not None and edge_opt[3]:      # the uint8 that goes into the PNG: its Canny edges against the control image's edge set
+            rows = edge_maps.score_batch(control_edges, torch.from_numpy(np.ascontiguousarray(arr)).to(device), edge_opt[1], edge_opt[2], edge_opt[4])
+            adh_rows.update({f'{key:06d}.png': row for key, row in zip(batch, rows)})
         for key, img in zip(batch, arr):
             path = sample_path(outdir, subdirs, key)
             os.makedirs(os.path.dirname(path), exist_ok=True)
@@ -606,6 +662,22 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
             with open(os.path.join(outdir, 'fidelity.json'), 'w') as f:      # inf / nan are written as Infinity / NaN, which json.load reads back
                 json.dump(report, f, indent=1)
             dist.print0(f'Fidelity over {len(fid_rows)} images: {format_means(report["mean"])}')
+    if edge_opt is not None and edge_opt[3]:
+        if world > 1:
+            parts = [None] * world
+            torch.distributed.all_gather_object(parts, adh_rows)
+            adh_rows = {k: v for part in parts for k, v in part.items()}
+        if rank == 0:
+            adh_rows = dict(sorted(adh_rows.items()))
+            report = dict(options=dict(network=network_pkl, controlnet=controlnet, control_images=control_images, control_preprocess=control_preprocess,
+                                       control_scale=control[2], canny_low=edge_opt[1], canny_high=edge_opt[2], edge_tolerance=edge_opt[4],
+                                       resolution=resolution, init_timestep=init_timestep, num_steps_eval=num_steps_eval, teacher_steps=teacher_steps,
+                                       init_images=init_images, mask_images=mask_images, mask_composite=bool(mask_composite), ip_adapter=ip_adapter),
+                          per_image=adh_rows, mean=edge_maps.aggregate(adh_rows))
+            os.makedirs(outdir, exist_ok=True)
+            with open(os.path.join(outdir, 'control_adherence.json'), 'w') as f:      # nan is written as NaN, as fidelity.json writes it
+                json.dump(report, f, indent=1)
+            dist.print0(f'Control adherence over {edge_maps.format_means(report["mean"])}')
     if div is not None:            # after every file is written: group g is scored by rank g mod world from the files read back
         if world > 1:
             torch.distributed.barrier()

@@ -641,6 +641,46 @@ int sidlsg_vae_posterior(const float* moments, const float* qw, const float* qb,
  *   2^31 bytes; SIDLSG_EINVAL and no launch otherwise.  Every contraction of a ControlNet runs on the GEMM / conv entry points above. */
 int sidlsg_control_hint_u8(const void* images_u8, void* out, int B, int H, int W, int f32_out, void* stream);
 
+/* ---- Canny control maps and edge adherence (sid_lsg_amd/edges.py, csrc/canny.hip; the reference has no counterpart) -----------------
+ * Integer arithmetic throughout: every result is specified to the bit.  The rules restate OpenCV's Canny(img, low, high, apertureSize
+ * = 3, L2gradient = false) on a 3-channel 8-bit image, which with (100, 200) is ControlNet's Canny annotator.
+ * EDGE MAPS travel as BIT PLANES: uint32 [B][H][Wd], Wd = ceil(W / 32); pixel x is bit x % 32 (LSB first) of word x / 32; the padding
+ * bits of a row's last word are always WRITTEN as 0 and never trusted on input (they are masked where they could matter).
+ * Images are uint8 [B][H][W][3] (what a PNG holds and sidlsg_control_hint_u8 takes), B H W 3 < 2^31.
+ * sidlsg_canny_classify_u8: images + thresholds 0 <= low <= high -> planes cand and strong.  One launch: a 64 x 16 tile with a halo of
+ *   2 in LDS, one lane per pixel, the planes written from wave64 ballots (no byte map exists in memory).  Per pixel:
+ *     Sobel      per channel, 3 x 3: dx = (p[y-1][x+1] + 2 p[y][x+1] + p[y+1][x+1]) - (the same at x-1), dy = (p[y+1][x-1] + 2 p[y+1][x]
+ *                + p[y+1][x+1]) - (the same at y-1), in int32, the border REPLICATED.
+ *     channel    the pixel takes (dx, dy) of the channel with the largest |dx| + |dy|; on a tie the first in R, G, B order.
+ *     magnitude  m = |dx| + |dy| of that channel; m OUTSIDE the image is 0.
+ *     candidate  m > low, and with TG22 = 13573 (= int(0.41421356.. * 2^15 + 0.5)), ax = |dx|, ay = |dy| << 15, t22 = ax * TG22,
+ *                t67 = t22 + (ax << 16):
+ *                  ay < t22 (horizontal gradient):  m > m[y][x-1] && m >= m[y][x+1]
+ *                  ay > t67 (vertical):             m > m[y-1][x] && m >= m[y+1][x]
+ *                  else (diagonal), s = ((dx ^ dy) < 0) ? -1 : 1:  m > m[y-1][x-s] && m > m[y+1][x+s]
+ *                The > / >= asymmetry is part of the rule: it decides which pixel of a two-pixel plateau survives.
+ *     strong     cand && m > high.
+ *   SIDLSG_EINVAL, and no launch, for a NULL pointer, B, H or W < 1, low < 0 or low > high, 2^31 image bytes or more.
+ * sidlsg_edge_hysteresis: edges = the unique least fixed point of E = (strong & cand) | (cand & dilate3x3(E)), 8-connectivity: the
+ *   candidates connected to a strong candidate.  ONE WORKGROUP PER IMAGE with both planes in LDS (2 H Wd 4 bytes, at most 147456 = two
+ *   planes of 768 x 768; sidlsg_edge_hysteresis_lds_bytes(H, W) is the host query, negative beyond the limit).  A round is bit-parallel:
+ *   a word's horizontal dilation is two shifts with the carry bits of its neighbour words, the vertical one reads the rows above and
+ *   below, the new bits fill their runs of candidates inside the word, then one workgroup-wide OR of "changed".  The round loop is
+ *   uniform and capped at H W + 1 rounds (a productive round adds a pixel, so correct code cannot reach the cap); no host round trip,
+ *   no atomics.  edges: the plane; rgb_u8: uint8 [B][H][W][3], 255 in all three channels on an edge, else 0 (what a ControlNet takes);
+ *   either may be NULL, not both.  rounds: int [B] or NULL, the rounds run (the last, unproductive one included).  strong bits outside
+ *   cand are ignored.  SIDLSG_EINVAL, and no launch, for NULL cand / strong, both outputs NULL, B, H or W < 1, planes beyond the limit.
+ * sidlsg_edge_pack_u8: bit = any of the pixel's three channels >= threshold (0 .. 255): how a control image becomes an edge set.
+ * sidlsg_edge_match_counts: planes a, b, tolerance 0 <= r <= 16 -> counts int64 [B][4] = |a|, |b|, |a & D_r(b)|, |b & D_r(a)|, D_r =
+ *   r rounds of 3 x 3 dilation (Chebyshev distance <= r) CLIPPED to the image: nothing leaks from padding bits, across rows or across
+ *   images.  Popcounts, added by integer atomics (an integer sum has no order) into counts, which the call zeroes first; counts 8-byte
+ *   aligned.  SIDLSG_EINVAL, nothing launched and counts untouched, for NULL pointers, B, H or W < 1, r outside 0 .. 16. */
+int sidlsg_canny_classify_u8(const void* images_u8, void* cand, void* strong, int B, int H, int W, int low, int high, void* stream);
+int sidlsg_edge_hysteresis_lds_bytes(int H, int W);
+int sidlsg_edge_hysteresis(const void* cand, const void* strong, void* edges, void* rgb_u8, int* rounds, int B, int H, int W, void* stream);
+int sidlsg_edge_pack_u8(const void* images_u8, void* bits, int B, int H, int W, int threshold, void* stream);
+int sidlsg_edge_match_counts(const void* a, const void* b, void* counts, int B, int H, int W, int r, void* stream);
+
 /* ---- CLIP text encoder (sid_lsg_amd/text.py HipCLIPTextModel; transformers' CLIPTextModel, which the reference calls) ------------
  * sidlsg_attn_causal_fwd(_f32): O = softmax(mask(Q K^T D^-1/2)) V per head, key j visible to query i iff j <= i.  Forward only, no
  *   LSE.  Q/K/V/O: [B][N][ld*] views of bf16 (_f32: fp32) holding H heads of width D side by side (token stride ld* >= H * D, batch
