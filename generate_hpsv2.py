@@ -17,16 +17,15 @@ generate_onestep.py does.
 """
 import json
 import os
-import pickle
 
 import click
 import numpy as np
 import torch
 
-from generate_onestep import StackedRandomGenerator, parse_int_list, teacher_options
+from generate_onestep import StackedRandomGenerator, load_generator, parse_int_list, sample_images, teacher_options, to_uint8_nhwc
 from sid_lsg_amd import distributed as dist
 from sid_lsg_amd import hps
-from sid_lsg_amd.sd_util import TEACHER, TEACHER_CFG, TEACHER_STEPS, check_prediction_type, load_sd15, sid_sd_sampler, teacher_sample
+from sid_lsg_amd.sd_util import TEACHER, TEACHER_CFG, TEACHER_STEPS
 
 
 def resolve_scorer_options(repo_id, hps_prompts, hps_checkpoint, hps_tokenizer, hps_arch):
@@ -75,7 +74,6 @@ def check_seeds(seeds, prompts):
 @click.option('--score_only', is_flag=True, help='Score the JPEG files already in --outdir; generate nothing')
 def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, init_timestep, repo_id, resolution, num_steps_eval, text_encoder,
          teacher_steps, guidance_scale, hps_prompts, hps_checkpoint, hps_tokenizer, hps_arch, score_only):
-    text_encoder_kind = text_encoder
     if resolution % 8:
         raise click.BadParameter(f'{resolution}: must be a multiple of 8', param_hint='--resolution')
     if not score_only and not network_pkl:
@@ -93,18 +91,7 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
         rank_batches = torch.as_tensor(seeds).tensor_split(num_batches)[rank::world]
         if world > 1 and rank != 0:
             torch.distributed.barrier()                    # rank 0 touches the files first
-        if teacher is None:
-            dist.print0(f'Loading network from "{network_pkl}"...')
-            with open(network_pkl, 'rb') as f:
-                G_ema = pickle.load(f)['ema'].to(device)
-            G_ema.eval().requires_grad_(False)
-            _, vae, sched, text_encoder, tokenizer = load_sd15(repo_id, repo_id, device, torch.bfloat16, text_encoder=text_encoder_kind)
-            del _
-            check_prediction_type(G_ema, sched)
-        else:
-            dist.print0(f'Sampling the teacher "{repo_id}": DDIM {teacher[0]} steps, guidance scale {teacher[1]:g}')
-            G_ema, vae, sched, text_encoder, tokenizer = load_sd15(repo_id, repo_id, device, torch.bfloat16, text_encoder=text_encoder_kind)
-            G_ema.eval().requires_grad_(False)
+        net = load_generator(network_pkl, repo_id, device, text_encoder, teacher)
         if world > 1 and rank == 0:
             torch.distributed.barrier()
         lat = resolution // 8
@@ -117,25 +104,13 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
                     continue
                 batch_seeds = [int(s) for s in batch_seeds]
                 z = StackedRandomGenerator(device, batch_seeds).randn([len(batch_seeds), 4, lat, lat], device=device)
-                c = [all_prompts[style][s] for s in batch_seeds]
-                with torch.no_grad():
-                    if teacher is not None:
-                        images = teacher_sample(unet=G_ema, latents=z, contexts=c, noise_scheduler=sched, text_encoder=text_encoder,
-                                                tokenizer=tokenizer, resolution=resolution, guidance_scale=teacher[1],
-                                                num_inference_steps=teacher[0], return_images=True, vae=vae)
-                    else:
-                        images = sid_sd_sampler(unet=G_ema, latents=z, contexts=c,
-                                                init_timesteps=init_timestep * torch.ones(len(c), device=device, dtype=torch.long),
-                                                noise_scheduler=sched, text_encoder=text_encoder, tokenizer=tokenizer, resolution=resolution,
-                                                dtype=torch.bfloat16, return_images=True, vae=vae, num_steps=1, train_sampler=False,
-                                                num_steps_eval=num_steps_eval)
-                arr = (images.float() * 127.5 + 128).clip(0, 255).to(torch.uint8).permute(0, 2, 3, 1).cpu().numpy()
-                for seed, img in zip(batch_seeds, arr):
+                images = sample_images(net, z, [all_prompts[style][s] for s in batch_seeds], resolution, teacher, None, init_timestep, num_steps_eval)
+                for seed, img in zip(batch_seeds, to_uint8_nhwc(images)):
                     path = hps.image_path(outdir, style, seed, subdirs)
                     os.makedirs(os.path.dirname(path), exist_ok=True)
                     with open(path, 'wb') as f:
                         f.write(hps.jpeg_bytes(np.ascontiguousarray(img)))
-        del G_ema, vae, text_encoder
+        del net
         if world > 1:
             torch.distributed.barrier()
 

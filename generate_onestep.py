@@ -78,6 +78,8 @@ import math
 import os
 import pickle
 import re
+from types import SimpleNamespace
+from typing import NamedTuple
 
 import click
 import numpy as np
@@ -122,6 +124,18 @@ def read_prompts(path):
         return [line.strip() for line in f if line.strip()]
 
 
+# What the *_options functions below return (None when their options are not given): plain tuples with names, in the order of each docstring
+TeacherOpt = NamedTuple('TeacherOpt', [('steps', int), ('guidance_scale', float)])
+Img2ImgOpt = NamedTuple('Img2ImgOpt', [('files', list), ('start', int), ('sample_posterior', bool)])
+MaskOpt = NamedTuple('MaskOpt', [('files', list), ('composite', bool)])
+ControlOpt = NamedTuple('ControlOpt', [('spec', str), ('files', list), ('scale', float)])
+EdgeOpt = NamedTuple('EdgeOpt', [('preprocess', bool), ('low', int), ('high', int), ('adherence', bool), ('tolerance', int)])
+IpOpt = NamedTuple('IpOpt', [('adapter', str), ('image_encoder', str), ('files', list), ('scale', float)])
+LoraOpt = NamedTuple('LoraOpt', [('specs', list), ('scales', list)])
+FidelityOpt = NamedTuple('FidelityOpt', [('lpips_vgg', str), ('lpips_lin', str)])
+DiversityOpt = NamedTuple('DiversityOpt', [('lpips_vgg', str), ('lpips_lin', str), ('groups', dict)])
+
+
 def teacher_options(network_pkl, teacher_steps, guidance_scale):
     """-> (steps, guidance scale) when --network is the teacher sentinel, else None; the teacher's options with a snapshot are refused."""
     if network_pkl != TEACHER:
@@ -130,7 +144,7 @@ def teacher_options(network_pkl, teacher_steps, guidance_scale):
             raise click.UsageError(f'{" / ".join(given)} apply to --network {TEACHER} only: a distilled generator is sampled without guidance '
                                    'in --num_steps_eval steps')
         return None
-    return (TEACHER_STEPS if teacher_steps is None else teacher_steps), (TEACHER_CFG if guidance_scale is None else guidance_scale)
+    return TeacherOpt(TEACHER_STEPS if teacher_steps is None else teacher_steps, TEACHER_CFG if guidance_scale is None else guidance_scale)
 
 
 def teacher_solver_options(network_pkl, teacher_sampler=None, teacher_spacing=None, teacher_eta=None, guidance_rescale=None,
@@ -168,33 +182,51 @@ def strength_to_step(strength, num_steps):
     return min(max(num_steps - run, 0), num_steps - 1)
 
 
-def list_init_images(path):
-    """The PNG / JPEG files of a directory, sorted by name."""
+def image_files(path, flag, expect=None):
+    """The PNG / JPEG files of directory `path`, the value of option `flag`, sorted by name.  At least one, or with `expect` (the mask's
+    rule) exactly 1 or `expect` of them."""
     if not os.path.isdir(path):
-        raise click.UsageError(f'--init_images {path}: not a directory')
+        raise click.UsageError(f'{flag} {path}: not a directory')
     files = sorted(f for f in os.listdir(path) if f.lower().endswith(IMAGE_EXTENSIONS) and os.path.isfile(os.path.join(path, f)))
-    if not files:
-        raise click.UsageError(f'--init_images {path}: no PNG or JPEG files')
+    if expect is None and not files:
+        raise click.UsageError(f'{flag} {path}: no PNG or JPEG files')
+    if expect is not None and len(files) not in (1, expect):
+        raise click.UsageError(f'{flag} {path}: {len(files)} PNG or JPEG files, expected 1 or one per init image ({expect})')
     return [os.path.join(path, f) for f in files]
 
 
-def load_init_image(path, resolution):
-    """-> uint8 [resolution, resolution, 3]: RGB, centre-cropped to a square, resized with PIL's LANCZOS filter (on the host)."""
+def list_init_images(path):
+    """The PNG / JPEG files of a directory, sorted by name."""
+    return image_files(path, '--init_images')
+
+
+def _load_square(path, resolution, mode, resample):
+    """-> uint8 [resolution, resolution(, 3)]: converted to `mode`, centre-cropped to a square, resized with PIL's filter `resample`."""
     import PIL.Image
     with PIL.Image.open(path) as im:
-        im = im.convert('RGB')
+        im = im.convert(mode)
         w, h = im.size
         side = min(w, h)
         left, top = (w - side) // 2, (h - side) // 2
         im = im.crop((left, top, left + side, top + side))
         if side != resolution:
-            im = im.resize((resolution, resolution), PIL.Image.LANCZOS)
+            im = im.resize((resolution, resolution), getattr(PIL.Image, resample))
         return np.ascontiguousarray(np.asarray(im, dtype=np.uint8))
+
+
+def _batch(load, files, indices, resolution):
+    """Sample idx takes file idx % len(files) -> the stacked load(file, resolution)."""
+    return np.stack([load(files[i % len(files)], resolution) for i in indices])
+
+
+def load_init_image(path, resolution):
+    """-> uint8 [resolution, resolution, 3]: RGB, centre-cropped to a square, resized with PIL's LANCZOS filter (on the host)."""
+    return _load_square(path, resolution, 'RGB', 'LANCZOS')
 
 
 def load_init_batch(files, indices, resolution):
     """Sample idx takes file idx % len(files) -> uint8 [B, resolution, resolution, 3]."""
-    return np.stack([load_init_image(files[i % len(files)], resolution) for i in indices])
+    return _batch(load_init_image, files, indices, resolution)
 
 
 def init_image_options(network_pkl, init_images, strength, sample_posterior, num_steps_eval):
@@ -209,7 +241,7 @@ def init_image_options(network_pkl, init_images, strength, sample_posterior, num
     if num_steps_eval < 1:
         raise click.UsageError('--init_images needs --num_steps_eval >= 1')
     files = list_init_images(init_images)
-    return files, strength_to_step(1.0 if strength is None else strength, num_steps_eval), bool(sample_posterior)
+    return Img2ImgOpt(files, strength_to_step(1.0 if strength is None else strength, num_steps_eval), bool(sample_posterior))
 
 
 def teacher_init_image_options(init_images, strength, sample_posterior, teacher_steps):
@@ -222,7 +254,7 @@ def teacher_init_image_options(init_images, strength, sample_posterior, teacher_
         k = teacher_start_index(teacher_steps, strength)
     except ValueError as e:
         raise click.UsageError(f'--strength {strength:g} with --network {TEACHER}: {e}')
-    return list_init_images(init_images), k, bool(sample_posterior)
+    return Img2ImgOpt(list_init_images(init_images), k, bool(sample_posterior))
 
 
 def image_to_image_options(network_pkl, init_images, strength, sample_posterior, num_steps_eval, teacher_steps=None):
@@ -234,12 +266,7 @@ def image_to_image_options(network_pkl, init_images, strength, sample_posterior,
 
 def list_mask_images(path, num_init):
     """The PNG / JPEG files of --mask_images, sorted by name: one for all samples, or one per init image."""
-    if not os.path.isdir(path):
-        raise click.UsageError(f'--mask_images {path}: not a directory')
-    files = sorted(f for f in os.listdir(path) if f.lower().endswith(IMAGE_EXTENSIONS) and os.path.isfile(os.path.join(path, f)))
-    if len(files) not in (1, num_init):
-        raise click.UsageError(f'--mask_images {path}: {len(files)} PNG or JPEG files, expected 1 or one per init image ({num_init})')
-    return [os.path.join(path, f) for f in files]
+    return image_files(path, '--mask_images', expect=num_init)
 
 
 def mask_options(init_images, mask_images, mask_composite, num_init):
@@ -250,26 +277,17 @@ def mask_options(init_images, mask_images, mask_composite, num_init):
         return None
     if init_images is None:
         raise click.UsageError('--mask_images applies to --init_images only: the init image is the region that is kept')
-    return list_mask_images(mask_images, num_init), bool(mask_composite)
+    return MaskOpt(list_mask_images(mask_images, num_init), bool(mask_composite))
 
 
 def load_mask_image(path, resolution):
     """-> uint8 [resolution, resolution]: 'L', the centre crop of load_init_image, resized with PIL's NEAREST filter."""
-    import PIL.Image
-    with PIL.Image.open(path) as im:
-        im = im.convert('L')
-        w, h = im.size
-        side = min(w, h)
-        left, top = (w - side) // 2, (h - side) // 2
-        im = im.crop((left, top, left + side, top + side))
-        if side != resolution:
-            im = im.resize((resolution, resolution), PIL.Image.NEAREST)
-        return np.ascontiguousarray(np.asarray(im, dtype=np.uint8))
+    return _load_square(path, resolution, 'L', 'NEAREST')
 
 
 def load_mask_batch(files, indices, resolution):
     """Sample idx takes file idx % len(files) -> uint8 [B, resolution, resolution]."""
-    return np.stack([load_mask_image(files[i % len(files)], resolution) for i in indices])
+    return _batch(load_mask_image, files, indices, resolution)
 
 
 def latent_mask(pixel_mask):
@@ -285,12 +303,7 @@ def composite(generated, init_pixels, pixel_mask):
 
 def list_control_images(path):
     """The PNG / JPEG files of --control_images, sorted by name."""
-    if not os.path.isdir(path):
-        raise click.UsageError(f'--control_images {path}: not a directory')
-    files = sorted(f for f in os.listdir(path) if f.lower().endswith(IMAGE_EXTENSIONS) and os.path.isfile(os.path.join(path, f)))
-    if not files:
-        raise click.UsageError(f'--control_images {path}: no PNG or JPEG files')
-    return [os.path.join(path, f) for f in files]
+    return image_files(path, '--control_images')
 
 
 def control_options(controlnet, control_images, control_scale):
@@ -304,7 +317,7 @@ def control_options(controlnet, control_images, control_scale):
         raise click.UsageError('--control_images needs --controlnet (a ControlNet directory or random:controlnet[:seed])')
     if control_images is None:
         raise click.UsageError('--controlnet needs --control_images (the directory of control images)')
-    return controlnet, list_control_images(control_images), 1.0 if control_scale is None else float(control_scale)
+    return ControlOpt(controlnet, list_control_images(control_images), 1.0 if control_scale is None else float(control_scale))
 
 
 def load_control_image(path, resolution):
@@ -320,7 +333,7 @@ def load_control_image(path, resolution):
 
 def load_control_batch(files, indices, resolution):
     """Sample idx takes file idx % len(files) -> uint8 [B, resolution, resolution, 3]."""
-    return np.stack([load_control_image(files[i % len(files)], resolution) for i in indices])
+    return _batch(load_control_image, files, indices, resolution)
 
 
 def control_edge_options(controlnet, control_preprocess, canny_low, canny_high, control_adherence, edge_tolerance, resolution):
@@ -348,17 +361,12 @@ def control_edge_options(controlnet, control_preprocess, canny_low, canny_high, 
     if edge_maps.hysteresis_lds_bytes(resolution, resolution) > edge_maps.HYST_LDS_MAX:
         raise click.UsageError(f'--resolution {resolution}: the Canny hysteresis keeps both bit planes of an image on chip, '
                                f'{edge_maps.hysteresis_lds_bytes(resolution, resolution)} bytes here against a limit of {edge_maps.HYST_LDS_MAX} (768 x 768)')
-    return control_preprocess is not None, low, high, bool(control_adherence), tolerance
+    return EdgeOpt(control_preprocess is not None, low, high, bool(control_adherence), tolerance)
 
 
 def list_ip_images(path):
     """The PNG / JPEG files of --ip_images, sorted by name."""
-    if not os.path.isdir(path):
-        raise click.UsageError(f'--ip_images {path}: not a directory')
-    files = sorted(f for f in os.listdir(path) if f.lower().endswith(IMAGE_EXTENSIONS) and os.path.isfile(os.path.join(path, f)))
-    if not files:
-        raise click.UsageError(f'--ip_images {path}: no PNG or JPEG files')
-    return [os.path.join(path, f) for f in files]
+    return image_files(path, '--ip_images')
 
 
 def ip_options(ip_adapter, ip_image_encoder, ip_images, ip_scale):
@@ -374,7 +382,7 @@ def ip_options(ip_adapter, ip_image_encoder, ip_images, ip_scale):
         have = [k for k, v in given.items() if v is not None]
         raise click.UsageError(f'{" / ".join(have)} need{"s" if len(have) == 1 else ""} {" and ".join(missing)} (an IP-Adapter file or '
                                'random:ip-adapter[:seed], a CLIP image encoder directory or random:clip-<arch>, and the directory of prompt images)')
-    return ip_adapter, ip_image_encoder, list_ip_images(ip_images), 1.0 if ip_scale is None else float(ip_scale)
+    return IpOpt(ip_adapter, ip_image_encoder, list_ip_images(ip_images), 1.0 if ip_scale is None else float(ip_scale))
 
 
 def lora_options(lora, lora_scale):
@@ -384,7 +392,7 @@ def lora_options(lora, lora_scale):
         scales = lora_scales(len(lora or ()), lora_scale)
     except ValueError as e:
         raise click.UsageError(str(e))
-    return (list(lora), scales) if lora else None
+    return LoraOpt(list(lora), scales) if lora else None
 
 
 def fidelity_options(init_images, fidelity, lpips_vgg, lpips_lin, diversity=False):
@@ -401,7 +409,7 @@ def fidelity_options(init_images, fidelity, lpips_vgg, lpips_lin, diversity=Fals
             check_lpips_specs(lpips_vgg, lpips_lin)
         except ValueError as e:
             raise click.UsageError(str(e))
-    return lpips_vgg, lpips_lin
+    return FidelityOpt(lpips_vgg, lpips_lin)
 
 
 def diversity_options(diversity, seeds_per_prompt, lpips_vgg, lpips_lin, keys):
@@ -419,7 +427,7 @@ def diversity_options(diversity, seeds_per_prompt, lpips_vgg, lpips_lin, keys):
     if len(keys) % seeds_per_prompt:
         raise click.UsageError(f'--diversity: {len(keys)} samples (--seeds, --num) are not a multiple of --seeds_per_prompt {seeds_per_prompt}')
     try:
-        return lpips_vgg, lpips_lin, prompt_diversity.groups_of(keys, seeds_per_prompt)
+        return DiversityOpt(lpips_vgg, lpips_lin, prompt_diversity.groups_of(keys, seeds_per_prompt))
     except ValueError as e:
         raise click.UsageError(f'--diversity: {e}')
 
@@ -450,6 +458,141 @@ def ip_image_embeds(files, indices, tower, device):
     """Sample idx takes file idx % len(files) -> image embeddings [B, E] fp32; one tower call per image (the files may differ in size)."""
     with torch.no_grad():
         return torch.cat([tower(torch.from_numpy(load_ip_image(files[i % len(files)])).to(device)[None]).float() for i in indices])
+
+
+def write_report(rows, path, options, rows_key, aggregate, sort_key=None):
+    """This rank's `rows` merged with every other rank's and sorted by key (`sort_key`: the order of the keys, which are written as
+    strings) -> dict(options=, <rows_key>=, mean=aggregate(rows)) on every rank; rank 0 writes it to `path` with indent 1 (inf / nan
+    as Infinity / NaN, which json.load reads back), in a directory made if need be."""
+    if dist.get_world_size() > 1:
+        parts = [None] * dist.get_world_size()
+        torch.distributed.all_gather_object(parts, rows)
+        rows = {k: v for part in parts for k, v in part.items()}
+    rows = {str(k): rows[k] for k in sorted(rows, key=sort_key)}
+    report = {'options': options, rows_key: rows, 'mean': aggregate(rows)}
+    if dist.get_rank() == 0:
+        os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
+        with open(path, 'w') as f:
+            json.dump(report, f, indent=1)
+    return report
+
+
+Networks = NamedTuple('Networks', [('G_ema', object), ('vae', object), ('sched', object), ('text_encoder', object), ('tokenizer', object)])
+
+
+def load_generator(network_pkl, repo_id, device, text_encoder_kind, teacher, solver_kw=None):
+    """-> Networks(G_ema, vae, sched, text_encoder, tokenizer) of --repo_id; G_ema is the 'ema' of the snapshot pickle, or with `teacher`
+    (a TeacherOpt; `solver_kw`: teacher_solver_options') the UNet of --repo_id itself."""
+    if teacher is None:
+        dist.print0(f'Loading network from "{network_pkl}"...')
+        with open(network_pkl, 'rb') as f:
+            G_ema = pickle.load(f)['ema'].to(device)
+    elif solver_kw is None:
+        dist.print0(f'Sampling the teacher "{repo_id}": DDIM {teacher.steps} steps, guidance scale {teacher.guidance_scale:g}')
+    else:
+        dist.print0(f'Sampling the teacher "{repo_id}": {solver_kw["solver"]} {teacher.steps} steps, spacing {solver_kw["spacing"] or "of the model"}, '
+                    f'eta {solver_kw["eta"]:g}, guidance scale {teacher.guidance_scale:g}, rescale {solver_kw["guidance_rescale"]:g}')
+    unet, vae, sched, text_encoder, tokenizer = load_sd15(repo_id, repo_id, device, torch.bfloat16, text_encoder=text_encoder_kind)
+    if teacher is None:
+        del unet
+        check_prediction_type(G_ema, sched)       # a v snapshot with an epsilon --repo_id (or the reverse) would sample garbage
+    else:
+        G_ema = unet
+    G_ema.eval().requires_grad_(False)
+    return Networks(G_ema, vae, sched, text_encoder, tokenizer)
+
+
+def sample_images(net, z, prompts, resolution, teacher, solver_kw=None, init_timestep=None, num_steps_eval=1, randn=None, **conditions):
+    """The decoded images fp32 NCHW of latents z under `prompts`: the snapshot's sampler, or with `teacher` the DDIM loop, or with `solver_kw`
+    too the solver family (`randn`: its per-step noise).  `conditions`: the samplers' keywords, as build_conditions makes them."""
+    common = dict(unet=net.G_ema, latents=z, contexts=prompts, noise_scheduler=net.sched, text_encoder=net.text_encoder, tokenizer=net.tokenizer,
+                  resolution=resolution, return_images=True, vae=net.vae, **conditions)
+    with torch.no_grad():
+        if teacher is None:
+            return sid_sd_sampler(init_timesteps=init_timestep * torch.ones(len(z), device=z.device, dtype=torch.long), dtype=torch.bfloat16,
+                                  num_steps=1, train_sampler=False, num_steps_eval=num_steps_eval, **common)
+        common.update(guidance_scale=teacher.guidance_scale, num_inference_steps=teacher.steps)
+        if solver_kw is None:
+            return teacher_sample_i2i(**common)
+        kw = {k: v for k, v in solver_kw.items() if k != 'negative_prompt'}
+        neg = None if solver_kw['negative_prompt'] is None else [solver_kw['negative_prompt']] * len(z)
+        return teacher_sample_solver_i2i(negative_contexts=neg, randn=randn, **kw, **common)
+
+
+def to_uint8_nhwc(images):
+    """Images fp32 NCHW in [-1, 1] -> the uint8 [B, H, W, 3] array that is written: (img * 127.5 + 128).clip(0, 255)."""
+    return (images.float() * 127.5 + 128).clip(0, 255).to(torch.uint8).permute(0, 2, 3, 1).cpu().numpy()
+
+
+def load_models(o, network_pkl, repo_id, device, text_encoder_kind, num_steps_eval):
+    """What the resolved options `o` need, loaded once -> one namespace: net (load_generator's Networks, the LoRA files merged), and
+    vae_encoder, control_net, ip_tower, ip_net, lpips, each None where its option is absent."""
+    net = load_generator(network_pkl, repo_id, device, text_encoder_kind, o.teacher, o.solver)
+    m = SimpleNamespace(net=net, vae_encoder=None, control_net=None, ip_tower=None, ip_net=None, lpips=None)
+    if o.teacher is not None and num_steps_eval != 1:
+        dist.print0(f'Note: --num_steps_eval {num_steps_eval} is ignored with --network {TEACHER} (the step count is --teacher_steps)')
+    if o.lora is not None:           # merged once, before anything derives from the weights; the sampling loop does not change
+        load_lora(o.lora.specs, o.lora.scales, net.G_ema, net.text_encoder, log=dist.print0)
+    if o.img2img is not None:
+        m.vae_encoder = load_vae_encoder(repo_id, device)
+        dist.print0(f'Image-to-image: {len(o.img2img.files)} init images from "{o.dirs.init}", entering at step {o.img2img.start} of '
+                    f'{num_steps_eval if o.teacher is None else o.teacher.steps}')
+    if o.control is not None:
+        m.control_net = load_controlnet(o.control.spec, net.G_ema, device)
+        dist.print0(f'ControlNet "{o.control.spec}": scale {o.control.scale:g}, {len(o.control.files)} control image(s) from "{o.dirs.control}"')
+        if o.edge is not None:
+            dist.print0(f'Canny {o.edge.low} / {o.edge.high}:' + (' control images made from the files of --control_images;' if o.edge.preprocess else '')
+                        + (f' edge adherence with a tolerance of {o.edge.tolerance} pixel(s)' if o.edge.adherence else ''))
+    if o.ip is not None:
+        m.ip_tower = load_clip_vision(o.ip.image_encoder, device, net.G_ema.compute_dtype)
+        m.ip_net = load_ip_adapter(o.ip.adapter, net.G_ema, device, m.ip_tower.cfg.projection_dim)
+        dist.print0(f'IP-Adapter "{o.ip.adapter}": {m.ip_net.tokens} image tokens, scale {o.ip.scale:g}, image encoder "{o.ip.image_encoder}", '
+                    f'{len(o.ip.files)} prompt image(s) from "{o.dirs.ip}"')
+    if o.masks is not None:
+        dist.print0(f'Inpainting: {len(o.masks.files)} mask image(s) from "{o.dirs.mask}"' + (', kept pixels composited from the init images' if o.masks.composite else ''))
+    if o.fid is not None:
+        m.lpips = load_lpips(o.fid.lpips_vgg, o.fid.lpips_lin, device) if o.fid.lpips_vgg is not None else None
+        dist.print0('Fidelity against the init images: PSNR, SSIM' + (f', LPIPS-VGG "{o.fid.lpips_vgg}" / "{o.fid.lpips_lin}"' if m.lpips is not None else ''))
+    return m
+
+
+def build_conditions(o, m, rnd, cond, resolution, device):
+    """The conditioning of one batch, `cond` the index that selects each sample's files -> (the samplers' keywords init_latents, start_step or
+    start_index, mask, control, ip; the sources kept for compositing and scoring).  The posterior's eps is the second draw from `rnd`, after z."""
+    i2i, src = {}, SimpleNamespace(init_pixels=None, pixels=None, pixel_mask=None, control_edges=None)
+    dup = 2 if (o.teacher is not None and o.teacher.guidance_scale != 1) else 1          # the guided teacher batch is [uncond ; cond]
+    if o.img2img is not None:
+        src.init_pixels = load_init_batch(o.img2img.files, cond, resolution)
+        src.pixels = torch.from_numpy(src.init_pixels).to(device)
+        eps = rnd.randn([len(cond), 4, resolution // 8, resolution // 8], device=device) if o.img2img.sample_posterior else None
+        i2i = {'init_latents': m.vae_encoder.encode_latents(src.pixels, eps=eps), 'start_step' if o.teacher is None else 'start_index': o.img2img.start}
+        if o.masks is not None:
+            src.pixel_mask = load_mask_batch(o.masks.files, cond, resolution)
+            i2i['mask'] = torch.from_numpy(latent_mask(src.pixel_mask)).to(device)
+    if o.control is not None:        # one conversion launch + the hint embedder, once per batch
+        if o.edge is not None and o.edge.preprocess:      # photographs: the crop of load_init_image, then their Canny map, made on the device
+            src.control_edges = edge_maps.canny(torch.from_numpy(load_init_batch(o.control.files, cond, resolution)).to(device), o.edge.low, o.edge.high, rgb=True)
+            hints = src.control_edges.rgb_u8()
+        else:
+            hints = torch.from_numpy(load_control_batch(o.control.files, cond, resolution)).to(device)
+            if o.edge is not None:
+                src.control_edges = edge_maps.pack(hints)
+        i2i['control'] = m.control_net.prepare(hints, scale=o.control.scale, dup=dup)
+    if o.ip is not None:             # the image tower, the projection and ONE k|v GEMM for all layers, once per batch
+        i2i['ip'] = m.ip_net.prepare(ip_image_embeds(o.ip.files, cond, m.ip_tower, device), scale=o.ip.scale, dup=dup)
+    return i2i, src
+
+
+def score_written(o, m, src, arr, names, device, fid_rows, adh_rows):
+    """`arr`, the uint8 that goes into the PNG files `names`, scored on the device: against the crop load_init_image produced (--fidelity
+    -> fid_rows) and its Canny edges against the control image's edge set (--control_adherence -> adh_rows)."""
+    if o.fid is not None:
+        rows = score_batch(src.pixels.permute(0, 3, 1, 2).contiguous(), torch.from_numpy(np.ascontiguousarray(arr)).to(device).permute(0, 3, 1, 2).contiguous(),
+                           None if o.masks is None else torch.from_numpy(src.pixel_mask).to(device), m.lpips)
+        fid_rows.update(zip(names, rows))
+    if o.edge is not None and o.edge.adherence:
+        rows = edge_maps.score_batch(src.control_edges, torch.from_numpy(np.ascontiguousarray(arr)).to(device), o.edge.low, o.edge.high, o.edge.tolerance)
+        adh_rows.update(zip(names, rows))
 
 
 @click.command()
@@ -506,79 +649,38 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
          teacher_sampler, teacher_spacing, teacher_eta, guidance_rescale, negative_prompt, mask_images, mask_composite, controlnet, control_images,
          control_scale, ip_adapter, ip_image_encoder, ip_images, ip_scale, fidelity, lpips_vgg, lpips_lin, lora, lora_scale, seeds_per_prompt, diversity,
          control_preprocess, canny_low, canny_high, control_adherence, edge_tolerance):
-    text_encoder_kind = text_encoder
     if resolution % 8:
         raise click.BadParameter(f'{resolution}: must be a multiple of 8', param_hint='--resolution')
-    teacher = teacher_options(network_pkl, teacher_steps, guidance_scale)
-    solver_kw = teacher_solver_options(network_pkl, teacher_sampler, teacher_spacing, teacher_eta, guidance_rescale, negative_prompt)
-    img2img = image_to_image_options(network_pkl, init_images, strength, sample_posterior, num_steps_eval, teacher_steps)
-    masks = mask_options(init_images, mask_images, mask_composite, 0 if img2img is None else len(img2img[0]))
-    control = control_options(controlnet, control_images, control_scale)
-    edge_opt = control_edge_options(controlnet, control_preprocess, canny_low, canny_high, control_adherence, edge_tolerance, resolution)
-    ip = ip_options(ip_adapter, ip_image_encoder, ip_images, ip_scale)
-    fid = fidelity_options(init_images, fidelity, lpips_vgg, lpips_lin, diversity)
-    lora_opt = lora_options(lora, lora_scale)
-    div = diversity_options(diversity, seeds_per_prompt, lpips_vgg, lpips_lin,
-                            list(range(len(seeds[:num_fid_samples]))) if custom_seed else [int(s) for s in seeds[:num_fid_samples]])
+    seeds = seeds[:num_fid_samples]
+    # the options, resolved: every usage error comes from these lines, in this order, before a GPU is touched (dirs: as given, for the messages)
+    o = SimpleNamespace(dirs=SimpleNamespace(init=init_images, mask=mask_images, control=control_images, ip=ip_images))
+    o.teacher = teacher_options(network_pkl, teacher_steps, guidance_scale)
+    o.solver = teacher_solver_options(network_pkl, teacher_sampler, teacher_spacing, teacher_eta, guidance_rescale, negative_prompt)
+    o.img2img = image_to_image_options(network_pkl, init_images, strength, sample_posterior, num_steps_eval, teacher_steps)
+    o.masks = mask_options(init_images, mask_images, mask_composite, 0 if o.img2img is None else len(o.img2img.files))
+    o.control = control_options(controlnet, control_images, control_scale)
+    o.edge = control_edge_options(controlnet, control_preprocess, canny_low, canny_high, control_adherence, edge_tolerance, resolution)
+    o.ip = ip_options(ip_adapter, ip_image_encoder, ip_images, ip_scale)
+    o.fid = fidelity_options(init_images, fidelity, lpips_vgg, lpips_lin, diversity)
+    o.lora = lora_options(lora, lora_scale)
+    o.div = diversity_options(diversity, seeds_per_prompt, lpips_vgg, lpips_lin, list(range(len(seeds))) if custom_seed else [int(s) for s in seeds])
     dist.init()
     device = torch.device('cuda')
     rank, world = dist.get_rank(), dist.get_world_size()
     captions = read_prompts(text_prompts)
-    seeds = seeds[:num_fid_samples]
     num_batches = ((len(seeds) - 1) // (max_batch_size * world) + 1) * world
     index = torch.arange(len(seeds)) if custom_seed else torch.as_tensor(seeds)
     rank_batches = index.tensor_split(num_batches)[rank::world]
 
     if world > 1 and rank != 0:
         torch.distributed.barrier()                    # rank 0 touches the files first
-    if teacher is None:
-        dist.print0(f'Loading network from "{network_pkl}"...')
-        with open(network_pkl, 'rb') as f:
-            G_ema = pickle.load(f)['ema'].to(device)
-        G_ema.eval().requires_grad_(False)
-        _, vae, sched, text_encoder, tokenizer = load_sd15(repo_id, repo_id, device, torch.bfloat16, text_encoder=text_encoder_kind)
-        del _
-        check_prediction_type(G_ema, sched)       # a v snapshot with an epsilon --repo_id (or the reverse) would sample garbage
-    else:
-        if solver_kw is None:
-            dist.print0(f'Sampling the teacher "{repo_id}": DDIM {teacher[0]} steps, guidance scale {teacher[1]:g}')
-        else:
-            dist.print0(f'Sampling the teacher "{repo_id}": {solver_kw["solver"]} {teacher[0]} steps, spacing {solver_kw["spacing"] or "of the model"}, '
-                        f'eta {solver_kw["eta"]:g}, guidance scale {teacher[1]:g}, rescale {solver_kw["guidance_rescale"]:g}')
-        G_ema, vae, sched, text_encoder, tokenizer = load_sd15(repo_id, repo_id, device, torch.bfloat16, text_encoder=text_encoder_kind)
-        G_ema.eval().requires_grad_(False)
-        if num_steps_eval != 1:
-            dist.print0(f'Note: --num_steps_eval {num_steps_eval} is ignored with --network {TEACHER} (the step count is --teacher_steps)')
-    if lora_opt is not None:           # merged once, before anything derives from the weights; the sampling loop below does not change
-        load_lora(lora_opt[0], lora_opt[1], G_ema, text_encoder, log=dist.print0)
-    if img2img is not None:
-        vae_encoder = load_vae_encoder(repo_id, device)
-        dist.print0(f'Image-to-image: {len(img2img[0])} init images from "{init_images}", entering at step {img2img[1]} of '
-                    f'{num_steps_eval if teacher is None else teacher[0]}')
-    if control is not None:
-        control_net = load_controlnet(control[0], G_ema, device)
-        dist.print0(f'ControlNet "{control[0]}": scale {control[2]:g}, {len(control[1])} control image(s) from "{control_images}"')
-        if edge_opt is not None:
-            adh_rows = {}
-            dist.print0(f'Canny {edge_opt[1]} / {edge_opt[2]}:' + (' control images made from the files of --control_images;' if edge_opt[0] else '')
-                        + (f' edge adherence with a tolerance of {edge_opt[4]} pixel(s)' if edge_opt[3] else ''))
-    if ip is not None:
-        ip_tower = load_clip_vision(ip[1], device, G_ema.compute_dtype)
-        ip_net = load_ip_adapter(ip[0], G_ema, device, ip_tower.cfg.projection_dim)
-        dist.print0(f'IP-Adapter "{ip[0]}": {ip_net.tokens} image tokens, scale {ip[3]:g}, image encoder "{ip[1]}", {len(ip[2])} prompt image(s) '
-                    f'from "{ip_images}"')
-    if masks is not None:
-        dist.print0(f'Inpainting: {len(masks[0])} mask image(s) from "{mask_images}"' + (', kept pixels composited from the init images' if masks[1] else ''))
-    if fid is not None:
-        lpips_net = load_lpips(fid[0], fid[1], device) if fid[0] is not None else None
-        fid_rows = {}
-        dist.print0('Fidelity against the init images: PSNR, SSIM' + (f', LPIPS-VGG "{fid[0]}" / "{fid[1]}"' if lpips_net is not None else ''))
+    m = load_models(o, network_pkl, repo_id, device, text_encoder, num_steps_eval)
     if world > 1 and rank == 0:
         torch.distributed.barrier()
-    if teacher is None and num_steps_eval > 1:
+    if o.teacher is None and num_steps_eval > 1:
         outdir = f'{outdir}_numstep{num_steps_eval}'
 
-    lat = resolution // 8
+    fid_rows, adh_rows = {}, {}
     dist.print0(f'Generating {len(seeds)} images to "{outdir}"...')
     for batch in rank_batches:
         if world > 1:
@@ -586,121 +688,51 @@ def main(network_pkl, outdir, seeds, subdirs, max_batch_size, num_fid_samples, i
         if len(batch) == 0:
             continue
         batch = [int(b) for b in batch]
-        batch_seeds = [seeds[i] for i in batch] if custom_seed else batch
-        rnd = StackedRandomGenerator(device, batch_seeds)
-        z = rnd.randn([len(batch), 4, lat, lat], device=device)
+        rnd = StackedRandomGenerator(device, [seeds[i] for i in batch] if custom_seed else batch)
+        z = rnd.randn([len(batch), 4, resolution // 8, resolution // 8], device=device)
         cond = [i // seeds_per_prompt for i in batch]          # the index that selects a sample's condition; K = 1: the sample's own
-        prompts = [captions[i % len(captions)] for i in cond]
-        i2i = {}
-        if img2img is not None:
-            files, start_step, sample = img2img
-            init_pixels = load_init_batch(files, cond, resolution)
-            pixels = torch.from_numpy(init_pixels).to(device)
-            eps = rnd.randn([len(batch), 4, lat, lat], device=device) if sample else None
-            i2i = {'init_latents': vae_encoder.encode_latents(pixels, eps=eps), 'start_step' if teacher is None else 'start_index': start_step}
-            if masks is not None:
-                pixel_mask = load_mask_batch(masks[0], cond, resolution)
-                i2i['mask'] = torch.from_numpy(latent_mask(pixel_mask)).to(device)
-        if control is not None:        # one conversion launch + the hint embedder, once per batch; the guided teacher batch is [uncond ; cond]
-            if edge_opt is not None and edge_opt[0]:      # photographs: the crop of load_init_image, then their Canny map, made on the device
-                control_edges = edge_maps.canny(torch.from_numpy(load_init_batch(control[1], cond, resolution)).to(device), edge_opt[1], edge_opt[2], rgb=True)
-                hints = control_edges.rgb_u8()
-            else:
-                hints = torch.from_numpy(load_control_batch(control[1], cond, resolution)).to(device)
-                if edge_opt is not None:
-                    control_edges = edge_maps.pack(hints)
-            i2i['control'] = control_net.prepare(hints, scale=control[2], dup=2 if (teacher is not None and teacher[1] != 1) else 1)
-        if ip is not None:             # the image tower, the projection and ONE k|v GEMM for all layers, once per batch
-            i2i['ip'] = ip_net.prepare(ip_image_embeds(ip[2], cond, ip_tower, device), scale=ip[3],
-                                       dup=2 if (teacher is not None and teacher[1] != 1) else 1)
-        with torch.no_grad():
-            if teacher is not None and solver_kw is not None:
-                kw = {k: v for k, v in solver_kw.items() if k != 'negative_prompt'}
-                neg = None if solver_kw['negative_prompt'] is None else [solver_kw['negative_prompt']] * len(batch)
-                images = teacher_sample_solver_i2i(unet=G_ema, latents=z, contexts=prompts, noise_scheduler=sched, text_encoder=text_encoder,
-                                               tokenizer=tokenizer, resolution=resolution, guidance_scale=teacher[1],
-                                               num_inference_steps=teacher[0], return_images=True, vae=vae, negative_contexts=neg,
-                                               randn=lambda shape: rnd.randn(list(shape), device=device), **kw, **i2i)
-            elif teacher is not None:
-                images = teacher_sample_i2i(unet=G_ema, latents=z, contexts=prompts, noise_scheduler=sched, text_encoder=text_encoder,
-                                        tokenizer=tokenizer, resolution=resolution, guidance_scale=teacher[1],
-                                        num_inference_steps=teacher[0], return_images=True, vae=vae, **i2i)
-            else:
-                images = sid_sd_sampler(unet=G_ema, latents=z, contexts=prompts,
-                                        init_timesteps=init_timestep * torch.ones(len(batch), device=device, dtype=torch.long),
-                                        noise_scheduler=sched, text_encoder=text_encoder, tokenizer=tokenizer, resolution=resolution,
-                                        dtype=torch.bfloat16, return_images=True, vae=vae, num_steps=1, train_sampler=False,
-                                        num_steps_eval=num_steps_eval, **i2i)
-        arr = (images.float() * 127.5 + 128).clip(0, 255).to(torch.uint8).permute(0, 2, 3, 1).cpu().numpy()
-        if masks is not None and masks[1]:
-            arr = composite(arr, init_pixels, pixel_mask)
-        if fid is not None:            # the uint8 that goes into the PNG against the crop load_init_image produced, both on the device
-            rows = score_batch(pixels.permute(0, 3, 1, 2).contiguous(), torch.from_numpy(np.ascontiguousarray(arr)).to(device).permute(0, 3, 1, 2).contiguous(),
-                               None if masks is None else torch.from_numpy(pixel_mask).to(device), lpips_net)
-            fid_rows.update({f'{key:06d}.png': row for key, row in zip(batch, rows)})
-        if edge_opt is not None and edge_opt[3]:      # the uint8 that goes into the PNG: its Canny edges against the control image's edge set
-            rows = edge_maps.score_batch(control_edges, torch.from_numpy(np.ascontiguousarray(arr)).to(device), edge_opt[1], edge_opt[2], edge_opt[4])
-            adh_rows.update({f'{key:06d}.png': row for key, row in zip(batch, rows)})
+        i2i, src = build_conditions(o, m, rnd, cond, resolution, device)
+        images = sample_images(m.net, z, [captions[i % len(captions)] for i in cond], resolution, o.teacher, o.solver, init_timestep, num_steps_eval,
+                               randn=lambda shape: rnd.randn(list(shape), device=device), **i2i)
+        arr = to_uint8_nhwc(images)
+        if o.masks is not None and o.masks.composite:
+            arr = composite(arr, src.init_pixels, src.pixel_mask)
+        score_written(o, m, src, arr, [f'{key:06d}.png' for key in batch], device, fid_rows, adh_rows)
         for key, img in zip(batch, arr):
             path = sample_path(outdir, subdirs, key)
             os.makedirs(os.path.dirname(path), exist_ok=True)
             save_png(path, np.ascontiguousarray(img))
         if enable_compress_npz:
             np.savez_compressed(os.path.join(outdir, f'images_{batch[0]:06d}.npz'), images=arr)
-    if fid is not None:
-        if world > 1:
-            parts = [None] * world
-            torch.distributed.all_gather_object(parts, fid_rows)
-            fid_rows = {k: v for part in parts for k, v in part.items()}
-        if rank == 0:
-            fid_rows = dict(sorted(fid_rows.items()))
-            report = dict(options=dict(network=network_pkl, init_images=init_images, mask_images=mask_images, mask_composite=bool(mask_composite),
-                                       strength=strength, init_timestep=init_timestep, num_steps_eval=num_steps_eval, resolution=resolution,
-                                       teacher_steps=teacher_steps, controlnet=controlnet, ip_adapter=ip_adapter, lpips_vgg=fid[0], lpips_lin=fid[1]),
-                          per_image=fid_rows, mean=aggregate_fidelity(fid_rows))
-            os.makedirs(outdir, exist_ok=True)
-            with open(os.path.join(outdir, 'fidelity.json'), 'w') as f:      # inf / nan are written as Infinity / NaN, which json.load reads back
-                json.dump(report, f, indent=1)
-            dist.print0(f'Fidelity over {len(fid_rows)} images: {format_means(report["mean"])}')
-    if edge_opt is not None and edge_opt[3]:
-        if world > 1:
-            parts = [None] * world
-            torch.distributed.all_gather_object(parts, adh_rows)
-            adh_rows = {k: v for part in parts for k, v in part.items()}
-        if rank == 0:
-            adh_rows = dict(sorted(adh_rows.items()))
-            report = dict(options=dict(network=network_pkl, controlnet=controlnet, control_images=control_images, control_preprocess=control_preprocess,
-                                       control_scale=control[2], canny_low=edge_opt[1], canny_high=edge_opt[2], edge_tolerance=edge_opt[4],
-                                       resolution=resolution, init_timestep=init_timestep, num_steps_eval=num_steps_eval, teacher_steps=teacher_steps,
-                                       init_images=init_images, mask_images=mask_images, mask_composite=bool(mask_composite), ip_adapter=ip_adapter),
-                          per_image=adh_rows, mean=edge_maps.aggregate(adh_rows))
-            os.makedirs(outdir, exist_ok=True)
-            with open(os.path.join(outdir, 'control_adherence.json'), 'w') as f:      # nan is written as NaN, as fidelity.json writes it
-                json.dump(report, f, indent=1)
-            dist.print0(f'Control adherence over {edge_maps.format_means(report["mean"])}')
-    if div is not None:            # after every file is written: group g is scored by rank g mod world from the files read back
+    if o.fid is not None:
+        report = write_report(fid_rows, os.path.join(outdir, 'fidelity.json'),
+                              dict(network=network_pkl, init_images=init_images, mask_images=mask_images, mask_composite=bool(mask_composite),
+                                   strength=strength, init_timestep=init_timestep, num_steps_eval=num_steps_eval, resolution=resolution,
+                                   teacher_steps=teacher_steps, controlnet=controlnet, ip_adapter=ip_adapter, lpips_vgg=o.fid.lpips_vgg,
+                                   lpips_lin=o.fid.lpips_lin), 'per_image', aggregate_fidelity)
+        dist.print0(f'Fidelity over {len(report["per_image"])} images: {format_means(report["mean"])}')
+    if o.edge is not None and o.edge.adherence:
+        report = write_report(adh_rows, os.path.join(outdir, 'control_adherence.json'),
+                              dict(network=network_pkl, controlnet=controlnet, control_images=control_images, control_preprocess=control_preprocess,
+                                   control_scale=o.control.scale, canny_low=o.edge.low, canny_high=o.edge.high, edge_tolerance=o.edge.tolerance,
+                                   resolution=resolution, init_timestep=init_timestep, num_steps_eval=num_steps_eval, teacher_steps=teacher_steps,
+                                   init_images=init_images, mask_images=mask_images, mask_composite=bool(mask_composite), ip_adapter=ip_adapter),
+                              'per_image', edge_maps.aggregate)
+        dist.print0(f'Control adherence over {edge_maps.format_means(report["mean"])}')
+    if o.div is not None:            # after every file is written: group g is scored by rank g mod world from the files read back
         if world > 1:
             torch.distributed.barrier()
-        lpips_div = load_lpips(div[0], div[1], device)
-        div_rows = {}
-        for n, (g, keys) in enumerate(div[2].items()):
+        lpips_div, div_rows = load_lpips(o.div.lpips_vgg, o.div.lpips_lin, device), {}
+        for n, (g, keys) in enumerate(o.div.groups.items()):
             if n % world == rank:
                 row = prompt_diversity.score_groups(load_png_group([sample_path(outdir, subdirs, k) for k in keys], device), seeds_per_prompt, lpips_div)[0]
                 div_rows[g] = dict(prompt=captions[g % len(captions)], files=[f'{k:06d}.png' for k in keys], **row)
-        if world > 1:
-            parts = [None] * world
-            torch.distributed.all_gather_object(parts, div_rows)
-            div_rows = {k: v for part in parts for k, v in part.items()}
-        if rank == 0:
-            div_rows = {str(g): div_rows[g] for g in sorted(div_rows)}
-            report = dict(options=dict(network=network_pkl, seeds_per_prompt=seeds_per_prompt, text_prompts=text_prompts, resolution=resolution,
-                                       init_timestep=init_timestep, num_steps_eval=num_steps_eval, teacher_steps=teacher_steps,
-                                       guidance_scale=guidance_scale, init_images=init_images, controlnet=controlnet, ip_adapter=ip_adapter,
-                                       lpips_vgg=div[0], lpips_lin=div[1]),
-                          per_prompt=div_rows, mean=prompt_diversity.aggregate(div_rows))
-            with open(os.path.join(outdir, 'diversity.json'), 'w') as f:
-                json.dump(report, f, indent=1)
-            dist.print0(f'Diversity over {prompt_diversity.format_means(report["mean"])}')
+        report = write_report(div_rows, os.path.join(outdir, 'diversity.json'),
+                              dict(network=network_pkl, seeds_per_prompt=seeds_per_prompt, text_prompts=text_prompts, resolution=resolution,
+                                   init_timestep=init_timestep, num_steps_eval=num_steps_eval, teacher_steps=teacher_steps,
+                                   guidance_scale=guidance_scale, init_images=init_images, controlnet=controlnet, ip_adapter=ip_adapter,
+                                   lpips_vgg=o.div.lpips_vgg, lpips_lin=o.div.lpips_lin), 'per_prompt', prompt_diversity.aggregate)
+        dist.print0(f'Diversity over {prompt_diversity.format_means(report["mean"])}')
     if world > 1:
         torch.distributed.barrier()
     dist.print0('Done.')

@@ -449,12 +449,15 @@ def sid_sd_sampler(unet, latents, contexts, init_timesteps, noise_scheduler, tex
                 D_x = hip_generate(unet, noise.to(torch.float32).contiguous(), emb, t_i.contiguous(), noise_scheduler, x0=D_x, control=control, ip=ip)
                 if mask is not None:
                     D_x = ops.masked_renoise(D_x, z0, mask, want_input=False, inplace=True)[1]
-    if not return_images:
-        return D_x.to(torch.float32)
+    return decode_latents(vae, D_x) if return_images else D_x.to(torch.float32)
+
+
+def decode_latents(vae, x):
+    """Scaled latents -> images fp32: vae.decode(x / scaling_factor), a float16 VAE with force_upcast run in float32 for the call."""
     upcast = vae.dtype == torch.float16 and getattr(vae.config, 'force_upcast', False)
     if upcast:
         vae.to(dtype=torch.float32)
-    images = vae.decode(D_x.to(vae.dtype) / vae.config.scaling_factor, return_dict=False)[0]
+    images = vae.decode(x.to(vae.dtype) / vae.config.scaling_factor, return_dict=False)[0]
     if upcast:
         vae.to(dtype=torch.float16)
     return images.to(torch.float32)
@@ -528,6 +531,56 @@ def sampling_config_of(noise_scheduler, schedule_config=None):
     return SD_SAMPLING_CONFIG if found is None else found
 
 
+def _teacher_loop(who, plan, unet, latents, contexts, negative_contexts, noise_scheduler, text_encoder, tokenizer, guidance_scale, return_images,
+                  vae, init_latents, start_index, mask, control, ip):
+    """The loop under teacher_sample_i2i and teacher_sample_solver_i2i.  `plan(z, compute dtype, prediction type, entry)` is the sampler's
+    part: it builds its tables on z's device, calls `entry(n)` (_teacher_entry) once, and returns (what entry returned, ts [n], s0 [n, b],
+    s1 [n, b], step, renoise) with `step(i, eps, x_t, last) -> (next network input, x_prev)` the boundary launch(es) of step i and
+    `renoise(i) -> (a0, a1)` the level to which a mask re-noises the known region after step i.  Pinned by tests and by the files written:
+      * launches: one noisy_input; per step one forward_nhwc, then the boundary (ddim_step; or cfg_rescale_stats where guided and phi != 0,
+        then solver_step), then with a mask one masked_renoise (after the last step with want_input=False: z0 itself);
+      * random draws: the solver boundary calls randn once per step whose c_n is non-zero, in step order, and never otherwise;
+      * table casts: the DDIM plan casts its tables with .to(torch.float32) before the expand to [n, b], the solver plan does not;
+      * last flag: the boundary gets last = (last step) or (mask given); start: noisy_input(None, z, ones, ones) unless `noised`;
+      * error precedence: guidance_rescale's range, then _teacher_entry with int(num_inference_steps), then the schedule (solver); the
+        schedule, then _teacher_entry with ts.numel() (DDIM); the length of negative_contexts after either; `who` names the public sampler."""
+    _require_hip(unet)
+    check_prediction_type(unet, noise_scheduler)
+    net = _unwrap(unet)
+    dt = net.compute_dtype
+    with torch.no_grad():
+        z = latents.to(torch.float32).contiguous()
+        b, dev = z.shape[0], z.device
+        (z0, mask, noised), ts, s0, s1, step, renoise = plan(z, dt, noise_scheduler.config.prediction_type,
+                                                             lambda n: _teacher_entry(z, init_latents, start_index, mask, n, who))
+        n = ts.numel()
+        guided = guidance_scale != 1
+        dup = 2 if guided else 1
+        if negative_contexts is not None and not torch.is_tensor(negative_contexts) and len(negative_contexts) != b:
+            raise ValueError(f'negative_contexts: {len(negative_contexts)} prompts for a batch of {b}')
+        ctx = encode_contexts(contexts, text_encoder, tokenizer, dev).to(dt)
+        if guided:
+            neg = [''] * b if negative_contexts is None else negative_contexts
+            ctx = torch.cat([encode_contexts(neg, text_encoder, tokenizer, dev).to(dt), ctx])
+        ctx = ctx.contiguous()
+        tt = ts[:, None].expand(n, dup * b).contiguous()
+        ones = torch.ones(b, device=dev, dtype=torch.float32)
+        if noised:
+            xin, xt = ops.noisy_input(z0, z, s0[start_index], s1[start_index], dup, dt)      # x_{t_k} = alpha_k z0 + sigma_k z
+        else:
+            xin, xt = ops.noisy_input(None, z, ones, ones, dup, dt)      # x_T = z, as the [uncond ; cond] NHWC batch
+        for i in range(start_index, n):
+            eps = net.forward_nhwc(xin, tt[i], ctx, control=control, ip=ip)
+            last = i == n - 1
+            xin, xt = step(i, eps, xt, last or mask is not None)
+            if mask is not None and last:
+                xt = ops.masked_renoise(xt, z0, mask, want_input=False, inplace=True)[1]
+            elif mask is not None:
+                a0, a1 = renoise(i)
+                xin, xt = ops.masked_renoise(xt, z0, mask, noise=z, a0=a0, a1=a1, dup=dup, act_dtype=dt, inplace=True)
+        return decode_latents(vae, xt) if return_images else xt
+
+
 def teacher_sample(unet, latents, contexts, noise_scheduler, text_encoder, tokenizer, resolution, guidance_scale=TEACHER_CFG,
                    num_inference_steps=TEACHER_STEPS, return_images=False, vae=None, schedule_config=None):
     """teacher_sample_i2i from pure noise: the text-to-image teacher row, under the signature it has always had."""
@@ -557,48 +610,16 @@ def teacher_sample_i2i(unet, latents, contexts, noise_scheduler, text_encoder, t
     ip: an ip_adapter.IPState (HipIPAdapter.prepare(image_embeds, scale, dup=2 with guidance, else 1)), passed to every UNet call; it
     composes with control and with the image-to-image arguments in the same way.
     -> the final latent x_0 fp32 NCHW, or (return_images) the decoded images as sid_sd_sampler returns them."""
-    _require_hip(unet)
-    check_prediction_type(unet, noise_scheduler)
-    net = _unwrap(unet)
-    dt, pt = net.compute_dtype, noise_scheduler.config.prediction_type
-    schedule_config = sampling_config_of(noise_scheduler, schedule_config)
-    with torch.no_grad():
-        z = latents.to(torch.float32).contiguous()
-        b, dev = z.shape[0], z.device
-        ts, s0, s1, s0p, s1p = (v.to(dev) for v in ddim_schedule(noise_scheduler, schedule_config, num_inference_steps))
-        n = ts.numel()
-        z0, mask, noised = _teacher_entry(z, init_latents, start_index, mask, n, 'teacher_sample_i2i')
-        guided = guidance_scale != 1
-        dup = 2 if guided else 1
-        ctx = encode_contexts(contexts, text_encoder, tokenizer, dev).to(dt)
-        if guided:
-            ctx = torch.cat([encode_contexts([''] * b, text_encoder, tokenizer, dev).to(dt), ctx])
-        ctx = ctx.contiguous()
-        tt = ts[:, None].expand(n, dup * b).contiguous()
-        s0, s1, s0p, s1p = (v.to(torch.float32)[:, None].expand(n, b).contiguous() for v in (s0, s1, s0p, s1p))
-        ones = torch.ones(b, device=dev, dtype=torch.float32)
-        if noised:
-            xin, xt = ops.noisy_input(z0, z, s0[start_index], s1[start_index], dup, dt)      # x_{t_k} = alpha_k z0 + sigma_k z
-        else:
-            xin, xt = ops.noisy_input(None, z, ones, ones, dup, dt)      # x_T = z, as the [uncond ; cond] NHWC batch
-        for i in range(start_index, n):
-            eps = net.forward_nhwc(xin, tt[i], ctx, control=control, ip=ip)
-            last = i == n - 1
-            xin, xt, _ = ops.ddim_step(eps, xt, s0[i], s1[i], s0p[i], s1p[i], guidance_scale, dt, prediction_type=pt,
-                                       last=last or mask is not None)
-            if mask is not None and last:
-                xt = ops.masked_renoise(xt, z0, mask, want_input=False, inplace=True)[1]
-            elif mask is not None:
-                xin, xt = ops.masked_renoise(xt, z0, mask, noise=z, a0=s0p[i], a1=s1p[i], dup=dup, act_dtype=dt, inplace=True)
-        if not return_images:
-            return xt
-        upcast = vae.dtype == torch.float16 and getattr(vae.config, 'force_upcast', False)
-        if upcast:
-            vae.to(dtype=torch.float32)
-        images = vae.decode(xt.to(vae.dtype) / vae.config.scaling_factor, return_dict=False)[0]
-        if upcast:
-            vae.to(dtype=torch.float16)
-        return images.to(torch.float32)
+    def plan(z, dt, pt, entry):
+        ts, *tables = (v.to(z.device) for v in ddim_schedule(noise_scheduler, sampling_config_of(noise_scheduler, schedule_config), num_inference_steps))
+        start = entry(ts.numel())
+        s0, s1, s0p, s1p = (v.to(torch.float32)[:, None].expand(ts.numel(), z.shape[0]).contiguous() for v in tables)
+
+        def step(i, eps, xt, last):
+            return ops.ddim_step(eps, xt, s0[i], s1[i], s0p[i], s1p[i], guidance_scale, dt, prediction_type=pt, last=last)[:2]
+        return start, ts, s0, s1, step, lambda i: (s0p[i], s1p[i])          # the mask re-noises to the level step i has just reached
+    return _teacher_loop('teacher_sample_i2i', plan, unet, latents, contexts, None, noise_scheduler, text_encoder, tokenizer, guidance_scale,
+                         return_images, vae, init_latents, start_index, mask, control, ip)
 
 
 def teacher_sample_solver(unet, latents, contexts, noise_scheduler, text_encoder, tokenizer, resolution, guidance_scale=TEACHER_CFG,
@@ -628,62 +649,29 @@ def teacher_sample_solver_i2i(unet, latents, contexts, noise_scheduler, text_enc
     region to the level of t_{i+1}, known = s0[i+1]*z0 + s1[i+1]*latents (after the last step: z0), and leaves the x0 history alone.
     control: a controlnet.ControlState, ip: an ip_adapter.IPState, as in teacher_sample_i2i.
     -> the final latent x_0 fp32 NCHW, or (return_images) the decoded images as sid_sd_sampler returns them."""
-    _require_hip(unet)
-    check_prediction_type(unet, noise_scheduler)
-    net = _unwrap(unet)
-    dt, pt = net.compute_dtype, noise_scheduler.config.prediction_type
-    schedule_config = sampling_config_of(noise_scheduler, schedule_config)
-    phi = float(guidance_rescale)
-    if not 0 <= phi <= 1:
-        raise ValueError(f'guidance_rescale={guidance_rescale}: expected a value in [0, 1]')
-    with torch.no_grad():
-        z = latents.to(torch.float32).contiguous()
-        b, dev = z.shape[0], z.device
-        z0, mask, noised = _teacher_entry(z, init_latents, start_index, mask, int(num_inference_steps), 'teacher_sample_solver_i2i')
-        ts, s0, s1, coef = solver_schedule(noise_scheduler, schedule_config, num_inference_steps, solver=solver, spacing=spacing, eta=eta,
-                                           start=start_index)
+    def plan(z, dt, pt, entry):
+        phi = float(guidance_rescale)
+        if not 0 <= phi <= 1:
+            raise ValueError(f'guidance_rescale={guidance_rescale}: expected a value in [0, 1]')
+        start = entry(int(num_inference_steps))
+        ts, s0, s1, coef = solver_schedule(noise_scheduler, sampling_config_of(noise_scheduler, schedule_config), num_inference_steps, solver=solver,
+                                           spacing=spacing, eta=eta, start=start_index)
         flags = (coef.cpu() != 0).tolist()          # per step: which terms exist (read before the loop; the loop itself reads nothing back)
-        ts, s0, s1, coef = (v.to(dev) for v in (ts, s0, s1, coef))
-        n = ts.numel()
-        guided = guidance_scale != 1
-        dup = 2 if guided else 1
-        if negative_contexts is not None and not torch.is_tensor(negative_contexts) and len(negative_contexts) != b:
-            raise ValueError(f'negative_contexts: {len(negative_contexts)} prompts for a batch of {b}')
-        ctx = encode_contexts(contexts, text_encoder, tokenizer, dev).to(dt)
-        if guided:
-            neg = [''] * b if negative_contexts is None else negative_contexts
-            ctx = torch.cat([encode_contexts(neg, text_encoder, tokenizer, dev).to(dt), ctx])
-        ctx = ctx.contiguous()
-        if randn is None:
-            randn = lambda shape: torch.randn(shape, device=dev, dtype=torch.float32)  # noqa: E731
-        tt = ts[:, None].expand(n, dup * b).contiguous()
-        s0, s1 = (v[:, None].expand(n, b).contiguous() for v in (s0, s1))
-        coef = coef[:, None, :].expand(n, b, 4).contiguous()
-        ones = torch.ones(b, device=dev, dtype=torch.float32)
-        if noised:
-            xin, xt = ops.noisy_input(z0, z, s0[start_index], s1[start_index], dup, dt)      # x_{t_k} = alpha_k z0 + sigma_k z
-        else:
-            xin, xt = ops.noisy_input(None, z, ones, ones, dup, dt)      # x_T = z, as the [uncond ; cond] NHWC batch
-        history = [torch.empty_like(z), torch.empty_like(z)]
+        ts, s0, s1, coef = (v.to(z.device) for v in (ts, s0, s1, coef))
+        s0, s1 = (v[:, None].expand(ts.numel(), z.shape[0]).contiguous() for v in (s0, s1))
+        coef = coef[:, None, :].expand(ts.numel(), z.shape[0], 4).contiguous()
+        draw = randn if randn is not None else lambda shape: torch.randn(shape, device=z.device, dtype=torch.float32)
+        history = [torch.empty_like(z), torch.empty_like(z)]          # the two x0 buffers, swapped per step
         x0_prev = None
-        for i in range(start_index, n):
-            eps = net.forward_nhwc(xin, tt[i], ctx, control=control, ip=ip)
-            scale = ops.cfg_rescale_stats(eps, z.shape[1], guidance_scale, phi) if guided and phi != 0 else None
-            noise = randn(tuple(z.shape)).to(device=dev, dtype=torch.float32).contiguous() if flags[i][3] else None
-            last = i == n - 1
+
+        def step(i, eps, xt, last):
+            nonlocal x0_prev
+            scale = ops.cfg_rescale_stats(eps, z.shape[1], guidance_scale, phi) if guidance_scale != 1 and phi != 0 else None
+            noise = draw(tuple(z.shape)).to(device=z.device, dtype=torch.float32).contiguous() if flags[i][3] else None
             xin, xt, x0_prev = ops.solver_step(eps, xt, s0[i], s1[i], coef[i], guidance_scale, dt, prediction_type=pt,
-                                               x0p=x0_prev if flags[i][2] else None, noise=noise, scale=scale,
-                                               last=last or mask is not None, x0_out=history[i & 1], need_prev=flags[i][2])
-            if mask is not None and last:
-                xt = ops.masked_renoise(xt, z0, mask, want_input=False, inplace=True)[1]
-            elif mask is not None:
-                xin, xt = ops.masked_renoise(xt, z0, mask, noise=z, a0=s0[i + 1], a1=s1[i + 1], dup=dup, act_dtype=dt, inplace=True)
-        if not return_images:
-            return xt
-        upcast = vae.dtype == torch.float16 and getattr(vae.config, 'force_upcast', False)
-        if upcast:
-            vae.to(dtype=torch.float32)
-        images = vae.decode(xt.to(vae.dtype) / vae.config.scaling_factor, return_dict=False)[0]
-        if upcast:
-            vae.to(dtype=torch.float16)
-        return images.to(torch.float32)
+                                               x0p=x0_prev if flags[i][2] else None, noise=noise, scale=scale, last=last,
+                                               x0_out=history[i & 1], need_prev=flags[i][2])
+            return xin, xt
+        return start, ts, s0, s1, step, lambda i: (s0[i + 1], s1[i + 1])          # the mask re-noises to the level of t_{i+1}
+    return _teacher_loop('teacher_sample_solver_i2i', plan, unet, latents, contexts, negative_contexts, noise_scheduler, text_encoder, tokenizer,
+                         guidance_scale, return_images, vae, init_latents, start_index, mask, control, ip)
