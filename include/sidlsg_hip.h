@@ -733,7 +733,12 @@ int sidlsg_bias_act(const void* x, const void* b, const void* dy, void* out, lon
  * For FROZEN networks: W8 = OCP e4m3 bytes [N][K] with one fp32 scale per output channel (sidlsg_quantize_fp8_rows from
  * the bf16 compute copy); A / X stay bf16 in HBM and are converted to e4m3 in the kernel's loader (static unit scale,
  * saturating); v_mfma_f32_16x16x32_fp8_fp8, fp32 accumulation, C = act(alpha * wscale[n] * acc + bias + rowvec + res).
- * Same remaining arguments as sidlsg_gemm_bf16 / sidlsg_conv3x3_bf16; K (Cin) multiple of 16. */
+ * Same remaining arguments as sidlsg_gemm_bf16 / sidlsg_conv3x3_bf16; K (Cin) multiple of 16.
+ * NaN: every bf16 / fp32 -> e4m3 conversion of this library (sidlsg_cast_fp8, the fp8w loader, the e4m3-output norms,
+ * sidlsg_quantize_fp8_rows) turns a NaN into an e4m3 NaN byte (0x7F / 0xFF), never into a clamped number: a NaN activation
+ * makes every output of its row NaN.  sidlsg_quantize_fp8_rows: scale[r] = max|x| / 448 over the row's non-NaN entries (1 if
+ * that maximum is 0), a NaN entry becomes a NaN byte and leaves the other bytes and the scale of its row unchanged; a row of NaN
+ * only has scale 1.  An infinite entry makes the row's scale infinite, its own byte NaN and every finite entry's byte a zero of its sign. */
 int sidlsg_quantize_fp8_rows(const void* src_bf16, void* dst_fp8, float* scale, int rows, int cols, void* stream);
 int sidlsg_gemm_fp8w(const void* A, int lda, const void* W8, const float* wscale, void* C, int ldc, const float* bias, const void* res,
                      int ldres, const float* rowvec, int ld_rowvec, int rows_per_batch, int M, int N, int K, float alpha,
@@ -744,13 +749,17 @@ int sidlsg_conv3x3_fp8w(const void* X, int ldx, const void* W8, const float* wsc
 /* Both operands e4m3 (MX MFMA v_mfma_scale_f32_16x16x128_f8f6f4 with unit block scales: twice the bf16 rate on gfx950).
  * A8: e4m3 bytes [M][lda] at unit scale -- what the GroupNorm / LayerNorm kernels write with an e4m3 output
  * (sidlsg_cast_fp8 converts a bf16 matrix: clamp to +-448, round to nearest even); W8 / wscale as above.  N % 160 == 0,
- * K % 16 == 0, lda % 16 == 0; the epilogue arguments are those of sidlsg_gemm_bf16. */
+ * K % 16 == 0, lda % 16 == 0; the epilogue arguments are those of sidlsg_gemm_bf16.  sidlsg_cast_fp8: n % 8 == 0; a NaN
+ * element becomes an e4m3 NaN byte ("NaN" under "fp8-weight contractions" above). */
 int sidlsg_cast_fp8(const void* src_bf16, void* dst_fp8, long long n, void* stream);
 /* conv3x3, pad 1, stride 1 on an e4m3 NHWC image (X8: [B][H][Wd][ldx] bytes); W8: [Cout][9 * Cin] e4m3; Cin % 16 == 0,
  * Cout % 160 == 0; rowvec: the per-image row vector (time-embedding broadcast), one row per image. */
 int sidlsg_conv3x3_mx8(const void* X8, int ldx, const void* W8, const float* wscale, void* Y, int ldc, const float* bias, const void* res,
                        int ldres, const float* rowvec, int ld_rowvec, int B, int H, int Wd, int Cin, int Cout, float alpha, int flags,
                        void* stream);
+/* sidlsg_layernorm_fwd / sidlsg_groupnorm_fwd on bf16 x with y8 written as e4m3 bytes at unit scale (clamped to +-448, round to
+ * nearest even); stats as in the bf16 forms.  A NaN in x makes every y8 byte of its row / (sample, group) an e4m3 NaN byte ("NaN"
+ * under "fp8-weight contractions" above). */
 int sidlsg_layernorm_fwd_fp8(const void* x, const float* gamma, const float* beta, void* y8, float* stats, int rows, int C,
                              float eps, void* stream);
 int sidlsg_groupnorm_fwd_fp8(const void* x, const float* gamma, const float* beta, void* y8, float* stats, float* ws, int B,

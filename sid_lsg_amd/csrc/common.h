@@ -153,8 +153,10 @@ template <> DEVFN void stv8<float>(float* p, const float (&v)[8]) {
 
 // ---- OCP e4m3 output (frozen networks: activations written as e4m3 at unit scale for the MX-fp8 contractions) ----
 // explicit clamp to the e4m3 range (v_med3_f32): whether v_cvt_pk_fp8_f32 saturates or returns NaN past +-448 depends on a
-// mode bit this library does not own; NaN inputs stay NaN
-DEVFN float clamp_e4m3(float x) { return __builtin_amdgcn_fmed3f(x, -448.f, 448.f); }
+// mode bit this library does not own.  A NaN input stays NaN (the conversion turns it into an e4m3 NaN byte): the clamp is the
+// IEEE 754-2019 maximum / minimum pair (v_maximum3_f32, v_minimum3_f32 on gfx950), which propagate NaN.  v_med3_f32 -- one
+// instruction less -- returns the smaller bound or the larger by the NaN's sign instead, so a NaN activation became +-448.
+DEVFN float clamp_e4m3(float x) { return __builtin_elementwise_minimum(__builtin_elementwise_maximum(x, -448.f), 448.f); }
 DEVFN unsigned cvt4_fp8(float a, float b, float c, float d) {
     a = clamp_e4m3(a); b = clamp_e4m3(b); c = clamp_e4m3(c); d = clamp_e4m3(d);
     int r = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);

@@ -1,5 +1,6 @@
 """Shared by tests/test_gemm_cases_host.py and tests/test_gpu_gemm_exact.py (not a test module): EXACT cases for the bf16 GEMM / conv3x3 /
-weight-gradient family of csrc/gemm.hip, csrc/wgrad.hip and csrc/gemm_p8.h, the dispatch record every case must produce, and guarded buffers.
+weight-gradient family of csrc/gemm.hip, csrc/wgrad.hip and csrc/gemm_p8.h and for the e4m3 kernels of csrc/gemm_fp8.hip, the dispatch record
+every case must produce, and guarded buffers.
 
 Exact operands.  Activations and dY are integers in [-3, 3], weights integers in [-2, 2], all stored as bf16; bias, row vector and the
 previous contents of an accumulated output are integer-valued fp32, the residual is integer-valued bf16, alpha is 1, 0.5 or 2.  Every
@@ -16,7 +17,14 @@ records without a GPU (the record is written before the launch), the GPU test ch
 Memory around the operands.  Outputs live in a buffer of M + GUARD rows of ldc = N + pad elements filled with a sentinel bit pattern (a
 NaN); inputs have row strides wider than their logical width, the padding columns and GUARD rows after the last row hold NaN; the
 split-K workspace is NaN-filled.  After a call every element outside [0, M) x [0, N) must still be the sentinel and no NaN may have
-reached the output."""
+reached the output.
+
+e4m3 rows (FP8W_CASES, MX8_CASES).  The entry points take the e4m3 BYTES and the per-channel scale vector, so the operands stay exact:
+weights are e4m3 bytes of integers in [-2, 2], activations e4m3 bytes of integers in [-3, 3] (mx8) or bf16 integers the loader converts
+(fp8w), wscale[n] cycles through a short list of powers of two and small integers whose period divides no tile, fragment or wave width.
+Every product, partial sum and wscale[n] * acc is then exact in fp32 in any order and the reference is alpha * wscale[n] * acc followed by
+the same epilogue chain.  Padding bytes and guard rows of an e4m3 operand are 0x7F, the e4m3 NaN: a chunk read past K or Cin that reaches
+the MFMA shows up as a NaN in the output."""
 import ctypes
 import functools
 import os
@@ -25,10 +33,11 @@ import re
 import torch
 import torch.nn.functional as F
 
-BF16, F32, F64 = torch.bfloat16, torch.float32, torch.float64
+BF16, F32, F64, F8 = torch.bfloat16, torch.float32, torch.float64, torch.float8_e4m3fn
 OUT_F32, SILU, ACCUM = 1, 2, 4
 GUARD = 3                          # rows after the last logical row of every guarded buffer
-SENTINEL = {BF16: 0x7FA5, F32: 0x7FA55AA5}          # NaN bit patterns (bf16 as int16, fp32 as int32)
+SENTINEL = {BF16: 0x7FA5, F32: 0x7FA55AA5, F8: 0x7F}          # NaN bit patterns (bf16 as int16, fp32 as int32, e4m3 as uint8)
+INT_OF = {BF16: torch.int16, F32: torch.int32, F8: torch.uint8}
 SILU_TOL = 1.2e-2                  # max|err| / max|ref|, the bf16 bar of tests/test_gpu_ops.py
 WORKSPACE_BYTES = 512 << 20        # what ops.ensure_workspace registers; the dispatch rules depend on it
 
@@ -107,6 +116,7 @@ NO_RV = tuple(f for f in FEATS if 'rv' not in FEATS[f])
 AS_FEATS = ('plain', 'bias', 'bias_res', 'alpha')          # gemm_as_kernel: no row vector, no flags
 BR_FEATS = ('plain', 'bias', 'f32_bias', 'silu')
 FEATS['f32_bias'] = dict(bias=1, f32=1, pad=64)             # sidlsg_conv3x3_br_bf16: bias is its only epilogue operand
+FEATS['f32_plain'] = dict(f32=1, pad=8)                     # the bare scaled accumulator (tests/test_gpu_fp8_bytes.py)
 
 
 def feat_flags(f):
@@ -125,14 +135,17 @@ def rpb_values(M):
     return (100, 24, M)
 
 
-def _dense(M, N, K, expect, feats=ALL_FEATS, p8=-1, g2=False):
-    return dict(ep='gemm', id=f"gemm-{M}x{N}x{K}{'-g2' if g2 else ''}{'-p8=%d' % p8 if p8 >= 0 else ''}", M=M, N=N, K=K, expect=expect, feats=feats, p8=p8, g2=g2)
+# fp8: None (bf16 kernels), 'fp8w' (e4m3 weights, bf16 activations) or 'mx8' (both e4m3); sat: activations past +-448 (fp8w);
+# small_ws: the workspace is set too small for two slabs for the call -> no split-K
+def _dense(M, N, K, expect, feats=ALL_FEATS, p8=-1, g2=False, fp8=None, sat=False, small_ws=False):
+    tag = f"{'-g2' if g2 else ''}{'-p8=%d' % p8 if p8 >= 0 else ''}{'-sat' if sat else ''}{'-smallws' if small_ws else ''}"
+    return dict(ep='gemm', id=f"{fp8 or 'gemm'}-{M}x{N}x{K}{tag}", M=M, N=N, K=K, expect=expect, feats=feats, p8=p8, g2=g2, fp8=fp8, sat=sat, small_ws=small_ws)
 
 
-def _conv(B, Hs, Ws, Cin, Cout, expect, stride=1, ups=0, feats=ALL_FEATS, g2=False, br=False):
-    tag = f"{'-s2' if stride == 2 else ''}{'-ups' if ups else ''}{'-br' if br else ''}{'-g2' if g2 else ''}"
-    return dict(ep='conv_br' if br else 'conv', id=f'conv-{B}x{Hs}x{Ws}x{Cin}-{Cout}{tag}', B=B, Hs=Hs, Ws=Ws, Cin=Cin, Cout=Cout, stride=2 if br else stride,
-                ups=ups, expect=expect, feats=feats, g2=g2, p8=-1)
+def _conv(B, Hs, Ws, Cin, Cout, expect, stride=1, ups=0, feats=ALL_FEATS, g2=False, br=False, fp8=None, small_ws=False):
+    tag = f"{'-s2' if stride == 2 else ''}{'-ups' if ups else ''}{'-br' if br else ''}{'-g2' if g2 else ''}{'-smallws' if small_ws else ''}"
+    return dict(ep='conv_br' if br else 'conv', id=f"{fp8 + 'conv' if fp8 else 'conv'}-{B}x{Hs}x{Ws}x{Cin}-{Cout}{tag}", B=B, Hs=Hs, Ws=Ws, Cin=Cin, Cout=Cout,
+                stride=2 if br else stride, ups=ups, expect=expect, feats=feats, g2=g2, p8=-1, fp8=fp8, sat=False, small_ws=small_ws)
 
 
 GEMM_CASES = (
@@ -199,6 +212,63 @@ CONV_CASES = (
 )
 
 
+_F8W, _F8WC = rec('GEMM_FP8W', 128, 128, 0), rec('GEMM_FP8W', 128, 128, 2)
+
+# gemm_fp8w_kernel: one 128 x 128 tile shape, 64-element K-tiles, no split-K
+FP8W_CASES = (
+    _dense(130, 24, 16, _F8W, fp8='fp8w'),                     # ragged N, K shorter than one K-tile
+    _dense(200, 136, 80, _F8W, fp8='fp8w'),                    # K tail 64 + 16, N one tile and 8 columns
+    _dense(129, 200, 144, _F8W, fp8='fp8w'),
+    _dense(130, 136, 80, _F8W, fp8='fp8w', g2=True),           # halves of 65 rows: the second set starts mid-tile
+    _dense(130, 136, 80, _F8W, fp8='fp8w', sat=True),          # activations past +-448 saturate in the loader
+    _conv(3, 9, 7, 16, 40, _F8WC, stride=2, fp8='fp8w'),
+    _conv(2, 6, 10, 48, 136, _F8WC, ups=1, fp8='fp8w'),
+    _conv(2, 12, 20, 80, 136, _F8WC, fp8='fp8w'),              # Cin = 80: the taps straddle the 64-wide K-tile
+    _conv(2, 12, 20, 80, 136, _F8WC, fp8='fp8w', g2=True),
+)
+
+
+def _mx(mode, splits=1):
+    return rec('GEMM_MX8', 128, 160, mode, splits=splits)
+
+
+# gemm_mx8_kernel: 128 x 160 tiles, 128-byte K-tiles; split-K from 16 K-tiles on (4 per split at least) while fewer than 384 tiles exist
+MX8_CASES = (
+    _dense(130, 160, 16, _mx(0), fp8='mx8'),                   # one 16-byte chunk
+    _dense(300, 320, 144, _mx(0), fp8='mx8'),                  # K = 128 + 16
+    _dense(129, 480, 320, _mx(0), fp8='mx8'),                  # three N tiles; tiles_m = 2 < group_m = 4
+    _dense(700, 160, 128, _mx(0), fp8='mx8'),                  # six M tiles: a raster group of 4, then one of 2
+    _dense(130, 160, 2048, _mx(0, 4), fp8='mx8'),              # nk = 16: 4 splits of 4
+    _dense(130, 320, 2064, _mx(0, 4), fp8='mx8'),              # nk = 17 at 5 per split: 4 splits, the ragged chunk in the last one
+    _dense(260, 160, 144, _mx(0), fp8='mx8', g2=True),
+    _dense(260, 160, 2048, _mx(0, 4), fp8='mx8', g2=True),
+    _conv(3, 9, 7, 16, 160, _mx(1), fp8='mx8'),
+    _conv(2, 12, 20, 48, 160, _mx(1), fp8='mx8'),
+    _conv(1, 10, 6, 144, 320, _mx(1, 4), fp8='mx8'),           # Cin = 128 + 16: nk = 18; the part-filled chunk of a tap runs into the next tap's weights
+    _conv(2, 8, 8, 320, 160, _mx(1, 6), fp8='mx8'),            # nk = 27, one tile: 6 splits, the last one short
+    _conv(1, 10, 6, 144, 320, _mx(1), fp8='mx8', small_ws=True),      # the unsplit K loop over all 18 / 27 K-tiles
+    _conv(2, 8, 8, 320, 160, _mx(1), fp8='mx8', small_ws=True),
+    _conv(4, 9, 7, 48, 160, _mx(1), fp8='mx8', g2=True),
+)
+FP8_CASES = FP8W_CASES + MX8_CASES
+
+# wscale[n] = list[n % len]: exactly representable, and a period (7, 9) that divides none of 4, 8, 16, 80 -- a kernel that reads the scale
+# of channel n + 4, n + 8, n + 16 or of the other wave's half (n + 80) changes the result
+WSCALES = (0.25, 0.5, 1.0, 2.0, 3.0, 4.0, 6.0)
+WSCALES1 = (2.0, 0.25, 6.0, 1.0, 3.0, 0.5, 4.0, 1.0, 0.5)
+SAT_VALUES = (448.0, -448.0, 449.0, 1e4, -3e38)
+MX8_SMALL_WS_BYTES = 64 << 10       # less than two slabs (M N 4 bytes each) of every `small_ws` forward row
+
+
+def wscale_of(N, values):
+    return torch.tensor(values, dtype=F32)[torch.arange(N) % len(values)]
+
+
+def a_pad_of(c, pad):
+    """Padding of the A / X operand (elements = bytes for mx8, where lda % 16 == 0 is required: 0, 16, 64)."""
+    return {0: 0, 8: 16, 64: 64}[pad] if c.get('fp8') == 'mx8' else pad
+
+
 def _wg(M, N, K, expect, **kw):
     return {**dict(ep='wgrad', id=f'wgrad-{M}x{N}x{K}' + ''.join(f'-{k}' for k in kw), M=M, N=N, K=K, expect=expect, small_ws=False, det=False), **kw}
 
@@ -248,15 +318,13 @@ WGRAD_GROUPS = (
          expect=rec('WGRAD_V2SG', 160, 160, 0, splits=5, partial='slabs')),
 )
 
-ALL_CASES = GEMM_CASES + CONV_CASES + WGRAD_CASES + WGRAD_GROUPS
+ALL_CASES = GEMM_CASES + CONV_CASES + FP8W_CASES + MX8_CASES + WGRAD_CASES + WGRAD_GROUPS
 
 # Kernel ids no row of the tables reaches, with the reason (tests/test_gemm_cases_host.py: every other id must appear)
 UNREACHED = {
     'NONE': 'not a kernel: the record before the first launch',
     'GEMM_P8W_GEGLU': 'GEGLU fusion: gelu is not exact (out of scope)',
     'GEMM_P8W_GEGLU_BWD': 'GEGLU fusion: gelu is not exact (out of scope)',
-    'GEMM_MX8': 'e4m3 kernels: the per-row scale makes the rounding order part of the result (out of scope)',
-    'GEMM_FP8W': 'e4m3 kernels: the per-row scale makes the rounding order part of the result (out of scope)',
 }
 
 
@@ -267,7 +335,7 @@ def case_seed(c):
 
 # ---- exact operands ----------------------------------------------------------------------------------------------------------------
 def ints(gen, shape, lo, hi, dtype):
-    """Integers in [lo, hi] as `dtype`; bf16 rounds what it cannot hold (to nearest even: still an integer)."""
+    """Integers in [lo, hi] as `dtype`; bf16 rounds what it cannot hold (to nearest even: still an integer); e4m3 holds every integer up to 16."""
     return torch.randint(lo, hi + 1, shape, generator=gen).to(F32).to(dtype)
 
 
@@ -291,18 +359,27 @@ def fwd_operands(c):
     """The logical operands of a forward case: a / x, w (w1), bias (bias1), rv, res, cprev -- CPU tensors, never modified by a caller."""
     g = torch.Generator().manual_seed(case_seed(c))
     M, N, K = mnk(c)
+    fp8 = c.get('fp8')
+    adt, wdt = (F8 if fp8 == 'mx8' else BF16), (F8 if fp8 else BF16)
     o = {}
     if c['ep'] == 'gemm':
-        o['a'] = ints(g, (M, K), -3, 3, BF16)
+        o['a'] = ints(g, (M, K), -3, 3, adt)
         nb = {r: (M + r - 1) // r for r in rpb_values(M)}
     else:
-        o['a'] = ints(g, (c['B'], c['Hs'], c['Ws'], c['Cin']), -3, 3, BF16)
+        o['a'] = ints(g, (c['B'], c['Hs'], c['Ws'], c['Cin']), -3, 3, adt)
         nb = {M // c['B']: c['B']}
-    o['w'] = ints(g, (N, K), -2, 2, BF16)
+    if c.get('sat'):             # about 1 % of the entries past (or at) the e4m3 range
+        hit = torch.rand(o['a'].shape, generator=g) < 0.01
+        o['a'] = torch.where(hit, torch.tensor(SAT_VALUES)[torch.randint(0, len(SAT_VALUES), o['a'].shape, generator=g)].to(BF16), o['a'])
+    o['w'] = ints(g, (N, K), -2, 2, wdt)
     o['bias'] = ints(g, (N,), -1000, 1000, F32)
+    if fp8:
+        o['wscale'] = wscale_of(N, WSCALES)
     if c['g2']:
-        o['w1'] = ints(g, (N, K), -2, 2, BF16)
+        o['w1'] = ints(g, (N, K), -2, 2, wdt)
         o['bias1'] = ints(g, (N,), -1000, 1000, F32)
+        if fp8:
+            o['wscale1'] = wscale_of(N, WSCALES1)
     o['rv'] = {r: ints(g, (n, N), -300, 300, F32) for r, n in nb.items()}
     o['res'] = ints(g, (M, N), -1000, 1000, BF16)
     o['cprev'] = ints(g, (M, N), -1000, 1000, F32)
@@ -320,7 +397,7 @@ def wgrad_operands(c):
 def conv_taps(x, stride, ups, br=False):
     """x [B, Hs, Ws, C] -> the nine shifted views [B, Ho, Wo, C] (fp64) a 3x3 window reads, tap-major (dh * 3 + dw): pad 1 on all four sides,
     or (br) zero padding on the bottom and right only with stride 2; `ups` reads x through a nearest x2 upsample."""
-    x = x.to(F64)
+    x = x.float().to(F64)
     if ups:
         x = x.repeat_interleave(2, 1).repeat_interleave(2, 2)
     B, H, W, C = x.shape
@@ -333,6 +410,9 @@ def conv_taps(x, stride, ups, br=False):
 
 def contract(c, a, w):
     """A W^T in fp64 -> [M, N]: dense rows, or the 3x3 conv as nine per-tap products (w: [N][9 Cin], tap-major like the kernels' weights)."""
+    a, w = a.float(), w.float()          # (exact: bf16 and e4m3 values are fp32 values)
+    if c.get('fp8') == 'fp8w':           # the loader's saturating conversion; the identity on the integers of every row but `sat`
+        a = a.clamp(-448, 448)
     if c['ep'] == 'gemm':
         return a.to(F64) @ w.to(F64).t()
     Cin = c['Cin']
@@ -349,14 +429,19 @@ def _accumulators(case_id):
     o = fwd_operands(c)
     M = mnk(c)[0]
     acc = contract(c, o['a'], o['w'])
+    if c.get('fp8'):
+        acc = acc * o['wscale'].to(F64)
     if c['g2']:              # rows (samples) of the second half with the second weight set
         acc1 = contract(c, o['a'], o['w1'])
+        if c.get('fp8'):
+            acc1 = acc1 * o['wscale1'].to(F64)
         acc = torch.cat([acc[:M // 2], acc1[M // 2:]])
     return o, acc
 
 
 def fwd_reference(c, feat, rpb=None):
-    """-> (operands, exact fp64 result [M, N] BEFORE the output rounding) of feature set `feat` (a FEATS key)."""
+    """-> (operands, exact fp64 result [M, N] BEFORE the output rounding) of feature set `feat` (a FEATS key); e4m3 rows: the accumulator
+    is wscale[n] * acc."""
     f = FEATS[feat]
     o, acc = _accumulators(c['id'])
     M, N, _ = mnk(c)
@@ -420,7 +505,7 @@ def dgrad_reference(dy, w, x_shape, stride, ups):
 
 # ---- judging a result --------------------------------------------------------------------------------------------------------------
 def bits(t):
-    return t.contiguous().view(torch.int16 if t.dtype == BF16 else torch.int32)
+    return t.contiguous().view(INT_OF[t.dtype])
 
 
 def _low16(x64):
@@ -472,7 +557,7 @@ def silu_mismatch(got, want64):
 def guarded(rows, cols, pad, dtype, device, fill=None):
     """-> (whole, view): `whole` has rows + GUARD rows of cols + pad elements, every element the sentinel; `view` = whole[:rows, :cols] is what
     the kernel gets (pointer view.data_ptr(), row stride cols + pad), filled from `fill` ([rows, cols]) when given."""
-    whole = torch.full((rows + GUARD, cols + pad), SENTINEL[dtype], dtype=torch.int16 if dtype == BF16 else torch.int32, device=device).view(dtype)
+    whole = torch.full((rows + GUARD, cols + pad), SENTINEL[dtype], dtype=INT_OF[dtype], device=device).view(dtype)
     view = whole[:rows, :cols]
     if fill is not None:
         view.copy_(fill.to(device=device, dtype=dtype))
@@ -493,6 +578,10 @@ def poisoned(t2d, pad, device):
     """An input [rows, cols] as the kernel reads it: row stride cols + pad, NaN in the padding columns and in GUARD rows after the last row.
     -> the view [rows, cols] (pointer .data_ptr(), stride .stride(0))."""
     rows, cols = t2d.shape
+    if t2d.dtype == F8:          # (bytes: e4m3 tensors have no fill / copy kernels of their own everywhere)
+        whole = torch.full((rows + GUARD, cols + pad), SENTINEL[F8], dtype=torch.uint8, device=device)
+        whole[:rows, :cols] = t2d.contiguous().view(torch.uint8).to(device)
+        return whole.view(F8)[:rows, :cols]
     whole = torch.full((rows + GUARD, cols + pad), float('nan'), dtype=t2d.dtype, device=device)
     whole[:rows, :cols] = t2d.to(device)
     return whole[:rows, :cols]
@@ -502,8 +591,13 @@ def poisoned_flat(t, device, dtype=None):
     """A contiguous operand followed by GUARD * 8 sentinel elements -> (whole, view of the operand's shape)."""
     dtype = dtype or t.dtype
     n = t.numel()
-    whole = torch.full((n + GUARD * 8,), SENTINEL[dtype], dtype=torch.int16 if dtype == BF16 else torch.int32, device=device).view(dtype)
-    whole[:n] = t.reshape(-1).to(device=device, dtype=dtype)
+    whole = torch.full((n + GUARD * 8,), SENTINEL[dtype], dtype=INT_OF[dtype], device=device)
+    if dtype == F8:
+        whole[:n] = t.reshape(-1).view(torch.uint8).to(device)
+        whole = whole.view(dtype)
+    else:
+        whole = whole.view(dtype)
+        whole[:n] = t.reshape(-1).to(device=device, dtype=dtype)
     return whole, whole[:n].view(t.shape)
 
 
@@ -519,11 +613,12 @@ def fwd_layout(c, feat):
     M, N, K = mnk(c)
     pad = f['pad']
     inner = K if c['ep'] == 'gemm' else c['Cin']
-    return dict(lda=inner + pad, ldc=N + pad, ldres=N + other_pad(pad), ldrv=N + pad)
+    return dict(lda=inner + a_pad_of(c, pad), ldc=N + pad, ldres=N + other_pad(pad), ldrv=N + pad)
 
 
 def fwd_call(c, feat, rpb, p):
-    """-> (entry point name, argument list).  p: addresses a, w, w1, c, bias, bias1, res, rv, stream (None where the feature set has none)."""
+    """-> (entry point name, argument list).  p: addresses a, w, w1, c, bias, bias1, res, rv, stream (None where the feature set has none); e4m3
+    rows also wscale, wscale1: every weight pointer is followed by its scale vector."""
     f = FEATS[feat]
     M, N, K = mnk(c)
     L = fwd_layout(c, feat)
@@ -532,17 +627,22 @@ def fwd_call(c, feat, rpb, p):
     if not f.get('bias'):
         bias = (None,) * len(bias)
     w = (p['w'], p['w1']) if g2 else (p['w'],)
+    fp8 = c.get('fp8')
+    if fp8:
+        w = (p['w'], p['wscale'], p['w1'], p['wscale1']) if g2 else (p['w'], p['wscale'])
+    sfx = f"_{fp8 or 'bf16'}{'_g2' if g2 else ''}"
     res, rv = (p['res'] if f.get('res') else None), (p['rv'] if f.get('rv') else None)
     if c['ep'] == 'gemm':
-        return ('sidlsg_gemm_bf16_g2' if g2 else 'sidlsg_gemm_bf16',
+        return ('sidlsg_gemm' + sfx,
                 [p['a'], L['lda'], *w, p['c'], L['ldc'], *bias, res, L['ldres'] if res else 0, rv, L['ldrv'] if rv else 0, rpb or 1, M, N, K,
                  float(f.get('alpha', 1.0)), feat_flags(f), p['stream']])
     H, W, _, _ = conv_geometry(c)
     if c['ep'] == 'conv_br':
         return 'sidlsg_conv3x3_br_bf16', [p['a'], L['lda'], p['w'], p['c'], L['ldc'], bias[0], c['B'], H, W, c['Cin'], c['Cout'], feat_flags(f), p['stream']]
-    return ('sidlsg_conv3x3_bf16_g2' if g2 else 'sidlsg_conv3x3_bf16',
+    geom = () if fp8 == 'mx8' else (c['stride'], c['ups'])          # sidlsg_conv3x3_mx8: stride 1, no upsampling
+    return ('sidlsg_conv3x3' + sfx,
             [p['a'], L['lda'], *w, p['c'], L['ldc'], *bias, res, L['ldres'] if res else 0, rv, L['ldrv'] if rv else 0, c['B'], H, W, c['Cin'], c['Cout'],
-             c['stride'], c['ups'], float(f.get('alpha', 1.0)), feat_flags(f), p['stream']])
+             *geom, float(f.get('alpha', 1.0)), feat_flags(f), p['stream']])
 
 
 def fwd_runs(c):

@@ -1,4 +1,4 @@
-"""Shared by tests/test_norm_cases_host.py, tests/test_gpu_ops.py and tests/test_gpu_fp32.py (not a test module): GroupNorm /
+"""Shared by tests/test_norm_cases_host.py, tests/test_gpu_ops.py, tests/test_gpu_fp32.py and tests/test_gpu_norm_fp8.py (not a test module): GroupNorm /
 LayerNorm inputs whose (sample, group) blocks -- rows for LayerNorm -- all have DIFFERENT statistics, their fp64 reference, the
 per-block error metric and three deliberately wrong references.
 
@@ -42,6 +42,80 @@ TOL_F32 = dict(y=2e-5, dx=5e-5, dgamma=5e-5, dbeta=5e-5)
 OFFSET_SETS_F32 = (('off30', (0, 3, -10, 30, -30), 1.0), ('off100', (0, 3, -30, 100, -100), 4.0))
 GN_CASES_F32 = ((3, 64, 32, 8, 1, 1e-5, False), (3, 1024, 320, 32, 1, 1e-5, False), (2, 4096, 320, 32, 0, 1e-5, False), (1, 1100, 320, 32, 1, 1e-5, False))
 LN_CASES_F32 = ((100, 320), (257, 1280))
+
+
+# e4m3-output forwards (sidlsg_groupnorm_fwd_fp8 / sidlsg_layernorm_fwd_fp8): the small cases above, judged byte for byte (tests/fp8_cases.py
+# byte_oracle).  An element is decidable when the fp64 reference lies further than d = TOL_F32['y'] * (block max |y|) from every midpoint between
+# neighbouring e4m3 values -- the project's own fp32 bar for the same per-block metric: the kernels compute y in fp32 from the given bf16 x, and an
+# fp32 y within that bar of the reference rounds to the reference's byte.  At most F8_UNDECIDABLE_CAP of a case's elements may be undecidable.
+_F8_GN = ((3, 64, 32, 8, 1), (2, 64, 1280, 32, 1), (2, 100, 80, 8, 0), (3, 1024, 320, 32, 1), (2, 4096, 320, 32, 0), (1, 1100, 320, 32, 1))
+GN_CASES_F8 = tuple(c for c in GN_CASES_BF16 if c[:5] in _F8_GN)
+LN_CASES_F8 = ((100, 320), (257, 1280), (300, 80))
+F8_UNDECIDABLE_CAP = 0.05
+# gamma * F8_SAT_GAIN on one GroupNorm and one LayerNorm case: |y| passes 448 where |xhat gamma| > 7 -- the few outputs where a 3-sigma input
+# meets one of the largest gammas, on either side; they must be the +-448 bytes.  F8_SAT_COUNTS: how many reference outputs round to the +448 /
+# -448 byte in each saturating case (the host test asserts these numbers on the reference, the GPU test counts the kernel's bytes against them)
+F8_SAT_GAIN = 64.0
+GN_CASE_F8_SAT, LN_CASE_F8_SAT = (2, 4096, 320, 32, 0, 1e-5, True), (257, 1280)
+F8_SAT_COUNTS = {'gn': (75, 81), 'ln': (6, 15)}
+# ids of the cases that also run with one NaN input element
+F8_NAN_IDS = ('gn-2-100-80-8-0', 'gn-3-1024-320-32-1', 'ln-300-80', 'ln-257-1280')
+# The statistics an e4m3 forward writes are fp32 (mean, rstd), judged against fp64 on the bf16 x: the mean's error in sigma, rstd's relatively.
+# The bar is what fp32 arithmetic on these inputs can cost, not what the bf16 outputs tolerate: a variance formed as E[x^2] - mean^2 from a block
+# whose mean is `off` standard deviations away works on numbers of size (1 + off^2) sigma^2, every rounding of which is 2^-24 of that relative to
+# sigma^2; rstd moves by half of the variance's relative error.  Four such roundings (sum of squares, its division, mean^2, the subtraction) at
+# the largest offset of OFFSETS_BF16 give 1.07e-4 -- twenty times below a biased / unbiased slip at n = 256 (2e-3).
+F8_STATS_TOL = 4 * 2.0 ** -24 * (1 + max(abs(o) for o in OFFSETS_BF16) ** 2) / 2
+
+
+def block_stats(x, G, eps):
+    """-> (mean, rstd) fp64 [B, G] of x [B, HW, C] (LayerNorm: x.view(rows, 1, C), G = 1)."""
+    B, HW, C = x.shape
+    xg = x.double().view(B, HW, G, C // G)
+    return xg.mean(dim=(1, 3)), torch.rsqrt(xg.var(dim=(1, 3), unbiased=False) + eps)
+
+
+def f8_sat_bounds(y, d):
+    """-> ((lo+, lo-), (hi+, hi-)): how many +448 / -448 bytes a forward within d of the reference y may write -- at least the decidable elements
+    whose nearest-even byte is the saturated one, at most those plus the undecidable ones with it as a neighbour."""
+    import fp8_cases as fc
+    want = fc.ref_bytes(y.double().clamp(-fc.E4M3_MAX, fc.E4M3_MAX).float())
+    dec = fc.decidable(y, d)
+    lo, hi = fc.neighbours(y)
+    out = []
+    for byte in (0x7E, 0xFE):
+        sure = int((dec & (want == byte)).sum())
+        out.append((sure, sure + int((~dec & ((want == byte) | (lo == byte) | (hi == byte))).sum())))
+    return tuple(o[0] for o in out), tuple(o[1] for o in out)
+
+
+def block_d(y, G):
+    """d of the decidable-byte oracle: TOL_F32['y'] * (block max |y|), broadcast to y's shape [B, HW, C]."""
+    B, HW, C = y.shape
+    blk = y.double().abs().view(B, HW, G, C // G).amax(dim=(1, 3), keepdim=True)
+    return (TOL_F32['y'] * blk).expand(B, HW, G, C // G).reshape(B, HW, C)
+
+
+def f8_cases():
+    """-> [(id, kind, case, gain)] of every e4m3-output forward case: kind 'gn' / 'ln'; gain multiplies gamma (the saturating cases)."""
+    out = [('gn-' + gn_id(c), 'gn', c, 1.0) for c in GN_CASES_F8] + [(f'ln-{c[0]}-{c[1]}', 'ln', c, 1.0) for c in LN_CASES_F8]
+    return out + [('gn-' + gn_id(GN_CASE_F8_SAT) + '-sat', 'gn', GN_CASE_F8_SAT, F8_SAT_GAIN), (f'ln-{LN_CASE_F8_SAT[0]}-{LN_CASE_F8_SAT[1]}-sat', 'ln', LN_CASE_F8_SAT, F8_SAT_GAIN)]
+
+
+@functools.lru_cache(maxsize=None)
+def f8_case(kind, case, gain):
+    """dict(x bf16 [B, HW, C], gam, bet, G, eps, silu, y fp64 [B, HW, C], mean, rstd): callers must not modify the tensors."""
+    if kind == 'gn':
+        B, HW, C, G, silu, eps, _ = case
+        x, _ = structured_gn(B, HW, C, G, case_seed(case), OFFSETS_BF16, BF16)
+    else:
+        (B, C), HW, G, silu, eps = case, 1, 1, 0, 1e-5
+        x = structured_ln(B, C, case_seed((B, C, 0, 0, 0)), OFFSETS_BF16, BF16)[0].view(B, 1, C)
+    gam, bet = affine(C)
+    gam = gam * gain
+    y = norm_by_formula(x, torch.zeros_like(x), gam, bet, G, eps, silu)['y']
+    mean, rstd = block_stats(x, G, eps)
+    return dict(x=x, gam=gam, bet=bet, G=G, eps=eps, silu=silu, y=y, mean=mean, rstd=rstd)
 
 
 def gn_id(case):

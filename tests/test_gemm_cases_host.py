@@ -1,5 +1,7 @@
 """tests/gemm_cases.py checked on the CPU: its references against F.conv2d / matmul / autograd in fp64, every case below 2^24 and with
-enough bf16 rounding to notice a wrong rounding mode, its oracle against planted mutants of a correct result, and -- in a child process
+enough bf16 rounding to notice a wrong rounding mode (the e4m3 rows: every operand an e4m3 value, every scaled sum below 2^24), its oracle
+against planted mutants of a correct result (a dropped K chunk, swapped taps, a wrong image's row; for the e4m3 kernels the scale of another
+channel, a wrong halo bit, a part-filled channel chunk that is not zeroed, a dropped split-K slab), and -- in a child process
 that sees no GPU -- the dispatch record of every table row against the kernel the row names."""
 import json
 import os
@@ -13,8 +15,9 @@ import torch.nn.functional as F
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import gemm_cases as gc      # noqa: E402
 
-BF16, F32, F64 = torch.bfloat16, torch.float32, torch.float64
+BF16, F32, F64, F8 = torch.bfloat16, torch.float32, torch.float64, torch.float8_e4m3fn
 FWD = gc.GEMM_CASES + gc.CONV_CASES
+FP8_CONV = tuple(c for c in gc.FP8_CASES if c['ep'] == 'conv')
 ids = lambda cases: [c['id'] for c in cases]      # noqa: E731
 
 
@@ -22,10 +25,10 @@ ids = lambda cases: [c['id'] for c in cases]      # noqa: E731
 def torch_conv(c, x, w):
     """F.conv2d in fp64 on the NCHW view of a case's operands -> [M, N]."""
     Cin, Cout = c['Cin'], c['Cout']
-    xi = x.to(F64).permute(0, 3, 1, 2)
+    xi = x.float().to(F64).permute(0, 3, 1, 2)
     if c['ups']:
         xi = F.interpolate(xi, scale_factor=2, mode='nearest')
-    wt = w.to(F64).view(Cout, 3, 3, Cin).permute(0, 3, 1, 2)
+    wt = w.float().to(F64).view(Cout, 3, 3, Cin).permute(0, 3, 1, 2)
     if c['ep'] == 'conv_br':
         y = F.conv2d(F.pad(xi, (0, 1, 0, 1)), wt, stride=2)
     else:
@@ -33,7 +36,7 @@ def torch_conv(c, x, w):
     return y.permute(0, 2, 3, 1).reshape(-1, Cout)
 
 
-@pytest.mark.parametrize('c', gc.CONV_CASES, ids=ids(gc.CONV_CASES))
+@pytest.mark.parametrize('c', gc.CONV_CASES + FP8_CONV, ids=ids(gc.CONV_CASES + FP8_CONV))
 def test_conv_reference_is_conv2d(c):
     o = gc.fwd_operands(c)
     assert torch.equal(gc.contract(c, o['a'], o['w']), torch_conv(c, o['a'], o['w']))
@@ -100,6 +103,68 @@ def test_forward_case_is_exact_and_rounds(c):
             if N * M >= 1000:
                 up = gc.tie_goes_up(x)
                 assert (tie & up).any() and (tie & ~up).any(), 'ties must go both ways (to even)'
+
+
+def _abs_sum(c, a, w):
+    """max over the outputs of sum_k |a_k| |w_k| (a as the loader converts it): no partial sum of any order exceeds it."""
+    return gc.contract(c, a.float().abs().to(a.dtype), w.float().abs().to(w.dtype)).max().item()
+
+
+@pytest.mark.parametrize('c', gc.FP8_CASES, ids=ids(gc.FP8_CASES))
+def test_fp8_case_is_exact_and_rounds(c):
+    o = gc.fwd_operands(c)
+    M, N, K = gc.mnk(c)
+    mx8 = c['fp8'] == 'mx8'
+    assert o['w'].dtype == F8 and o['a'].dtype == (F8 if mx8 else BF16)
+    # every operand is what its bytes say: integers that survive the e4m3 round trip unchanged (the fp8w activations as the loader converts them)
+    a = o['a'].float()
+    if c['sat']:
+        big = a.abs() >= 448
+        assert 0.003 < big.float().mean().item() < 0.03 and (a.abs() > 448).any(), 'the sat row needs entries at and past +-448'
+        assert set(a[big].clamp(-448, 448).tolist()) == {448.0, -448.0}
+        a = a.clamp(-448, 448)
+        small = a[~big]
+    else:
+        small = a
+    assert small.abs().max() <= 3 and torch.equal(small, small.round())
+    assert torch.equal(a.to(F8).float(), a)
+    for k in ('w', 'w1') if c['g2'] else ('w',):
+        wf = o[k].float()
+        assert wf.abs().max() <= 2 and torch.equal(wf, wf.round()) and torch.equal(wf.to(F8).float(), wf)
+    # the scales: exactly representable with two significant bits, a period that divides no tile, fragment or wave width
+    for vals in (gc.WSCALES, gc.WSCALES1):
+        assert all(len(vals) % d and d % len(vals) for d in (4, 8, 16, 80)) and all(v * 4 == int(v * 4) and v in (0.25, 0.5, 1, 2, 3, 4, 6) for v in vals)
+    assert torch.equal(o['wscale'], gc.wscale_of(N, gc.WSCALES)) and (not c['g2'] or torch.equal(o['wscale1'], gc.wscale_of(N, gc.WSCALES1)))
+    for d in (4, 8, 16, 80):
+        if N > d:
+            assert not torch.equal(o['wscale'][d:], o['wscale'][:-d]), f'a scale read {d} channels off would go unnoticed'
+    bound = max(_abs_sum(c, o['a'], o[k]) for k in (('w', 'w1') if c['g2'] else ('w',)))
+    assert bound * max(gc.WSCALES + gc.WSCALES1) * 2 + 4000 < 2 ** 24, bound      # alpha <= 2; bias + row vector + residual + previous contents < 4000
+    if c['small_ws']:
+        assert 2 * M * N * 4 > gc.MX8_SMALL_WS_BYTES
+    for feat, rpb in gc.fwd_runs(c):
+        f = gc.FEATS[feat]
+        _, x = gc.fwd_reference(c, feat, rpb)
+        assert x.shape == (M, N)
+        if f.get('silu'):
+            continue
+        gc.round_out(x, F32)                        # asserts exactness in fp32
+        if not f.get('f32') and f.get('bias'):
+            frac = gc.needs_rounding(x).double().mean().item()
+            tie = gc.is_tie(x)
+            assert frac >= 0.10 and tie.any(), f'{c["id"]} {feat}: {frac:.3f} of the outputs need rounding, {int(tie.sum())} ties'
+            if N * M >= 1000:
+                up = gc.tie_goes_up(x)
+                assert (tie & up).any() and (tie & ~up).any(), 'ties must go both ways (to even)'
+
+
+def test_fp8_rows_cover_both_epilogues_split_and_unsplit():
+    """bf16 outputs leave gemm_mx8_kernel through its LDS ring, fp32 / accumulating ones through the direct epilogue: both on split and unsplit rows."""
+    for split in (False, True):
+        rows = [c for c in gc.MX8_CASES if (c['expect']['splits'] > 1) == split]
+        for ep in ('gemm', 'conv'):
+            assert any(c['ep'] == ep and {'plain', 'all', 'f32', 'accum'} <= set(c['feats']) for c in rows), (split, ep)
+    assert all(set(c['feats']) == set(gc.ALL_FEATS) for c in gc.FP8_CASES)
 
 
 @pytest.mark.parametrize('c', gc.WGRAD_CASES, ids=ids(gc.WGRAD_CASES))
@@ -185,6 +250,66 @@ def test_mutant_truncation_instead_of_rne():
     assert torch.equal(gc.bits(bad)[exact], gc.bits(want)[exact])          # (the mutant is right wherever nothing needs rounding)
 
 
+def _rejected(bad64, x64):
+    """Both output types must tell the mutant from the result."""
+    return all(gc.exact_mismatch(gc.round_out(bad64, t), gc.round_out(x64, t)) != '' for t in (BF16, F32))
+
+
+def test_mutant_scale_of_channel_n_plus_4():
+    for cid in ('mx8-130x160x16', 'fp8w-200x136x80', 'mx8conv-3x9x7x16-160'):
+        c = _case(cid)
+        o, x = gc.fwd_reference(c, 'bias')
+        acc = gc.contract(c, o['a'], o['w'])
+        assert torch.equal(acc * o['wscale'].double() + o['bias'].double(), x)
+        for d in (4, 8, 16, 80):
+            if d < c.get('N', c.get('Cout')):
+                assert _rejected(acc * o['wscale'].roll(-d).double() + o['bias'].double(), x), (cid, d)
+
+
+def test_mutant_halo_tap_dropped_at_an_image_corner():
+    """One bit of gemm_mx8_kernel's 9-bit halo mask wrong for one pixel: the top-left pixel of the second image loses its right neighbour."""
+    c = _case('mx8conv-2x12x20x48-160')
+    o, x = gc.fwd_reference(c, 'plain')
+    Cin, m = c['Cin'], 12 * 20                                               # row m: image 1, pixel (0, 0)
+    tap = 1 * 3 + 2                                                          # (dh, dw) = (1, 2): input pixel (0, 1), inside the image
+    lost = o['a'].float().double()[1, 0, 1] @ o['w'].float().double()[:, tap * Cin:(tap + 1) * Cin].t() * o['wscale'].double()
+    assert (lost != 0).any()
+    bad = x.clone()
+    bad[m] -= lost
+    assert _rejected(bad, x)
+    # and the opposite error: a tap outside the image (its memory holds the last pixel of image 0) read instead of zero
+    tap = 1 * 3 + 0
+    extra = o['a'].float().double()[0, 11, 19] @ o['w'].float().double()[:, tap * Cin:(tap + 1) * Cin].t() * o['wscale'].double()
+    bad = x.clone()
+    bad[m] += extra
+    assert (extra != 0).any() and _rejected(bad, x)
+
+
+def test_mutant_partial_channel_chunk_meets_the_next_taps_weights():
+    """Cin = 144 = 128 + 16: the second channel chunk of a tap holds 16 channels; the W tile's other 112 columns are the NEXT tap's weights of
+    channels 0 .. 111.  The mutant lets the A lanes past Cin read on (into the next pixel's channels 0 .. 111) instead of zeros, for the centre tap."""
+    for cid in ('mx8conv-1x10x6x144-320', 'mx8conv-1x10x6x144-320-smallws'):
+        c = _case(cid)
+        o, x = gc.fwd_reference(c, 'plain')
+        Cin, M = c['Cin'], gc.mnk(c)[0]
+        xf = torch.cat([o['a'].float().double().reshape(M, Cin), torch.zeros(1, Cin, dtype=F64)])
+        extra = xf[1:, :112] @ o['w'].float().double()[:, 5 * Cin:5 * Cin + 112].t() * o['wscale'].double()
+        assert _rejected(x + extra, x)
+
+
+def test_mutant_last_splits_slab_dropped():
+    c = _case('mx8-130x320x2064')
+    assert c['expect']['splits'] == 4
+    o, x = gc.fwd_reference(c, 'bias')
+    a = o['a'].float()
+    a[:, 3 * 5 * 128:] = 0                                                   # 17 K-tiles at 5 per split: the last split holds tiles 15 and 16
+    bad = gc.contract(c, a.to(F8), o['w']) * o['wscale'].double() + o['bias'].double()
+    assert _rejected(bad, x)
+    a = o['a'].float()
+    a[:, 2048:] = 0                                                          # only the ragged last chunk (16 bytes)
+    assert _rejected(gc.contract(c, a.to(F8), o['w']) * o['wscale'].double() + o['bias'].double(), x)
+
+
 @pytest.mark.parametrize('dtype', [BF16, F32])
 def test_mutant_writes_outside_the_output(dtype):
     M, N, pad = 37, 24, 8
@@ -246,7 +371,7 @@ def _worker():
     lib.load()
     raw = ctypes.create_string_buffer(4096 + 16)
     ptr = (ctypes.addressof(raw) + 15) & ~15
-    P = {k: ptr for k in ('a', 'w', 'w1', 'c', 'bias', 'bias1', 'res', 'rv', 'dy', 'dw', 'db')}
+    P = {k: ptr for k in ('a', 'w', 'w1', 'wscale', 'wscale1', 'c', 'bias', 'bias1', 'res', 'rv', 'dy', 'dw', 'db')}
     P['stream'] = None
     lib.sidlsg_set_workspace.raw(ptr, gc.WORKSPACE_BYTES)
     assert gc.last_launch(lib)['kernel'] == 'NONE'
@@ -264,8 +389,11 @@ def _worker():
         recs = []
         if c['ep'] in ('gemm', 'conv', 'conv_br'):
             old = lib.sidlsg_debug_set_p8.raw(c['p8'])
+            if c['small_ws']:
+                lib.sidlsg_set_workspace.raw(ptr, gc.MX8_SMALL_WS_BYTES)
             for feat, rpb in gc.fwd_runs(c):
                 recs.append((f'{feat}/{rpb}', call(*gc.fwd_call(c, feat, rpb, P))))
+            lib.sidlsg_set_workspace.raw(ptr, gc.WORKSPACE_BYTES)
             lib.sidlsg_debug_set_p8.raw(old)
         elif c['ep'] in ('wgrad', 'wgrad_conv'):
             if c['small_ws']:

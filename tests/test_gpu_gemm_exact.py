@@ -1,4 +1,5 @@
-"""The bf16 GEMM / conv3x3 / weight-gradient kernels of csrc/gemm.hip, csrc/wgrad.hip and csrc/gemm_p8.h on the EXACT cases of tests/gemm_cases.py: for
+"""The bf16 GEMM / conv3x3 / weight-gradient kernels of csrc/gemm.hip, csrc/wgrad.hip and csrc/gemm_p8.h and the e4m3 GEMM / conv3x3 kernels of
+csrc/gemm_fp8.hip on the EXACT cases of tests/gemm_cases.py: for
 every table row the dispatch record must name the row's kernel, the result must equal the fp64 reference bit for bit (rounded once to
 bf16, to nearest even, where the output is bf16), the sentinel around the output must be intact and no NaN of the poisoned padding,
 guard rows or workspace may have reached the output.  Then the data-gradient chains of ops._conv_dgrad and one autograd pass each of
@@ -49,8 +50,8 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
-@pytest.mark.parametrize('c', gc.GEMM_CASES + gc.CONV_CASES, ids=ids(gc.GEMM_CASES + gc.CONV_CASES))
-def test_forward_row(dev, ws, c):
+def _forward_row(dev, ws, c):
+    """Every call of a forward row (bf16 or e4m3): record, guard zones, no NaN, bit-equality."""
     from sid_lsg_amd._lib import lib
     M, N, K = gc.mnk(c)
     o, _ = gc.fwd_reference(c, 'plain')
@@ -62,6 +63,10 @@ def test_forward_row(dev, ws, c):
     if c['g2']:
         _, w1 = gc.poisoned_flat(o['w1'], dev)
         _, bias1 = gc.poisoned_flat(o['bias1'], dev)
+    scales = {}
+    if c['fp8']:                 # the scale vectors, NaN behind their last channel
+        scale_bufs = {k: gc.poisoned_flat(o[k], dev)[1] for k in ('wscale', 'wscale1') if k in o}
+        scales = {k: v.data_ptr() for k, v in scale_bufs.items()}
     errors = []
     old = lib.sidlsg_debug_set_p8.raw(c['p8'])
     try:
@@ -70,7 +75,7 @@ def test_forward_row(dev, ws, c):
             L = gc.fwd_layout(c, feat)
             pad = f['pad']
             if pad not in a_pad:
-                a_pad[pad] = gc.poisoned(a2d, pad, dev)
+                a_pad[pad] = gc.poisoned(a2d, gc.a_pad_of(c, pad), dev)
             a = a_pad[pad]
             res = rv = None
             if f.get('res'):
@@ -85,10 +90,17 @@ def test_forward_row(dev, ws, c):
             whole, out = gc.guarded(M, N, pad, dtype, dev, fill=o['cprev'] if f.get('accum') else None)
             assert a.stride(0) == L['lda'] and out.stride(0) == L['ldc'] and (res is None or res.stride(0) == L['ldres']) and (rv is None or rv.stride(0) == L['ldrv'])
             p = dict(a=a.data_ptr(), w=w.data_ptr(), w1=w1.data_ptr() if c['g2'] else None, c=out.data_ptr(), bias=bias.data_ptr(),
-                     bias1=bias1.data_ptr() if c['g2'] else None, res=None if res is None else res.data_ptr(), rv=None if rv is None else rv.data_ptr(), stream=_stream())
+                     bias1=bias1.data_ptr() if c['g2'] else None, res=None if res is None else res.data_ptr(), rv=None if rv is None else rv.data_ptr(), stream=_stream(),
+                     **scales)
             name, args = gc.fwd_call(c, feat, rpb, p)
             ws.poison()
-            getattr(lib, name)(*args)
+            if c['small_ws']:
+                ws.shrink(gc.MX8_SMALL_WS_BYTES)
+            try:
+                getattr(lib, name)(*args)
+            finally:
+                if c['small_ws']:
+                    ws.shrink(gc.WORKSPACE_BYTES)
             got_rec = gc.last_launch(lib)
             torch.cuda.synchronize()
             label = f"{c['id']} [{feat}/{rpb}]"
@@ -103,6 +115,17 @@ def test_forward_row(dev, ws, c):
     finally:
         lib.sidlsg_debug_set_p8.raw(old)
     assert not errors, '\n'.join(errors)
+
+
+@pytest.mark.parametrize('c', gc.GEMM_CASES + gc.CONV_CASES, ids=ids(gc.GEMM_CASES + gc.CONV_CASES))
+def test_forward_row(dev, ws, c):
+    _forward_row(dev, ws, c)
+
+
+@pytest.mark.parametrize('c', gc.FP8_CASES, ids=ids(gc.FP8_CASES))
+def test_fp8_forward_row(dev, ws, c):
+    """The e4m3 rows: operands as bytes, 0x7F (e4m3 NaN) in every padding byte and guard row of an e4m3 operand."""
+    _forward_row(dev, ws, c)
 
 
 def _wgrad_buffers(o, assign, dev):

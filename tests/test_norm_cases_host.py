@@ -96,6 +96,55 @@ def test_layernorm_f32_cases(case, name, offsets, factor):
     _check_torch_f32(t32, c['ref'], rel, tol, f'ln {rows}-{C} {name}')
 
 
+F8_CASES = nc.f8_cases()
+
+
+def test_e4m3_case_lists_are_complete():
+    """The lists are filtered out of GN_CASES_BF16 and of the ids: an edit there must not drop a case silently."""
+    ids = [c[0] for c in F8_CASES]
+    assert len(nc.GN_CASES_F8) == 6 and len(nc.LN_CASES_F8) == 3 and len(F8_CASES) == 11 and len(set(ids)) == 11
+    assert len(nc.F8_NAN_IDS) == 4 and set(nc.F8_NAN_IDS) <= set(ids)
+    assert sum(c[3] != 1.0 for c in F8_CASES) == 2
+    assert 1.0e-4 < nc.F8_STATS_TOL < 1.1e-4
+
+
+@pytest.mark.parametrize('cid,kind,case,gain', F8_CASES, ids=[c[0] for c in F8_CASES])
+def test_e4m3_forward_cases(cid, kind, case, gain):
+    """The byte oracle of the e4m3-output forwards on the reference alone: the undecidable share stays under the cap, the reference's own bytes
+    pass, bytes of a forward that used the next group's / next sample's statistics do not, and the saturating cases saturate."""
+    import fp8_cases as fc
+    c = nc.f8_case(kind, case, gain)
+    x, y, G = c['x'], c['y'], c['G']
+    B = x.shape[0]
+    zero = torch.zeros_like(x)
+    auto = nc.gn_reference(x, zero, c['gam'], c['bet'], G, c['eps'], c['silu'])['y']
+    assert nc.group_rel_err(y, auto, G) < 1e-12, 'the written-out formula differs from F.group_norm'
+    d = nc.block_d(y, G)
+    msg, share = fc.byte_oracle(fc.ref_bytes(y.float()), y, d)
+    sat = min(int((y >= 448).sum()), int((y <= -448).sum()))
+    print(f'  {cid}: undecidable {100 * share:.2f} %, saturated outputs per sign >= {sat}')
+    assert msg == '' and share <= nc.F8_UNDECIDABLE_CAP, (msg, share)
+    if gain != 1.0:
+        want = fc.ref_bytes(y.float())
+        assert (int((want == 0x7E).sum()), int((want == 0xFE).sum())) == nc.F8_SAT_COUNTS[kind] and sat >= 5
+        lo, hi = nc.f8_sat_bounds(y, d)
+        assert all(0 < a <= b for a, b in zip(lo, hi)) and all(a <= n <= b for a, n, b in zip(lo, nc.F8_SAT_COUNTS[kind], hi)), (lo, hi)
+    else:
+        assert y.abs().max() < 448
+    for m in (['next_group'] if G > 1 else []) + (['next_sample'] if B > 1 else []):
+        bad = nc.norm_by_formula(x, zero, c['gam'], c['bet'], G, c['eps'], c['silu'], mutation=m)['y']
+        msg, _ = fc.byte_oracle(fc.ref_bytes(bad.float()), y, d)
+        assert 'decidable' in msg and int(msg.split(' of ')[0]) > 0.2 * y.numel(), f'{m}: {msg!r}'
+    # (the third wrong reference of this file, no_projection, only changes dx: the forward it describes is the right one)
+    assert torch.equal(nc.norm_by_formula(x, zero, c['gam'], c['bet'], G, c['eps'], c['silu'], mutation='no_projection')['y'], y)
+    # the bf16 forward's bar on the statistics notices the same two mutations
+    mean, rstd = c['mean'], c['rstd']
+    for shift, dims in ((1, G > 1), (0, B > 1)):
+        if dims:
+            e = max(((mean.roll(-1, shift) - mean).abs() * rstd).max().item(), (rstd.roll(-1, shift) / rstd - 1).abs().max().item())
+            assert e > 10 * nc.F8_STATS_TOL
+
+
 def test_every_offset_and_scale_is_used():
     """The generator's promise: each case sees every offset of its list and more than one scale."""
     for case in nc.GN_CASES_BF16:
